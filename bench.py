@@ -1,6 +1,6 @@
 """bench.py — headline benchmark: MPC + KKT-sensitivity solves per second, cartpole N=20, batch 4096 per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1 without a launcher: bench.py re-executes itself under
      python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...; under a launcher
      (WORLD_SIZE set) it is one rank of that job)
@@ -17,6 +17,14 @@ round 5 ran 40 untimed "settle" steps and the HBM-peak probe in front of the war
 after ~20 of these 0.5 ms steps), which this round reports as the separate `steady_state` field, measured by a second window AFTER the
 headline's.  The other configurations of BASELINE.json (chain n_mass 5 / 7, linear system, the TD3 closed loop) are measured after
 both through the same timed_steps and attached as `secondary` (median of three windows; they keep their disclosed settle steps).
+
+A plain run does only what its headline figure needs: set-up, W warm-ups, the K timed steps, the outputs (--dump-outputs) and the
+line.  Everything else it measures — the `steady_state` window, the measured HBM peak (`roofline.peak_measured`), the `secondary`
+configurations and the `cpu_baseline` — takes runs of its own and comes only with --full.
+
+--dump-outputs DIR: after the timed steps, what the last timed step returned to its caller (the solver's u0*, V, status, iteration
+counts, dV/dp, du0*/dp; for td3 the agent's theta, theta', observations and critic parameters) is written as DIR/<name>.npy in
+float32 / float64 (integer outputs as exact float64), so that two builds can be compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -252,8 +260,32 @@ def dry_line(args, world, rccl_ranks, elapsed, metric, secondary=None):
                       **({"secondary": secondary} if secondary is not None else {})}), flush=True)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def solve_outputs(r):
+    """The arrays a caller of MPCBatch.solve receives (SolveResult), by name."""
+    return {k: getattr(r, k) for k in ("u0", "V", "status", "iters", "dV_dp", "dpi_dp") if getattr(r, k) is not None}
+
+
+def dump_outputs(out_dir, arrays, rank):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64 as computed, integers as exact float64); the ranks > 0 of a
+    multi-GPU job write <name>_rank<r>.npy beside rank 0's."""
+    host = {}
+    for k, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ("" if rank == 0 else f"_rank{rank}") + ".npy"), a)
+
+
 def chain_measure(n_mass, B, sens, steps, warmup, world, rank, dist, dev):
-    """One chain_mass measurement through timed_steps: (job seconds, HIP-event ms per step, summary dict for the JSON line, ocp, x0).
+    """One chain_mass measurement through timed_steps: (job seconds, HIP-event ms per step, summary dict for the JSON line, ocp, x0,
+    result of the last timed step).
     x0 = masses on the x axis (examples/chain_mass.py:17-25) + N(0, 1e-2) velocity perturbation, seed = rank."""
     from mpc4rl_amd import MPCBatch, chain_mass_ocp
     from mpc4rl_amd.distributed import allreduce_weighted_grad
@@ -293,7 +325,7 @@ def chain_measure(n_mass, B, sens, steps, warmup, world, rank, dist, dev):
                          "fp64": {"achieved": fp64, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": fp64 / FP64_MFMA_PEAK_TFLOPS,
                                   "note": "SURVEY.md 8d: sweeps/s x F_sweep, sweeps = interior-point iterations + 1 + nu"}}}
     del mpc
-    return elapsed, kern_ms, summ, ocp, x0
+    return elapsed, kern_ms, summ, ocp, x0, r
 
 
 def chain_bench(args):
@@ -311,12 +343,15 @@ def chain_bench(args):
         if rank == 0:
             dry_line(args, world, rccl_ranks, elapsed, metric)
         return finish_ranks(dist)
-    elapsed, kern_ms, summ, ocp, x0 = chain_measure(n_mass, B, sens, args.steps, args.warmup, world, rank, dist, dev)
+    elapsed, kern_ms, summ, ocp, x0, r = chain_measure(n_mass, B, sens, args.steps, args.warmup, world, rank, dist, dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solve_outputs(r), rank)
     if rank == 0:
         nx, nu, N, n_th = ocp.nx, ocp.nu, ocp.N, ocp.n_p
-        peak_meas = measured_hbm_peak(dev)
         roof = dict(summ["roofline"])
-        roof.update({"peak_measured": peak_meas, "frac_of_measured": (roof["achieved"] / peak_meas) if peak_meas else None})
+        if args.full:
+            peak_meas = measured_hbm_peak(dev)
+            roof.update({"peak_measured": peak_meas, "frac_of_measured": (roof["achieved"] / peak_meas) if peak_meas else None})
         out = {"metric": metric, "value": summ["value"],
                "unit": "solves/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "settle_steps": summ["settle_steps"], "ms_per_step": summ["ms_per_step"],
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
@@ -328,7 +363,7 @@ def chain_bench(args):
                "roofline": roof}
         if rccl_ranks is not None:
             out["rccl_ranks"] = rccl_ranks
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             from oracle.problems import make_chain_mass
             out["cpu_baseline"] = cpu_baseline_guarded(make_chain_mass(n_mass=n_mass), x0, sens, label=f"chain_mass n_mass={n_mass}: ")
         print(json.dumps(out), flush=True)
@@ -336,7 +371,8 @@ def chain_bench(args):
 
 
 def small_measure(linear, B, sens, rti, steps, warmup, world, rank, dist, dev, settle_kind="small"):
-    """One cartpole / linear-system measurement through timed_steps: (job seconds, summary dict, ocp, x0, statuses, iteration counts)."""
+    """One cartpole / linear-system measurement through timed_steps: (job seconds, summary dict, ocp, x0, statuses, iteration counts,
+    result of the last timed step)."""
     from mpc4rl_amd import MPCBatch, cartpole_ocp, linear_system_ocp
     from mpc4rl_amd.distributed import allreduce_weighted_grad
     n_theta = 12 if linear else N_THETA
@@ -388,7 +424,7 @@ def small_measure(linear, B, sens, rti, steps, warmup, world, rank, dist, dev, s
                                   "note": "SURVEY.md 8d: sweeps/s x F_sweep, sweeps = interior-point iterations + 1 + nu; the path is a "
                                           "serial dependency chain, not flop-bound"}}}
     del mpc
-    return elapsed, summ, ocp, x0_np, status, iters
+    return elapsed, summ, ocp, x0_np, status, iters, r
 
 
 SECONDARY = (("chain5", 10, 3), ("chain7", 5, 2), ("linear", 50, 5), ("td3", 20, 5))   # (workload, steps, warm-ups): BASELINE configs 4, 1, 5
@@ -505,9 +541,9 @@ def count_ranks(dist_mod, dev):
 
 
 def td3_measure(E, steps, warmup, graphs, world, rank, dist, dev, settle, replay_iterates=True, pipeline=False):
-    """One TD3 closed-loop measurement through timed_steps: (job seconds, summary dict).  A step = one environment step of all E
-    environments + one TD3 update (batch E per rank); MPC solves per step and rank: E warm (roll-out actor) + E cold (target actor)
-    + E / policy_delay cold with du0*/dtheta (policy gradient)."""
+    """One TD3 closed-loop measurement through timed_steps: (job seconds, summary dict, the agent's state after the last timed step).
+    A step = one environment step of all E environments + one TD3 update (batch E per rank); MPC solves per step and rank: E warm
+    (roll-out actor) + E cold (target actor) + E / policy_delay cold with du0*/dtheta (policy gradient)."""
     from mpc4rl_amd import BatchedCartPoleSwingUpEnv, BatchedTD3, cartpole_ocp
     env = BatchedCartPoleSwingUpEnv(E, device=dev, seed=rank)
     agent = BatchedTD3(cartpole_ocp(), env, batch_size=E, buffer_steps=64, policy_delay=2, lr_actor=1e-6, seed=0, device=dev,
@@ -524,6 +560,8 @@ def td3_measure(E, steps, warmup, graphs, world, rank, dist, dev, settle, replay
         step()
     agent.collect(0)                       # zero the roll-out statistics
     elapsed, _, _ = timed_steps(step, argparse.Namespace(steps=steps, warmup=0), dist, dev, rank)
+    state = {"theta": agent.theta.clone(), "theta_target": agent.theta_target.clone(), "obs": agent.obs.clone(),
+             "critic_params": torch.cat([p.detach().reshape(-1) for p in agent.critic.parameters()])}
     st = agent.last_stats()
     tr = {"critic_loss": agent.last_critic_loss()} if agent._graphs else agent.train(1)
     solves = world * steps * (E + E + E / agent.policy_delay)
@@ -543,7 +581,7 @@ def td3_measure(E, steps, warmup, graphs, world, rank, dist, dev, settle, replay
             "replay_launch_shape": {"target_actor": list(agent.target_mpc.mpc.launch_times()), "policy": list(agent.pi_mpc.mpc.launch_times()),
                                     "rollout_warm": list(agent.actor.mpc.launch_times(warm=True))}}
     del agent, env
-    return elapsed, summ
+    return elapsed, summ, state
 
 
 def td3_bench(args):
@@ -560,8 +598,10 @@ def td3_bench(args):
             dry_line(args, world, rccl_ranks, elapsed, metric)
         return finish_ranks(dist)
     settle = SETTLE["td3"] if SETTLE_OVERRIDE is None else SETTLE_OVERRIDE
-    elapsed, summ = td3_measure(args.batch, args.steps, args.warmup, not args.no_graph, world, rank, dist, dev, settle,
-                                replay_iterates=not args.cold_replay, pipeline=args.td3_pipeline)
+    elapsed, summ, state = td3_measure(args.batch, args.steps, args.warmup, not args.no_graph, world, rank, dist, dev, settle,
+                                       replay_iterates=not args.cold_replay, pipeline=args.td3_pipeline)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, state, rank)
     if rank == 0:
         print(json.dumps({
             "metric": metric, "value": summ["value"],
@@ -583,12 +623,16 @@ def main():
     ap.add_argument("--batch", type=int, default=B_PER_GPU)
     ap.add_argument("--no-sens", action="store_true", help="forward solve only (BASELINE config 2)")
     ap.add_argument("--rti", action="store_true", help="one SQP iteration from the stored iterate (build-side mode)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the steady_state window, "
+                    "the measured HBM peak, the secondary configurations and the CPU baseline (a plain run does none of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned "
+                    "as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--settle", type=int, default=-1, help="untimed steps before the W warm-ups that bring an idle GPU to its sustained "
-                    "clocks (reported as settle_steps); -1 = per workload (headline 0 + a separate steady_state window, linear 40, "
-                    "chain 3, TD3 10), 0 = none anywhere")
-    ap.add_argument("--no-secondary", action="store_true", help="headline run: skip the chain5 / chain7 / linear figures measured after "
-                    "the headline's timed region and attached to the line as `secondary`")
+                    "clocks (reported as settle_steps); -1 = per workload (headline 0 + with --full a separate steady_state window, "
+                    "linear 40, chain 3, TD3 10), 0 = none anywhere")
+    ap.add_argument("--no-secondary", action="store_true", help="--full headline run: skip the chain5 / chain7 / linear / td3 figures "
+                    "measured after the headline's timed region and attached to the line as `secondary`")
     ap.add_argument("--no-graph", action="store_true", help="td3 workload: eager launches instead of replayed HIP graphs")
     ap.add_argument("--td3-pipeline", action="store_true", help="td3 workload, one rank, graphs on: BatchedTD3(pipeline=True) — the update runs beside the "
                     "roll-out step of the same call (pipelined actor / learner: the sampler leaves out the slot being written; same work per step)")
@@ -616,7 +660,7 @@ def main():
     sens = not args.no_sens
     metric = ("MPC+KKT-sens solves/sec, %s batch=%d" if sens else "MPC solves/sec, %s batch=%d") % (
         "linear_system N=40" if linear else "cartpole N=20", B)
-    want_secondary = not args.no_secondary and not linear and world == 1 and sens and not args.rti and B == B_PER_GPU
+    want_secondary = args.full and not args.no_secondary and not linear and world == 1 and sens and not args.rti and B == B_PER_GPU
     if DRY:
         elapsed, _, _ = timed_steps(None, args, dist, dev, rank)
         sec = secondary_lines(world, rank, dist, dev) if want_secondary else None
@@ -625,19 +669,22 @@ def main():
         return finish_ranks(dist)
     # The headline: the driver's contract and nothing else — W warm-ups, then EXACTLY K timed steps (no settle steps, the HBM probe
     # after the region).  With W = 5, K = 20 the 10 ms window sits on the clock ramp of a GPU that was idle; what the
-    # same binary does once the clocks have settled is measured by a SECOND window after it and reported as `steady_state`, a
+    # same binary does once the clocks have settled is measured (--full) by a SECOND window after it and reported as `steady_state`, a
     # separately labelled field that never feeds `value` / `ms_per_step`.
     headline = not linear
-    elapsed, summ, ocp, x0_np, status, iters = small_measure(linear, B, sens, args.rti, args.steps, args.warmup, world, rank, dist, dev,
-                                                             settle_kind="headline" if headline else "small")
-    steady = None
-    if headline and SETTLE_OVERRIDE is None:
+    elapsed, summ, ocp, x0_np, status, iters, r = small_measure(linear, B, sens, args.rti, args.steps, args.warmup, world, rank, dist, dev,
+                                                                settle_kind="headline" if headline else "small")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solve_outputs(r), rank)
+    steady, peak_meas = None, None
+    if args.full and headline and SETTLE_OVERRIDE is None:
         s_el, s_summ = small_measure(linear, B, sens, args.rti, args.steps, args.warmup, world, rank, dist, dev, settle_kind=STEADY_SETTLE)[:2]
         steady = {"ms_per_step": s_summ["ms_per_step"], "value": s_summ["value"], "unit": "solves/s", "settle_steps": STEADY_SETTLE,
                   "steps": args.steps, "warmup": args.warmup, "kernel_ms": s_summ["roofline"]["kernel_ms"],
                   "note": "the same workload and W / K measured again after the headline's region and %d more untimed steps (sustained "
                           "clocks): round 5's headline protocol; not part of value / ms_per_step" % STEADY_SETTLE}
-    peak_meas = measured_hbm_peak(dev)
+    if args.full:
+        peak_meas = measured_hbm_peak(dev)
     # the headline's timed region is over: the other configurations are measured after it, never inside it
     sec = secondary_lines(world, rank, dist, dev) if want_secondary else None
 
@@ -646,11 +693,11 @@ def main():
         # matrix-core work of the factor sweep: 6 v_mfma_f64_4x4x4 block-products (128 flop each) per stage step and instance
         mfma_tflops = 0.0 if linear else float(iters[:, 1].sum()) * ocp.N * 6 * 128 / (kern_ms * 1e-3) / 1e12
         roof = dict(summ["roofline"])
-        roof.update({"peak_measured": peak_meas, "frac_of_measured": (roof["achieved"] / peak_meas) if peak_meas else None,
-                     "mfma_f64_hw": {"achieved": mfma_tflops, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                     "frac": mfma_tflops / FP64_MFMA_PEAK_TFLOPS,
-                                     "note": "hardware flops of the 6 v_mfma_f64_4x4x4 per factor-sweep stage step (padded 4x4x4 "
-                                             "products; vector sweeps excluded): the MFMAs of the recursion wait on each other"}})
+        if args.full:
+            roof.update({"peak_measured": peak_meas, "frac_of_measured": (roof["achieved"] / peak_meas) if peak_meas else None})
+        roof["mfma_f64_hw"] = {"achieved": mfma_tflops, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": mfma_tflops / FP64_MFMA_PEAK_TFLOPS,
+                               "note": "hardware flops of the 6 v_mfma_f64_4x4x4 per factor-sweep stage step (padded 4x4x4 "
+                                       "products; vector sweeps excluded): the MFMAs of the recursion wait on each other"}
         out = {
             "metric": metric,
             "value": summ["value"], "unit": "solves/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "settle_steps": summ["settle_steps"],
@@ -666,7 +713,7 @@ def main():
         }
         if rccl_ranks is not None:
             out["rccl_ranks"] = rccl_ranks   # an all-reduce of ones over the job's communicator: how many ranks RCCL really joined
-        if world == 1 and not args.no_cpu:
+        if world == 1 and args.full and not args.no_cpu:
             from oracle.problems import make_cartpole, make_linear_system
             out["cpu_baseline"] = cpu_baseline_guarded(make_linear_system(gamma=0.99) if linear else make_cartpole(), x0_np, sens)
         if steady is not None:

@@ -47,18 +47,39 @@ def test_gpus_1_stays_in_process():
 
 
 def test_headline_line_carries_the_secondary_configurations():
-    """The driver only runs `bench.py --gpus 1`: the chain (BASELINE config 4), linear-system (config 1) and TD3 (config 5) figures ride on that ONE
+    """`bench.py --gpus 1 --full`: the chain (BASELINE config 4), linear-system (config 1) and TD3 (config 5) figures ride on that ONE
     line as `secondary`, measured by the same timed_steps AFTER the headline's timed region (its ms_per_step must not contain them);
-    `--no-secondary` and every non-headline workload leave the field out."""
+    a plain run, `--no-secondary` and every non-headline workload leave the field out."""
     import bench
-    line = _run(1)
+    line = _run(1, extra_args=["--full"])
     sec = line["secondary"]
     assert set(sec) == {wl for wl, _, _ in bench.SECONDARY} == {"chain5", "chain7", "linear", "td3"}
     for wl, steps, warmup in bench.SECONDARY:
         assert sec[wl]["steps"] == steps and sec[wl]["warmup"] == warmup and sec[wl]["ms_per_step"] >= 1.0
     assert line["ms_per_step"] < 5.0                 # 1 ms sleeps: the ~90 secondary steps are not in the headline's region
-    assert "secondary" not in _run(1, workload="linear") and "secondary" not in _run(2)
-    assert "secondary" not in _run(1, extra_args=["--no-secondary"])
+    assert "secondary" not in _run(1, workload="linear", extra_args=["--full"]) and "secondary" not in _run(2, extra_args=["--full"])
+    assert "secondary" not in _run(1, extra_args=["--full", "--no-secondary"])
+    assert "secondary" not in _run(1)                # a plain run times the headline and nothing else
+
+
+def test_dump_outputs_writes_float_npy_files(tmp_path):
+    """--dump-outputs: one <name>.npy per output, floats as computed, integers as exact float64, rank > 0 suffixed, 64 MB at most."""
+    import numpy as np
+    import pytest
+    import torch
+    import bench
+    st = torch.tensor([0, 2, 4], dtype=torch.int32)
+    v = torch.tensor([1.5, -2.0], dtype=torch.float64)
+    o = torch.tensor([0.25], dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path), {"status": st, "V": v, "obs": o}, 0)
+    bench.dump_outputs(str(tmp_path), {"V": v}, 1)
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["V.npy", "V_rank1.npy", "obs.npy", "status.npy"]
+    a = np.load(tmp_path / "status.npy")
+    assert a.dtype == np.float64 and a.tolist() == [0.0, 2.0, 4.0]
+    assert np.load(tmp_path / "V.npy").dtype == np.float64 and np.load(tmp_path / "obs.npy").dtype == np.float32
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros(bench.DUMP_MAX_BYTES // 8 + 1, dtype=torch.float64)}, 0)
+    assert not (tmp_path / "big").exists()
 
 
 def test_traffic_figure_is_bound_to_the_kernel_sources(tmp_path, monkeypatch):
