@@ -27,6 +27,12 @@
  *     rlmpc/mpc/nlp.py:1354-1372, rlmpc/examples/chain_mass.py:119-120
  *   the one warm solver object SB3's replay loop reuses          mpcrl_get_iterate_rows / mpcrl_set_iterate_rows
  *     rlmpc/td3/policies.py:186-213                              (per-transition iterates of a replay buffer)
+ *   perturb_action + env.step + replay_buffer.add of the        mpcrl_qlearning_cartpole_collect
+ *   cartpole Q-learning roll-out
+ *     scripts/cartpole_mpc_qlearning.py:104-107,223-234
+ *   td_error, dp = LR td dQ_dp, np.mean(dp) of the learning   mpcrl_qlearning_td_grad / mpcrl_qlearning_td_workspace_bytes,
+ *   sweep; mpc.set_p(p + mean)                                  mpcrl_qlearning_apply
+ *     scripts/cartpole_mpc_qlearning.py:255-269
  *
  * Conventions
  *   - plain C, no torch types.  Every array argument of mpcrl_solve / *_iterate / mpcrl_reset /
@@ -74,8 +80,10 @@ extern "C" {
  *        agree with the one-stage kernel and the oracle port to the QP tolerance (1e-4 ... 1e-3 on du0/dp), not to rounding
  *   120  round 6: mpcrl_solve flags MPCRL_NO_BND_STORE and MPCRL_EXACT_QP (test-only); mpcrl_get_iterate_rows / mpcrl_set_iterate_rows; mpcrl_policy_action
  *   130  round 6: mpcrl_critic_td_grad / mpcrl_critic_workspace_bytes / mpcrl_critic_dq_da (the TD3 learner's critic step); mpcrl_replay_sample; mpcrl_dpg_grad / mpcrl_dpg_workspace_bytes; mpcrl_td3_cartpole_collect; mpcrl_td3_policy_post; linear system: a
- *        failed WARM QP restarts cold (behaviour, see above) */
-#define MPCRL_ABI_VERSION 130
+ *        failed WARM QP restarts cold (behaviour, see above)
+ *   131  round 7: mpcrl_qlearning_cartpole_collect; mpcrl_qlearning_td_grad / mpcrl_qlearning_td_workspace_bytes; mpcrl_qlearning_apply
+ *        (the batched Q-learning loop of the cartpole); nothing existing changed */
+#define MPCRL_ABI_VERSION 131
 
 enum { MPCRL_MODEL_CARTPOLE = 0, MPCRL_MODEL_LINEAR = 1, MPCRL_MODEL_CHAIN = 2 };
 /* how the stage-cost scaling c_k is built (rlmpc/mpc/nlp.py:1044-1055 vs 1083-1091) */
@@ -336,6 +344,40 @@ int mpcrl_td3_cartpole_collect(const double *par, int E, double *state, int64_t 
  * tau theta;  crit_target = (1 - tau) crit_target + tau crit (float [n_crit], the flat critic parameters; n_crit may be 0). */
 int mpcrl_td3_policy_post(const double *msg, int n_theta, double lr, const double *mask, double tau, double *theta, double *theta_target,
                           double *step_out, const float *crit, float *crit_target, int n_crit, void *stream);
+
+/* ABI 131.  One roll-out step of the batched cartpole Q-learning loop after the policy's solve, one launch (qlearning_kernel.hpp), one lane per
+ * environment, nu = 1 — what scripts/cartpole_mpc_qlearning.py:223-234 does per step after mpc.get_action: for an environment that is
+ * alive, a = clip(scale_action(u0) + sigma eps, -1, 1) in float (mpcrl_policy_action with accept_status2 and noise_clip 0: a failed solve
+ * gives 0 before the noise), the environment step (mpcrl_env_cartpole_step), and its liveness: terminated, or truncated at
+ * max_episode_steps, at this step = this row is recorded and the environment is dead from the next one on (it is not stepped again).
+ * Row t = row[env] of the episode table, for every environment: S [T][E][4] = s_t (the state BEFORE the step — the reference stores
+ * s_{t+1} there, obs = next_obs before replay_buffer.add, lines 229-231; the TD formula means s_t), A [T][E] = unscale_action(a) =
+ * 0.5 (hi - lo) (a + 1) + lo, C [T][E] = x^2 + theta^2 of the new state, live [T][E] = 1; a dead environment's row holds its final state,
+ * A = C = 0 and live = 0.  row [E] int32 advances by one (a row >= T is not written: the call is then a no-op for that environment);
+ * alive [E] uint8 in / out; obs [E][4] double (may be NULL) = the state after the call (the next solve's x0); cold [E] int32 (may be NULL)
+ * = 0.  state / steps as mpcrl_env_cartpole_step, par its nine doubles; eps [T][E] float, row t read at step t; lo < hi = lbu, ubu. */
+int mpcrl_qlearning_cartpole_collect(const double *par, int E, int T, double *state, int64_t *steps, const double *u0, const int32_t *status,
+                                     const float *eps, double lo, double hi, double sigma, double *obs, uint8_t *alive, int32_t *row, int32_t *cold,
+                                     double *S, double *A, double *C, uint8_t *live, void *stream);
+
+/* ABI 131.  The TD step of one episode of the cartpole Q-learning loop, one launch (qlearning_kernel.hpp): scripts/cartpole_mpc_qlearning.py
+ * lines 255-269 for E environments.  Sample rows i < T - 1 of the learning sweep: Q, V [T-1][E], dQ_dp [T-1][E][n_p], status_q,
+ * status_v [T-1][E] (the Q solve with u0 fixed and the V solve); cost, live [T][E] (the collect's table).  Terms j = i E + e, i < T - 2:
+ *   valid_j = live[i][e], live[i+1][e], live[i+2][e] (live is a prefix per environment, so this is i + 1 < L_e - 1 with L_e the rows the
+ *             environment recorded: the reference's size - 1 samples and td[:-1]) and the four solves of rows i, i + 1 returned 0;
+ *   td_j    = (cost_j + gamma V[i+1][e]) - Q_j   -> td [T-2][E] (0 where not valid);  valid [T-2][E] uint8 (may be NULL);
+ *   msg [n_p + 2] = [sum_j w_j dQ_dp_j, sum_j w_j, sum_j valid_j] with w_j = valid_j ? lr td_j : 0 — selected, never multiplied by a mask
+ *             (Q / V of a failed solve may be NaN); dQ_dp read as nan_to_num does.  The layout of distributed.allreduce_weighted_grad.
+ * workspace: mpcrl_qlearning_td_workspace_bytes(T, E, n_p) bytes of device memory, ZERO before the first call (the call leaves it zero).
+ * Fixed summation order (no floating-point atomics): the same inputs give the same bits.  T >= 2 (T = 2: no term, msg = 0). */
+int64_t mpcrl_qlearning_td_workspace_bytes(int T, int E, int n_p);
+int mpcrl_qlearning_td_grad(const double *Q, const double *V, const double *dQ_dp, const int32_t *status_q, const int32_t *status_v, const double *cost,
+                            const uint8_t *live, int T, int E, int n_p, double gamma, double lr, void *workspace, double *td, uint8_t *valid, double *msg,
+                            void *stream);
+
+/* ABI 131.  After the collective: step_i = mask_i != 0 ? msg_i / max(1, msg[n_theta + 1]) : 0 (mask [n_theta] double, NULL = all), the mean of
+ * distributed.mean_update; theta += step; step_out [n_theta] = step (mpc.set_p(mpc.get_p() + np.mean(dp)), script lines 263-269). */
+int mpcrl_qlearning_apply(const double *msg, int n_theta, const double *mask, double *theta, double *step_out, void *stream);
 
 /* Bytes of device memory held by the handle; library version (MPCRL_ABI_VERSION of the header it was built from). */
 int64_t mpcrl_workspace_bytes(mpcrl_handle h);

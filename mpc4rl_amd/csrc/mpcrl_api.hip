@@ -19,6 +19,7 @@
 #include "critic_kernel.hpp"
 #include "replay_kernel.hpp"
 #include "td3_kernel.hpp"
+#include "qlearning_kernel.hpp"
 
 using namespace mpcrl;
 
@@ -680,6 +681,57 @@ int mpcrl_td3_policy_post(const double *msg, int n_theta, double lr, const doubl
     const int n = n_theta > n_crit ? n_theta : n_crit;
     hipLaunchKernelGGL(td3_policy_post_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, msg, n_theta, lr, mask, tau, theta, theta_target,
                        step_out, crit, crit_target, n_crit);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int mpcrl_qlearning_cartpole_collect(const double *par, int E, int T, double *state, int64_t *steps, const double *u0, const int32_t *status,
+                                     const float *eps, double lo, double hi, double sigma, double *obs, uint8_t *alive, int32_t *row, int32_t *cold,
+                                     double *S, double *A, double *C, uint8_t *live, void *stream) {
+    if (!par || E < 1 || T < 1 || !state || !steps || !u0 || !status || !eps || !alive || !row || !S || !A || !C || !live || !(hi > lo))
+        return MPCRL_E_ARG;
+    ON_DEVICE_OF(state);
+    QlCollectArgs a;
+    a.par.gravity = par[0], a.par.masscart = par[1], a.par.masspole = par[2], a.par.length = par[3], a.par.force_mag = par[4], a.par.tau = par[5];
+    a.par.x_threshold = par[6], a.par.theta_threshold = par[7], a.par.max_episode_steps = (long)par[8];
+    a.E = E, a.T = T, a.state = state, a.steps = steps, a.u0 = u0, a.status = (const int *)status, a.eps = eps, a.lo = lo, a.hi = hi;
+    a.sigma = (float)sigma, a.obs = obs, a.alive = alive, a.row = row, a.cold = cold, a.S = S, a.A = A, a.C = C, a.live = live;
+    hipLaunchKernelGGL(qlearning_cartpole_collect_kernel, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int64_t mpcrl_qlearning_td_workspace_bytes(int T, int E, int n_p) {
+    if (T < 2 || E < 1 || n_p < 1) return MPCRL_E_ARG;
+    const int64_t M = (int64_t)(T - 2) * E;
+    return 16 + ((M + TD_ROWS - 1) / TD_ROWS) * (n_p + 2) * (int64_t)sizeof(double);
+}
+
+int mpcrl_qlearning_td_grad(const double *Q, const double *V, const double *dQ_dp, const int32_t *status_q, const int32_t *status_v, const double *cost,
+                            const uint8_t *live, int T, int E, int n_p, double gamma, double lr, void *workspace, double *td, uint8_t *valid, double *msg,
+                            void *stream) {
+    if (!msg || T < 2 || E < 1 || n_p < 1) return MPCRL_E_ARG;
+    const int64_t M = (int64_t)(T - 2) * E;
+    if (M > 0 && (!Q || !V || !dQ_dp || !status_q || !status_v || !cost || !live || !workspace || !td)) return MPCRL_E_ARG;
+    ON_DEVICE_OF(msg);
+    if (M == 0) {   // no term: an empty message
+        HIP_OK(hipMemsetAsync(msg, 0, (size_t)(n_p + 2) * sizeof(double), (hipStream_t)stream));
+        return 0;
+    }
+    if ((M + TD_ROWS - 1) / TD_ROWS > 0x7fffffff) return MPCRL_E_ARG;
+    QlTdArgs a;
+    a.Q = Q, a.V = V, a.dQ = dQ_dp, a.sq = (const int *)status_q, a.sv = (const int *)status_v, a.cost = cost, a.live = live;
+    a.T = T, a.E = E, a.n_p = n_p, a.gamma = gamma, a.lr = lr, a.td = td, a.valid = valid;
+    a.ticket = (unsigned int *)workspace, a.partial = (double *)((char *)workspace + 16), a.msg = msg;
+    hipLaunchKernelGGL(qlearning_td_grad_kernel, dim3((unsigned)((M + TD_ROWS - 1) / TD_ROWS)), dim3(TD_ROWS), 0, (hipStream_t)stream, a);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int mpcrl_qlearning_apply(const double *msg, int n_theta, const double *mask, double *theta, double *step_out, void *stream) {
+    if (!msg || n_theta < 1 || !theta || !step_out) return MPCRL_E_ARG;
+    ON_DEVICE_OF(theta);
+    hipLaunchKernelGGL(qlearning_apply_kernel, dim3((n_theta + 255) / 256), dim3(256), 0, (hipStream_t)stream, msg, n_theta, mask, theta, step_out);
     HIP_OK(hipGetLastError());
     return 0;
 }
