@@ -82,8 +82,10 @@ extern "C" {
  *   130  round 6: mpcrl_critic_td_grad / mpcrl_critic_workspace_bytes / mpcrl_critic_dq_da (the TD3 learner's critic step); mpcrl_replay_sample; mpcrl_dpg_grad / mpcrl_dpg_workspace_bytes; mpcrl_td3_cartpole_collect; mpcrl_td3_policy_post; linear system: a
  *        failed WARM QP restarts cold (behaviour, see above)
  *   131  round 7: mpcrl_qlearning_cartpole_collect; mpcrl_qlearning_td_grad / mpcrl_qlearning_td_workspace_bytes; mpcrl_qlearning_apply
- *        (the batched Q-learning loop of the cartpole); nothing existing changed */
-#define MPCRL_ABI_VERSION 131
+ *        (the batched Q-learning loop of the cartpole); nothing existing changed
+ *   132  mpcrl_td3_policy_post: a masked entry (mask_i == 0) is selected out, step_i = 0, instead of multiplied by 0 — a NaN or +-inf
+ *        message there no longer turns a frozen theta_i into NaN (behaviour; the signature is unchanged) */
+#define MPCRL_ABI_VERSION 132
 
 enum { MPCRL_MODEL_CARTPOLE = 0, MPCRL_MODEL_LINEAR = 1, MPCRL_MODEL_CHAIN = 2 };
 /* how the stage-cost scaling c_k is built (rlmpc/mpc/nlp.py:1044-1055 vs 1083-1091) */
@@ -339,9 +341,11 @@ int mpcrl_td3_cartpole_collect(const double *par, int E, double *state, int64_t 
                                const double *u01, double lo, double hi, int scale, double sigma, double *obs, int32_t *ended, float *table, int cap,
                                double reward_scale, int64_t *pos, uint8_t *iter_ok, int64_t *iter_rows, double *stats, void *workspace, void *stream);
 
-/* ABI 130.  The policy half of a TD3 update after the collective, one launch: msg [n_theta + 1] double = the all-reduced theta-gradient
- * sum and sample count;  step = lr * mask * msg / max(1, count) -> step_out;  theta += step;  theta_target = (1 - tau) theta_target +
- * tau theta;  crit_target = (1 - tau) crit_target + tau crit (float [n_crit], the flat critic parameters; n_crit may be 0). */
+/* ABI 130 (132: masked entries selected out).  The policy half of a TD3 update after the collective, one launch: msg [n_theta + 1] double
+ * = the all-reduced theta-gradient sum and sample count;  step = mask != 0 ? lr * mask * msg / max(1, count) : 0 -> step_out (a masked
+ * entry is selected out, never multiplied: a non-finite message there leaves theta alone);  theta += step;  theta_target =
+ * (1 - tau) theta_target + tau theta;  crit_target = (1 - tau) crit_target + tau crit (float [n_crit], the flat critic parameters;
+ * n_crit may be 0, crit / crit_target then NULL). */
 int mpcrl_td3_policy_post(const double *msg, int n_theta, double lr, const double *mask, double tau, double *theta, double *theta_target,
                           double *step_out, const float *crit, float *crit_target, int n_crit, void *stream);
 

@@ -96,14 +96,15 @@ __global__ void __launch_bounds__(256) td3_cartpole_collect_kernel(const Td3Coll
 }
 
 // After the collective, every policy_delay-th update (BatchedTD3._update_post): the policy step from the all-reduced message
-//     step = lr * mask * g / max(1, count);  theta += step;  theta' = (1 - tau) theta' + tau theta
-// and the Polyak update of the target critics, critic' = (1 - tau) critic' + tau critic — nine framework launches — in one.
+//     step = mask != 0 ? lr * mask * g / max(1, count) : 0;  theta += step;  theta' = (1 - tau) theta' + tau theta
+// and the Polyak update of the target critics, critic' = (1 - tau) critic' + tau critic — nine framework launches — in one.  A masked
+// entry is selected out, never multiplied: a non-finite message there must not move a frozen parameter.
 __global__ void __launch_bounds__(256) td3_policy_post_kernel(const double *msg, int n_theta, double lr, const double *mask, double tau, double *theta,
                                                               double *theta_target, double *step_out, const float *crit, float *crit_target, int n_crit) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n_theta) {
         const double cnt = msg[n_theta] > 1.0 ? msg[n_theta] : 1.0;
-        const double st = lr * mask[i] * msg[i] / cnt;
+        const double st = mask[i] != 0.0 ? lr * mask[i] * msg[i] / cnt : 0.0;
         const double th = theta[i] + st;
         theta[i] = th, step_out[i] = st;
         theta_target[i] = theta_target[i] * (1.0 - tau) + tau * th;

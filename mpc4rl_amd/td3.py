@@ -692,7 +692,8 @@ class BatchedTD3:
             if push_theta:
                 self._push_theta()
         elif do_policy:
-            step = self.lr_actor * self.learn_mask * flat[self.n_crit: self.n_crit + n_theta] / flat[-1].clamp(min=1.0)
+            step = torch.where(self.learn_mask != 0, self.lr_actor * self.learn_mask * flat[self.n_crit: self.n_crit + n_theta] / flat[-1].clamp(min=1.0),
+                               0.0)     # selected, as mpcrl_td3_policy_post does: a non-finite message does not move a frozen entry
             self.theta.add_(step)
             self.theta_target.mul_(1.0 - self.tau).add_(self.theta, alpha=self.tau)
             if push_theta:

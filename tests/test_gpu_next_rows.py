@@ -652,7 +652,10 @@ def _critic_reference(critic, target, rows, nx, nu, a_next, ok_u, gamma, dtype):
     return loss.detach(), torch.cat([p.grad.reshape(-1) for p in cr.parameters()]), ok_b
 
 
-@pytest.mark.parametrize("B,nx,nu,n_critics", [(4096, 4, 1, 2), (257, 4, 1, 2), (37, 9, 3, 1), (16, 2, 1, 2), (5, 33, 3, 2)])
+@pytest.mark.parametrize("B,nx,nu,n_critics", [(4096, 4, 1, 2), (257, 4, 1, 2), (37, 9, 3, 1), (16, 2, 1, 2), (5, 33, 3, 2),
+                                                # D = nx + nu = 16 (the last four-wavefront case, every input in registers), 17 (the
+                                                # first single-wavefront one), 64 = CRITIC_DMAX, one critic on that path with nu = 8
+                                                (50, 15, 1, 2), (50, 16, 1, 2), (33, 60, 4, 2), (17, 40, 8, 1)])
 def test_critic_td_grad_and_dq_da_vs_autograd(B, nx, nu, n_critics):
     """mpcrl_critic_td_grad / mpcrl_critic_dq_da (round 6, ABI 130): the TD target, the twin-critic loss, its gradient with respect to the
     critics' parameters and dQ_1/da — hand-written forward and backward passes of the [obs | action] -> 64 -> 64 -> 1 MLPs — against torch

@@ -12,13 +12,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["mpcrl_qlearning_cartpole_collect", "mpcrl_qlearning_td_workspace_bytes", "mpcrl_qlearning_td_grad", "mpcrl_qlearning_apply"]
 
 
-def test_new_symbols_in_header_and_binding():
+def test_new_symbols_in_header_and_binding_abi132():
+    """The Q-learning symbols are declared and bound; header and binding agree on ABI 132 (mpcrl_td3_policy_post selects masked
+    entries out)."""
     from mpc4rl_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "mpcrl.h")).read()
     for name in NEW:
         assert re.search(r"\b" + name + r"\(", hdr), name
         assert name in _lib.EXPORTS, name
-    assert int(re.search(r"#define MPCRL_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 131
+    assert int(re.search(r"#define MPCRL_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 132
 
 
 def _script_loop(q, v, dq, sq, sv, cost, L, gamma, lr):
