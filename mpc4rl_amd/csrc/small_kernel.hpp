@@ -106,16 +106,7 @@ MPCRL_DI double lane_select(unsigned long long mask, double yes, double no) {
     return __hiloint2double(rh, rl);
 }
 constexpr unsigned long long LANES_C0 = 0x1111111111111111ull, LANES_C1 = 0x2222222222222222ull, LANES_C01 = 0x3333333333333333ull;   // lane & 3 == 0 / == 1 / < 2
-#ifndef MPCRL_V_ASMSEL
-#define MPCRL_V_ASMSEL 1
-#endif
 
-#ifndef MPCRL_SMALL_SCAN
-#define MPCRL_SMALL_SCAN 1      // vector sweeps of the stage-per-lane layout as parallel scans (SmallSolver::SCAN)
-#endif
-#ifndef MPCRL_IPM_SCALE_RES
-#define MPCRL_IPM_SCALE_RES 1
-#endif
 // segmented reductions over the LPI lanes of one instance; result broadcast to all of its lanes
 // SKIP (a model constant, M::SEG_SKIP): leave out the tree levels at which no lane has a partner (s >= lpi, wave-uniform).  One
 // cross-lane round trip less per reduction on paper; measured with everything else equal it is 2.3 % SLOWER for the cartpole kernels
@@ -707,11 +698,7 @@ struct SmallSolver {
             X1 = mfma4(Pm, o.ah.x, 0.0);
         };
         auto tail = [&](const MxOps &o, double Y, double X1, bool pin) {
-#if MPCRL_V_ASMSEL
             const double Am = o.ah.x, CZc = lane_select(LANES_C01, o.cp.y, 0.0);
-#else
-            const double Am = o.ah.x, CZc = c < 2 ? o.cp.y : 0.0;
-#endif
             const double Yb = quad_bcast<0>(Y);
             const double Zc = mfma4(Am, Y, CZc);
             const double Zb = mfma4(o.Br, Y, o.rp.x);
@@ -723,20 +710,11 @@ struct SmallSolver {
             const double Kr = Sr * Rinv;
             Pm = fma(-Kr, Zr, Qt);                              // P_k = Q - K S'
             const double t = fma(-Kr, Zb, Zc);                  // own column: p_k (c = 1), q_k (c = 2)
-#if MPCRL_V_ASMSEL
             pcol = lane_select(LANES_C1, t, 0.0);
-#else
-            pcol = c == 1 ? t : 0.0;
-#endif
             const double kf = mvu * Rinv;
             const double dk = fma(-o.Br, kf, o.cp.x);           // c = 1: bb[r] - B[r] kff
-#if MPCRL_V_ASMSEL
             sV1 = lane_select(LANES_C0, Kr, lane_select(LANES_C1, dk, t));       // K[r] | d[r] | q[r]
             sV2 = lane_select(LANES_C0, Rinv, lane_select(LANES_C1, kf, Zb));    // 1/R | kff | beta
-#else
-            sV1 = c == 0 ? Kr : (c == 1 ? dk : t);              // K[r] | d[r] | q[r]
-            sV2 = c == 0 ? Rinv : (c == 1 ? kf : Zb);           // 1/R | kff | beta
-#endif
             sV3 = t;
         };
         auto store = [&](int kk) {
@@ -891,29 +869,15 @@ struct SmallSolver {
     }
     bool mx_dyn_dirty = true;   // (kept for the stage-layout path's linearize; the matrix-layout path republishes everything)
 
-    // ---- backward sweep over the horizon (serial in k; the lanes of all instances in the wave step together).
-    // (P, p) of stage k+1 arrive by a one-lane shift.  For the vector-only sweeps (corrector, extra right-hand sides) the
-    // product P_{k+1} bb_k is formed beforehand, stage-parallel, by the lane that owns P_{k+1}, so only NX values travel.
-    template <bool FACTOR, class HF>
+    // ---- backward factor sweep over the horizon (serial in k; the lanes of all instances in the wave step together).
+    // (P, p) of stage k+1 arrive by a one-lane shift.  The vector-only sweeps on the stored factors are backward_scan below.
+    template <class HF>
     MPCRL_DI bool backward(HF Hs, const double *g, const double *bb) {
         // Every lane executes every stage step (full EXEC mask).
         bool ok = true;
         double hb[NX];
-        if constexpr (!FACTOR) {
-            double bbp[NX];
 #pragma unroll
-            for (int i = 0; i < NX; ++i) bbp[i] = lane_up(bb[i]);
-#pragma unroll
-            for (int i = 0; i < NX; ++i) {
-                double a = 0.0;
-#pragma unroll
-                for (int j = 0; j < NX; ++j) a = fma(P[sym(i, j)], bbp[j], a);
-                hb[i] = a;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NX; ++i) hb[i] = 0.0;
-        }
+        for (int i = 0; i < NX; ++i) hb[i] = 0.0;
         // No commit/select is needed: a lane whose stage is already final recomputes it from its (final) neighbour and gets the
         // same bits again; a lane whose turn has not come yet computes throw-away values that its own turn overwrites.
         for (int kk = N; kk >= 0; --kk) {
@@ -921,16 +885,10 @@ struct SmallSolver {
 #pragma unroll
             for (int i = 0; i < NX; ++i) pn[i] = lane_dn(p[i] + hb[i]);
             double Pn[NPK];
-            if constexpr (FACTOR) {
 #pragma unroll
-                for (int i = 0; i < NPK; ++i) Pn[i] = lane_dn(P[i]);
-                const bool okk = riccati_stage<true>(Pn, pn, Hs, g, bb);
-                ok = ok && (okk || k != kk);
-            } else {
-#pragma unroll
-                for (int i = 0; i < NPK; ++i) Pn[i] = 0.0;
-                riccati_stage<false>(Pn, pn, Hs, g, bb);
-            }
+            for (int i = 0; i < NPK; ++i) Pn[i] = lane_dn(P[i]);
+            const bool okk = riccati_stage<true>(Pn, pn, Hs, g, bb);
+            ok = ok && (okk || k != kk);
         }
         return ok;
     }
@@ -944,8 +902,8 @@ struct SmallSolver {
     // instance gives every stage its composed map in ceil(log2(N + 1)) = 6 steps of (6 doubles through ds_bpermute + 6 fma pairs)
     // instead of N + 1 = 41 serial steps in which ONE lane of the wavefront works (round 3: the three vector sweeps of an
     // interior-point iteration were 31 % of a wavefront's life).  Everything off the recursion (kff, Du, Dnu) is stage-local.
-    // Same numbers as the serial sweeps up to the association of the products (the port runs the serial order).
-    static constexpr bool SCAN = !MX && NU == 1 && MPCRL_SMALL_SCAN != 0;
+    // Same numbers as the serial sweeps up to the association of the products (the port runs the serial order).  Every model of the
+    // stage-per-lane layout has NU = 1.
     MPCRL_DI void compose_from(double (&Mm)[NX * NX], double (&vv)[NX], int s, bool up, bool valid) {
         // partner = lane -/+ s; this lane's map is applied AFTER (forward: partner covers earlier stages) / BEFORE ... in both sweeps
         // the own map is the OUTER one: new = own o partner
@@ -974,7 +932,7 @@ struct SmallSolver {
 #pragma unroll
         for (int i = 0; i < NX * NX; ++i) Mm[i] = valid ? Mn[i] : Mm[i];
     }
-    // vector-only backward sweep (what backward<false> computes: p_k, kff_k on the stored K, Li, P)
+    // vector-only backward sweep: p_k, kff_k on the stored K, Li, P
     MPCRL_DI void backward_scan(const double *g, const double *bb) {
         double hb[NX], hbn[NX];
 #pragma unroll
@@ -1011,7 +969,7 @@ struct SmallSolver {
         for (int m = 0; m < NX; ++m) mvu = fma(Bget(m * NU), lane_dn(p[m] + hb[m]), mvu);
         if (!term) kff[0] = (first && qmode) ? 0.0 : mvu * Li[0];
     }
-    // forward sweep (what forward() computes: Dx, Du, Dnu)
+    // forward sweep: Newton step (Dx, Du) and the multipliers Dnu of the arriving dynamics
     MPCRL_DI void forward_scan(const double *bb) {
         double Mm[NX * NX], vv[NX];
 #pragma unroll
@@ -1042,52 +1000,6 @@ struct SmallSolver {
             for (int j = 0; j < NX; ++j) a = fma(-K[i * NX + j], Dx[j], a);
             Du[i] = a;
         }
-#pragma unroll
-        for (int i = 0; i < NX; ++i) {
-            double a = p[i];
-#pragma unroll
-            for (int j = 0; j < NX; ++j) a = fma(P[sym(i, j)], Dx[j], a);
-            Dnu[i] = first ? 0.0 : a;
-        }
-    }
-
-    // ---- forward sweep: Newton step (Dx, Du) and the multipliers Dnu of the arriving dynamics ------
-    MPCRL_DI void forward(const double *bb) {
-#pragma unroll
-        for (int i = 0; i < NX; ++i) Dx[i] = 0.0, Dnu[i] = 0.0;
-#pragma unroll
-        for (int i = 0; i < NU; ++i) Du[i] = 0.0;
-        double xn[NX];
-#pragma unroll
-        for (int i = 0; i < NX; ++i) xn[i] = 0.0;
-        for (int kk = 0; kk < N; ++kk) {
-            double tu[NU], tx[NX];
-#pragma unroll
-            for (int i = 0; i < NU; ++i) {
-                double a = -kff[i];
-#pragma unroll
-                for (int j = 0; j < NX; ++j) a = fma(-K[i * NX + j], Dx[j], a);
-                tu[i] = a;
-            }
-#pragma unroll
-            for (int i = 0; i < NX; ++i) {
-                double a = bb[i];
-#pragma unroll
-                for (int j = 0; j < NX; ++j) a = fma(A[i * NX + j], Dx[j], a);
-#pragma unroll
-                for (int j = 0; j < NU; ++j) a = fma(Bm[i * NU + j], tu[j], a);
-                tx[i] = a;
-            }
-            // as in backward(): stages that are already final (k <= kk + 1) are recomputed to the same bits, later ones are provisional
-#pragma unroll
-            for (int i = 0; i < NU; ++i) Du[i] = tu[i];
-            double xin[NX];
-#pragma unroll
-            for (int i = 0; i < NX; ++i) xin[i] = lane_up(tx[i]);
-#pragma unroll
-            for (int i = 0; i < NX; ++i) Dx[i] = first ? 0.0 : xin[i];
-        }
-        // multipliers of the arriving dynamics: local to each stage once Dx is known
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
             double a = p[i];
@@ -1222,10 +1134,10 @@ struct SmallSolver {
             // (dx, du, nuq, lam, t, s), so a step of length alpha along a direction that solves the Newton system takes all their
             // residuals (r_b, r_g, the bound rows t - slack, the soft rows) to (1 - alpha) times their value exactly, and
             // sum lam t becomes a quadratic in alpha whose coefficients ride in the reduction of the step length.  Later
-            // iterations scale what they have (MPCRL_IPM_SCALE_RES; the oracle re-evaluates everything every iteration, the parity
-            // tests are the check that the scaled residuals are the true ones to rounding).
+            // iterations scale what they have (the oracle re-evaluates everything every iteration, the parity tests are the check
+            // that the scaled residuals are the true ones to rounding).
             double rinf, musum;
-            if (!MPCRL_IPM_SCALE_RES || it == 0) {
+            if (it == 0) {
                 double dxn[NX], nuqn[NX];
 #pragma unroll
                 for (int i = 0; i < NX; ++i) dxn[i] = lane_dn(dx[i]), nuqn[i] = lane_dn(nuq[i]);
@@ -1299,9 +1211,9 @@ struct SmallSolver {
             if constexpr (MX)
                 okf = mx_pred<SKIPC>(Hs, rt, rb);   // (with the p_k of this right-hand side where the predictor step may be the step)
             else {
-                okf = backward<true>(Hs, rt, rb);
+                okf = backward(Hs, rt, rb);
                 PHW(2);
-                if constexpr (SCAN) forward_scan(rb); else forward(rb);
+                forward_scan(rb);
                 PHW(3);
             }
             double okbad = okf ? 0.0 : 1.0;   // reduced together with the predictor's step length below
@@ -1367,15 +1279,13 @@ struct SmallSolver {
                 for (int i = 0; i < NX; ++i) dx[i] = fma(alpha, Dx[i], dx[i]), nuq[i] = fma(alpha, Dnu[i], nuq[i]);
 #pragma unroll
                 for (int i = 0; i < NU; ++i) du[i] = fma(alpha, Du[i], du[i]);
-                if (MPCRL_IPM_SCALE_RES) {
-                    const double om = 1.0 - alpha;
+                const double om = 1.0 - alpha;
 #pragma unroll
-                    for (int i = 0; i < NX; ++i) rb[i] *= om;
+                for (int i = 0; i < NX; ++i) rb[i] *= om;
 #pragma unroll
-                    for (int i = 0; i < NW; ++i) rg[i] *= om;
-                    rinf_c = om * rinf;
-                    musum_c = fma(alpha, fma(alpha, e12[1], e12[0]), musum);
-                }
+                for (int i = 0; i < NW; ++i) rg[i] *= om;
+                rinf_c = om * rinf;
+                musum_c = fma(alpha, fma(alpha, e12[1], e12[0]), musum);
             };
             bool corr = qlive;
             if constexpr (SKIPC) {
@@ -1403,9 +1313,9 @@ struct SmallSolver {
                 mx_corr(rt, rb);
             else {
                 PHW(5);
-                if constexpr (SCAN) backward_scan(rt, rb); else backward<false>(Hs, rt, rb);
+                backward_scan(rt, rb);
                 PHW(6);
-                if constexpr (SCAN) forward_scan(rb); else forward(rb);
+                forward_scan(rb);
                 PHW(7);
             }
             rmax = 1.0;
@@ -1556,13 +1466,11 @@ struct SmallSolver {
                 }
             } else {
                 if (iu == 0) {
-                    const bool okf = backward<true>(Hs, rt, zero);
+                    const bool okf = backward(Hs, rt, zero);
                     okall = seg_max<M::SEG_SKIP>(okf ? 0.0 : 1.0, k, lpi, base) < 0.5;
-                } else if constexpr (SCAN)
+                } else
                     backward_scan(rt, zero);
-                else
-                    backward<false>(Hs, rt, zero);
-                if constexpr (SCAN) forward_scan(zero); else forward(zero);
+                forward_scan(zero);
             }
             double ynn[NX], yv[NW];
 #pragma unroll
@@ -1611,55 +1519,8 @@ struct SmallSolver {
             }
         }
     }
-};
 
-// =====================================================================================================
-// Sensitivity pass on the state a lane holds (x, u, nu, lam, t of its stage; parameters, bounds and cost table set): dV/dp and
-// du0*/dp of the instance the lane's slot works on — what update_nlp computes after the reference's solve (nlp.py:1399-1424).
-// Called by the solve kernels at the end of a wavefront's life (MPCRL_FUSE_SENS: "the adjoint KKT solve fused into the same
-// sweep") and by small_sens_kernel on a stored iterate.  The output rows are written in full: the lanes of an instance zero
-// every entry sensitivities() does not store — the cost block of p (zero gradient of the mirror, nlp.py:1039-1055), everything
-// of an instance that was not solved, du0*/dp in Q-mode.
-// =====================================================================================================
-#ifndef MPCRL_FUSE_SENS
-#define MPCRL_FUSE_SENS 0   // measured (cartpole, 4096): fused 0.582 ms vs 0.564 ms with the pass as a second launch — the second-order jets of the
-                          // pass raise the register pressure of the SQP loop (sliced kernel: 36 -> 76 spilled VGPRs, 173 -> 237 SGPRs); the plain
-                          // launch (3072 instances) gains 0.6 %.  The fused form is kept buildable and tested (-DMPCRL_FUSE_SENS=1).
-#endif
-template <class M>
-MPCRL_DI void small_sens_tail(SmallSolver<M> &S, const SmallArgs &a, long inst, bool valid, int status) {
-    constexpr int NX = M::NX, NU = M::NU, NP = M::NP;
-    const int k = S.k, lpi = S.lpi;
-    double xn[NX], nun[NX];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) xn[i] = lane_dn(S.x[i]), nun[i] = lane_dn(S.nu_[i]);
-    double hdd[M::NLD * (M::NLD + 1) / 2];
-    if ((a.flags & 2) && a.dpi && !S.qmode) {   // wave-uniform
-        S.template linearize<true>(xn, nun, hdd);
-#ifdef MPCRL_PROFILE_PHASES
-        { unsigned long long n_ = clock64(); if (S.pht) S.phw[9] += n_ - S.pht; S.pht = n_; }      // (phase profile of the sensitivity kernel)
-#endif
-    } else {
-#pragma unroll
-        for (int e = 0; e < M::NLD * (M::NLD + 1) / 2; ++e) hdd[e] = 0.0;
-        S.linearize(xn);
-    }
-#pragma unroll
-    for (int i = 0; i < S.NPK; ++i) S.P[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < NX; ++i) S.p[i] = 0.0;
-    const bool sv = valid && (status == 0 || status == 2);
-    S.sensitivities(a.flags, sv, nun, a.dV ? a.dV + inst * NP : nullptr, a.dpi ? a.dpi + inst * NU * NP : nullptr, hdd);
-    // the zeros go last so that no load of the pass waits behind these stores; the two sets of addresses are disjoint
-    if (valid) {
-        if (a.dV)
-            for (int e = k; e < NP; e += lpi)
-                if (!(sv && M::p_has_gradient(e))) a.dV[inst * NP + e] = 0.0;
-        if (a.dpi)
-            for (int e = k; e < NU * NP; e += lpi)
-                if (!(sv && !S.qmode && M::p_has_gradient(e % NP))) a.dpi[inst * NU * NP + e] = 0.0;
-    }
-}
+};
 
 // =====================================================================================================
 // kernel: floor(64/(N+1)) instances per 64-lane workgroup
@@ -1922,10 +1783,6 @@ __global__ void __launch_bounds__(64, M::DISCRETE ? MPCRL_LINEAR_OCC : MPCRL_CAR
             }
         }
     }
-#if MPCRL_FUSE_SENS
-    // ---- sensitivities of the instances this wavefront solved, from the state its lanes still hold (wave-uniform branch)
-    if (a.flags & (1 | 2)) small_sens_tail<M>(S, a, inst, valid, status);
-#endif
 }
 
 // =====================================================================================================
@@ -1976,7 +1833,10 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
     SmallSolver<M> S(sp, k, lpi, base);
     __shared__ __attribute__((aligned(16))) double mx_lds[SmallSolver<M>::MX ? SmallSolver<M>::MX_LDS : 2];
     __shared__ double c_lds[M::MAX_IPW * SmallSolver<M>::CTAB];
-    __shared__ double sc_lds[M::MAX_IPW * 6];         // parked scalars: live, status, iterations, interior-point iterations, ...
+    // parked scalars: live, status, iterations, interior-point iterations, ... (5 doubles; a stride of 5 costs the WARM
+    // instantiations 12 more spilled VGPRs, measured: the slots stay 6 doubles apart)
+    constexpr int SC = 6;
+    __shared__ double sc_lds[M::MAX_IPW * SC];
     // The parked instance's state (x, nu, u, lam, t of every stage), field-major so that the lanes of a slot touch consecutive
     // words.  It fits next to the stage slots of the matrix-core sweep up to N + 1 = 21 stages (cartpole's horizon: 609 doubles —
     // the LDS of a CU is shared by four wavefronts, 40 960 B each); longer horizons park in the instance's stored-iterate arrays
@@ -2098,8 +1958,7 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
     // the parked instance (wave-uniform): local index or -1, and whether it has run at all
     int pk = (posof(ipw) < a.B) ? ipw : -1;
     bool pk_started = false;
-    int rr = 0, rounds_since = 0;
-    int first_done = -1;                              // local index of the instance that left its slot for good (wave-uniform), or -1
+    int rr = 0;
     double nun[NX];
     for (;;) {
         double xn[NX];
@@ -2247,21 +2106,9 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
         for (int s_ = 0; s_ < ipw; ++s_)
             if (v < 0 && !__shfl(live ? 1 : 0, s_ * lpi)) v = s_;
         const bool for_good = v >= 0;
-#ifndef MPCRL_SLICE_PERIOD
-#define MPCRL_SLICE_PERIOD 1
-#endif
-        if (!for_good && (++rounds_since % MPCRL_SLICE_PERIOD) != 0) continue;   // rotate every MPCRL_SLICE_PERIOD-th round only
         if (v < 0) v = rr % ipw, ++rr;
         const bool sw = slot_on && slot == v;
         const int lo = __shfl(loc, v * lpi);            // local index of the outgoing instance
-#if MPCRL_FUSE_SENS
-        // an instance that leaves its slot for good (it finished) is remembered: with the park area in LDS its final state goes
-        // there in place of the parked one's, so that the wavefront can run its sensitivity pass at the end without reading it back
-        const bool keep_out = !for_good || (lds_park && (a.flags & 3));
-        if (for_good) first_done = lo;
-#else
-        const bool keep_out = !for_good;
-#endif
         if (sw && !for_good) {                          // park: state to LDS (or the instance's stored-iterate arrays), scalars to LDS
             if (valid && !lds_park) {
 #pragma unroll
@@ -2278,14 +2125,11 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
                     bnd[0 * nb + i] = S.lam[0][i], bnd[1 * nb + i] = S.lam[1][i], bnd[2 * nb + i] = S.t[0][i], bnd[3 * nb + i] = S.t[1][i];
             }
             if (first) {   // the small integers share one word (exact in a double): live | tight | status (3 bits) | countdown (8) | iterations
-                double *sc = sc_lds + lo * 6;
+                double *sc = sc_lds + lo * SC;
                 sc[0] = (double)((live ? 1 : 0) + (last_tight ? 2 : 0) + 4 * status + 32 * (exit_cnt & 255)) + 8192.0 * (double)iti;
                 sc[1] = (double)n_ipm, sc[2] = stepn, sc[3] = rbest, sc[4] = rchk;
             }
         }
-#if MPCRL_FUSE_SENS
-        if (sw && for_good && first) sc_lds[lo * 6 + 5] = (double)status;   // (read again by the sensitivity pass at the end)
-#endif
         SmallSolver<M>::wave_lds_sync();                // orders the stores above before the loads below (same wavefront: in order)
         // take the parked instance: every lane runs the same loads, the lanes of the slot keep the results
         const int newloc = sw ? pk : loc;
@@ -2293,7 +2137,7 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
         bind(loc);
         load_params();
         {
-            const double *sc = sc_lds + pk * 6;
+            const double *sc = sc_lds + pk * SC;
             const double w_ = sc[0], ni_ = sc[1], sn_ = sc[2], rb_ = sc[3], rc_ = sc[4];
             const int it_ = (int)(w_ * (1.0 / 8192.0)), lo_ = (int)(w_ - 8192.0 * (double)it_);   // iterations | the packed low bits
             if (sw) {
@@ -2332,7 +2176,7 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
                 out[2 * NX + NU + 4 * i] = S.lam[0][i], out[2 * NX + NU + 4 * i + 1] = S.lam[1][i];
                 out[2 * NX + NU + 4 * i + 2] = S.t[0][i], out[2 * NX + NU + 4 * i + 3] = S.t[1][i];
             }
-            if (sw && keep_out) {
+            if (sw && !for_good) {
 #pragma unroll
                 for (int j = 0; j < PK; ++j) pl[j * lpi] = out[j];
             }
@@ -2410,56 +2254,13 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
 #ifdef MPCRL_PROFILE_PHASES
     if ((threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 16; ++i_) atomicAdd(&g_phase_ticks[i_], S.phw[i_]);
 #endif
-#if MPCRL_FUSE_SENS
-    // ---- sensitivities.  Pass 1: the instances the slots hold at the end, from registers.  Pass 2: the instance that left its slot
-    // for good earlier, on slot 0 from the park area (LDS parking) — or, with HBM parking, from its stored iterate, which this
-    // wavefront wrote itself (its own stores are visible to its later loads once they have been waited for).
-    if (a.flags & 3) {
-        small_sens_tail<M>(S, a, inst, valid, status);
-        if (first_done >= 0) {
-            const bool on0 = slot == 0;
-            loc = first_done;
-            bind(loc);
-            valid = on0 && posof(loc) < a.B;
-            load_params();
-            const int st_ = (int)sc_lds[first_done * 6 + 5];
-            if constexpr (lds_park) {
-                const double *pl = park_lds + k;
-                double in[PK];
-#pragma unroll
-                for (int j = 0; j < PK; ++j) in[j] = pl[j * lpi];
-#pragma unroll
-                for (int i = 0; i < NX; ++i) S.x[i] = in[i], S.nu_[i] = first ? 0.0 : in[NX + i];
-#pragma unroll
-                for (int i = 0; i < NU; ++i) S.u[i] = in[2 * NX + i];
-#pragma unroll
-                for (int i = 0; i < NW; ++i) {
-                    S.lam[0][i] = in[2 * NX + NU + 4 * i], S.lam[1][i] = in[2 * NX + NU + 4 * i + 1];
-                    S.t[0][i] = in[2 * NX + NU + 4 * i + 2], S.t[1][i] = in[2 * NX + NU + 4 * i + 3];
-                }
-            } else {
-                __builtin_amdgcn_s_waitcnt(0);   // the stores of the finished instance have completed
-#pragma unroll
-                for (int i = 0; i < NX; ++i) {
-                    S.x[i] = a.X[(inst * (N + 1) + k) * NX + i];
-                    S.nu_[i] = first ? 0.0 : a.PI[(inst * N + k - 1) * NX + i];
-                }
-#pragma unroll
-                for (int i = 0; i < NU; ++i) S.u[i] = term ? 0.0 : a.U[(inst * N + k) * NU + i];
-#pragma unroll
-                for (int i = 0; i < NW; ++i)
-                    S.lam[0][i] = bnd[0 * nb + i], S.lam[1][i] = bnd[1 * nb + i], S.t[0][i] = bnd[2 * nb + i], S.t[1][i] = bnd[3 * nb + i];
-            }
-            small_sens_tail<M>(S, a, inst, valid, st_);
-        }
-    }
-#endif
 }
 
 // =====================================================================================================
-// sensitivity kernel: re-reads the converged iterate (x, u, nu, lam, t) written by small_solve_kernel.  With MPCRL_FUSE_SENS the
-// solve kernels run the pass themselves at the end of a wavefront's life and this kernel is not launched (it stays for builds
-// with MPCRL_FUSE_SENS = 0, where the pass was a second launch: 49 us + a 17 us boundary per 4096 cartpole instances).
+// sensitivity kernel: dV/dp and du0*/dp of each instance (what update_nlp computes after the reference's solve, nlp.py:1399-1424)
+// on the converged iterate (x, u, nu, lam, t) a solve kernel stored.  The output rows are written in full: the lanes of an
+// instance zero every entry sensitivities() does not store — the cost block of p (zero gradient of the mirror, nlp.py:1039-1055),
+// everything of an instance that was not solved, du0*/dp in Q-mode.
 // =====================================================================================================
 template <class M>
 __global__ void __launch_bounds__(64) small_sens_kernel(const SmallSpec sp, const SmallArgs a) {
@@ -2504,11 +2305,40 @@ __global__ void __launch_bounds__(64) small_sens_kernel(const SmallSpec sp, cons
     for (int i = 0; i < NU; ++i) S.u[i] = term ? 0.0 : a.U[(inst * N + k) * NU + i];
 #pragma unroll
     for (int i = 0; i < NW; ++i) S.lam[0][i] = bnd[0 * nb + i], S.lam[1][i] = bnd[1 * nb + i], S.t[0][i] = bnd[2 * nb + i], S.t[1][i] = bnd[3 * nb + i];
-    // the dynamics Jacobians of the final iterate are needed by the adjoint Riccati sweep: linearised again inside the pass
 #ifdef MPCRL_PROFILE_PHASES
     S.pht = clock64();
 #endif
-    small_sens_tail<M>(S, a, inst, valid, a.status[inst]);
+    const int status = a.status[inst];
+    // the dynamics Jacobians of the final iterate are needed by the adjoint Riccati sweep: linearised again here
+    double xn[NX], nun[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xn[i] = lane_dn(S.x[i]), nun[i] = lane_dn(S.nu_[i]);
+    double hdd[M::NLD * (M::NLD + 1) / 2];
+    if ((a.flags & 2) && a.dpi && !S.qmode) {   // wave-uniform
+        S.template linearize<true>(xn, nun, hdd);
+#ifdef MPCRL_PROFILE_PHASES
+        { unsigned long long n_ = clock64(); if (S.pht) S.phw[9] += n_ - S.pht; S.pht = n_; }      // (phase profile of the sensitivity kernel)
+#endif
+    } else {
+#pragma unroll
+        for (int e = 0; e < M::NLD * (M::NLD + 1) / 2; ++e) hdd[e] = 0.0;
+        S.linearize(xn);
+    }
+#pragma unroll
+    for (int i = 0; i < S.NPK; ++i) S.P[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) S.p[i] = 0.0;
+    const bool sv = valid && (status == 0 || status == 2);
+    S.sensitivities(a.flags, sv, nun, a.dV ? a.dV + inst * NP : nullptr, a.dpi ? a.dpi + inst * NU * NP : nullptr, hdd);
+    // the zeros go last so that no load of the pass waits behind these stores; the two sets of addresses are disjoint
+    if (valid) {
+        if (a.dV)
+            for (int e = k; e < NP; e += lpi)
+                if (!(sv && M::p_has_gradient(e))) a.dV[inst * NP + e] = 0.0;
+        if (a.dpi)
+            for (int e = k; e < NU * NP; e += lpi)
+                if (!(sv && !S.qmode && M::p_has_gradient(e % NP))) a.dpi[inst * NU * NP + e] = 0.0;
+    }
 #ifdef MPCRL_PROFILE_PHASES
     { unsigned long long n_ = clock64(); S.phw[8] += n_ - S.pht; }
     if ((threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 16; ++i_) atomicAdd(&g_phase_ticks[i_], S.phw[i_]);
