@@ -33,6 +33,10 @@
  *   td_error, dp = LR td dQ_dp, np.mean(dp) of the learning   mpcrl_qlearning_td_grad / mpcrl_qlearning_td_workspace_bytes,
  *   sweep; mpc.set_p(p + mean)                                  mpcrl_qlearning_apply
  *     scripts/cartpole_mpc_qlearning.py:255-269
+ *   MPCActorCriticPolicy.forward / evaluate_actions /          mpcrl_ppo_cartpole_collect, mpcrl_ppo_gae,
+ *   predict_values (NotImplementedError in the reference)       mpcrl_ppo_surrogate_grad / mpcrl_ppo_surrogate_workspace_bytes,
+ *   and the PPO roll-out / update around them                   mpcrl_ppo_log_std_apply
+ *     rlmpc/ppo/policies.py:26-134
  *
  * Conventions
  *   - plain C, no torch types.  Every array argument of mpcrl_solve / *_iterate / mpcrl_reset /
@@ -84,7 +88,10 @@ extern "C" {
  *   131  round 7: mpcrl_qlearning_cartpole_collect; mpcrl_qlearning_td_grad / mpcrl_qlearning_td_workspace_bytes; mpcrl_qlearning_apply
  *        (the batched Q-learning loop of the cartpole); nothing existing changed
  *   132  mpcrl_td3_policy_post: a masked entry (mask_i == 0) is selected out, step_i = 0, instead of multiplied by 0 — a NaN or +-inf
- *        message there no longer turns a frozen theta_i into NaN (behaviour; the signature is unchanged) */
+ *        message there no longer turns a frozen theta_i into NaN (behaviour; the signature is unchanged)
+ *        additions under 132 (no existing export changed, so no bump): mpcrl_ppo_cartpole_collect; mpcrl_ppo_gae;
+ *        mpcrl_ppo_surrogate_grad / mpcrl_ppo_surrogate_workspace_bytes; mpcrl_ppo_log_std_apply (batched PPO with the MPC as
+ *        Gaussian actor, cartpole) */
 #define MPCRL_ABI_VERSION 132
 
 enum { MPCRL_MODEL_CARTPOLE = 0, MPCRL_MODEL_LINEAR = 1, MPCRL_MODEL_CHAIN = 2 };
@@ -382,6 +389,56 @@ int mpcrl_qlearning_td_grad(const double *Q, const double *V, const double *dQ_d
 /* ABI 131.  After the collective: step_i = mask_i != 0 ? msg_i / max(1, msg[n_theta + 1]) : 0 (mask [n_theta] double, NULL = all), the mean of
  * distributed.mean_update; theta += step; step_out [n_theta] = step (mpc.set_p(mpc.get_p() + np.mean(dp)), script lines 263-269). */
 int mpcrl_qlearning_apply(const double *msg, int n_theta, const double *mask, double *theta, double *step_out, void *stream);
+
+/* Added under ABI 132.  Batched PPO with the MPC as Gaussian actor (ppo_kernel.hpp; mpc4rl_amd/ppo.py), cartpole environment, nu = 1, all
+ * arithmetic fp64: a ~ N(mu, sigma^2) with mu = scale_action(u0*) of the solve and sigma = exp(log_std[0]), log_std a DEVICE double the
+ * learner steps.  Handle-less; every call launches on the device that owns its first output pointer, is asynchronous on `stream` and
+ * capture-safe (no host synchronisation).
+ *
+ * One roll-out step after the policy's solve, one launch, one lane per environment.  par: the nine doubles of mpcrl_env_cartpole_step;
+ * state / steps as there; u0, status [E]: the solve; eps [E] float standard-normal draws, u01 [E] uniform draws (resets), value [E] the
+ * critic's V at the observation just solved; lo < hi = lbu, ubu; 0 <= t < T the row written.
+ *   ok   = status in {0, 2} and u0 finite (mpcrl_policy_action's accept_status2 rule);   mu = ok ? 2 (u0 - lo) / (hi - lo) - 1 : 0;
+ *   a    = mu + sigma eps (unclipped: this is what is stored);   logp = -(a - mu)^2 / (2 sigma^2) - log_std - 1/2 log 2 pi;
+ *   the environment is stepped with clip(a, -1, 1) (the arithmetic of mpcrl_env_cartpole_step: the same bits).
+ * Row t of the tables [T][E]: OBS ([..][4], the state before the step), ACT, LOGP, VAL = value, REW = reward_scale * reward, NEXT ([..][4],
+ * the state after the step BEFORE any reset: the bootstrap value is taken there), TERM, DONE (uint8: terminated; terminated or
+ * truncated), OK (uint8).  Environments that are done are then reset as mpcrl_env_cartpole_reset does with u01 (steps = 0);
+ * obs [E][4] = the state after that (the next solve's x0), ended [E] int32 = DONE (the cold mask of the next solve). */
+int mpcrl_ppo_cartpole_collect(const double *par, int E, int T, int t, double *state, int64_t *steps, const double *u0, const int32_t *status,
+                               const float *eps, const double *u01, const double *value, const double *log_std, double lo, double hi,
+                               double reward_scale, double *OBS, double *ACT, double *LOGP, double *VAL, double *REW, double *NEXT, uint8_t *TERM,
+                               uint8_t *DONE, uint8_t *OK, double *obs, int32_t *ended, void *stream);
+
+/* Added under ABI 132.  Generalised advantage estimates, one launch, one lane per environment, serial over t = T-1 ... 0; all [T][E]:
+ *   delta_t = REW_t + gamma (1 - TERM_t) VNEXT_t - VAL_t;   ADV_t = delta_t + gamma lambda (1 - DONE_t) ADV_{t+1}, ADV_T = 0;   RET_t = ADV_t + VAL_t
+ * VNEXT = the critic at NEXT.  stable_baselines3's RolloutBuffer.compute_returns_and_advantage with its time-limit bootstrap (gamma
+ * V(terminal_obs) added to the reward of a truncated step) written as VNEXT on truncated rows: the same numbers. */
+int mpcrl_ppo_gae(const double *REW, const double *VAL, const double *VNEXT, const uint8_t *TERM, const uint8_t *DONE, int T, int E, double gamma,
+                  double gae_lambda, double *ADV, double *RET, void *stream);
+
+/* Added under ABI 132.  The policy half of one PPO minibatch update, two launches (advantage statistics, then terms).  idx [M] int64: rows
+ * of the flattened [n_rows = T E] tables ACT, LOGP, ADV, OK; from the minibatch's re-solve with MPCRL_SENS_PI: u0_new [M], status_new [M],
+ * dpi_dp [M][1][n_p].  Per row b, j = idx[b]:
+ *   valid_b = 0 <= j < n_rows, OK[j], status_new in {0, 2}, u0_new finite, ACT / LOGP / ADV [j] finite;
+ *   A_b  = normalize_adv and more than one valid row ? (ADV[j] - mean) / (std + 1e-8) : ADV[j]   (over the valid rows, unbiased std as torch.std);
+ *   mu_b, logp_b as in the roll-out from u0_new;   r_b = exp(logp_b - LOGP[j]);   loss_b = -min(r_b A_b, clip(r_b, 1 - eps, 1 + eps) A_b);
+ *   g_mu = -A r (a - mu) / sigma^2,  g_ls = -A r ((a - mu)^2 / sigma^2 - 1), both 0 where the clipped branch is the minimum (A > 0 and
+ *   r > 1 + eps, or A < 0 and r < 1 - eps).  An invalid row is selected out, never multiplied by 0; dpi_dp is read as nan_to_num does.
+ * msg [n_p + 8]:  [0, n_p) = -lr sum_b g_mu,b 2 / (hi - lo) dpi_dp_b;  [n_p] = -lr (sum_b g_ls,b - ent_coef count) (the entropy bonus adds
+ *   -ent_coef to the mean g_ls);  [n_p + 1] = count of valid rows — entries [0, n_p) with this count are the layout mpcrl_qlearning_apply and
+ *   distributed.allreduce_weighted_grad use;  [n_p + 2 ...] = sums over the valid rows of loss_b, (r - 1) - log r (approximate KL),
+ *   |r - 1| > eps (the clip fraction's count), r, ADV, (ADV - mean)^2.
+ * workspace: mpcrl_ppo_surrogate_workspace_bytes(M, n_p) bytes of device memory, ZERO before the first call (the call leaves it zero).
+ * Fixed summation order (no floating-point atomics): the same inputs give the same bits. */
+int64_t mpcrl_ppo_surrogate_workspace_bytes(int M, int n_p);
+int mpcrl_ppo_surrogate_grad(const int64_t *idx, int M, int64_t n_rows, const double *ACT, const double *LOGP, const double *ADV, const uint8_t *OK,
+                             const double *u0_new, const int32_t *status_new, const double *dpi_dp, int n_p, const double *log_std, double lo, double hi,
+                             double clip_range, double ent_coef, double lr, int normalize_adv, void *workspace, double *msg, void *stream);
+
+/* Added under ABI 132.  After the collective (and next to mpcrl_qlearning_apply, which steps theta from the same message as a masked mean):
+ * log_std[0] += msg[n_p] / max(1, msg[n_p + 1]). */
+int mpcrl_ppo_log_std_apply(const double *msg, int n_p, double *log_std, void *stream);
 
 /* Bytes of device memory held by the handle; library version (MPCRL_ABI_VERSION of the header it was built from). */
 int64_t mpcrl_workspace_bytes(mpcrl_handle h);

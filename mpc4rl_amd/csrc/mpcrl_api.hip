@@ -20,6 +20,7 @@
 #include "replay_kernel.hpp"
 #include "td3_kernel.hpp"
 #include "qlearning_kernel.hpp"
+#include "ppo_kernel.hpp"
 
 using namespace mpcrl;
 
@@ -730,6 +731,65 @@ int mpcrl_qlearning_apply(const double *msg, int n_theta, const double *mask, do
     if (!msg || n_theta < 1 || !theta || !step_out) return MPCRL_E_ARG;
     ON_DEVICE_OF(theta);
     hipLaunchKernelGGL(qlearning_apply_kernel, dim3((n_theta + 255) / 256), dim3(256), 0, (hipStream_t)stream, msg, n_theta, mask, theta, step_out);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int mpcrl_ppo_cartpole_collect(const double *par, int E, int T, int t, double *state, int64_t *steps, const double *u0, const int32_t *status,
+                               const float *eps, const double *u01, const double *value, const double *log_std, double lo, double hi,
+                               double reward_scale, double *OBS, double *ACT, double *LOGP, double *VAL, double *REW, double *NEXT, uint8_t *TERM,
+                               uint8_t *DONE, uint8_t *OK, double *obs, int32_t *ended, void *stream) {
+    if (!par || E < 1 || T < 1 || t < 0 || t >= T || !state || !steps || !u0 || !status || !eps || !u01 || !value || !log_std || !(hi > lo) || !OBS ||
+        !ACT || !LOGP || !VAL || !REW || !NEXT || !TERM || !DONE || !OK || !obs || !ended)
+        return MPCRL_E_ARG;
+    ON_DEVICE_OF(OBS);
+    PpoCollectArgs a;
+    a.par.gravity = par[0], a.par.masscart = par[1], a.par.masspole = par[2], a.par.length = par[3], a.par.force_mag = par[4], a.par.tau = par[5];
+    a.par.x_threshold = par[6], a.par.theta_threshold = par[7], a.par.max_episode_steps = (long)par[8];
+    a.E = E, a.T = T, a.t = t, a.state = state, a.steps = steps, a.u0 = u0, a.status = (const int *)status, a.eps = eps, a.u01 = u01, a.value = value;
+    a.log_std = log_std, a.lo = lo, a.hi = hi, a.reward_scale = reward_scale, a.OBS = OBS, a.ACT = ACT, a.LOGP = LOGP, a.VAL = VAL, a.REW = REW;
+    a.NEXT = NEXT, a.TERM = TERM, a.DONE = DONE, a.OK = OK, a.obs = obs, a.ended = ended;
+    hipLaunchKernelGGL(ppo_cartpole_collect_kernel, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int mpcrl_ppo_gae(const double *REW, const double *VAL, const double *VNEXT, const uint8_t *TERM, const uint8_t *DONE, int T, int E, double gamma,
+                  double gae_lambda, double *ADV, double *RET, void *stream) {
+    if (!REW || !VAL || !VNEXT || !TERM || !DONE || !ADV || !RET || T < 1 || E < 1) return MPCRL_E_ARG;
+    ON_DEVICE_OF(ADV);
+    hipLaunchKernelGGL(ppo_gae_kernel, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, REW, VAL, VNEXT, TERM, DONE, T, E, gamma, gae_lambda, ADV,
+                       RET);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int64_t mpcrl_ppo_surrogate_workspace_bytes(int M, int n_p) {
+    if (M < 1 || n_p < 1) return MPCRL_E_ARG;
+    return 16 + (int64_t)((M + PPO_ROWS - 1) / PPO_ROWS) * (n_p + PPO_NS) * (int64_t)sizeof(double);
+}
+
+int mpcrl_ppo_surrogate_grad(const int64_t *idx, int M, int64_t n_rows, const double *ACT, const double *LOGP, const double *ADV, const uint8_t *OK,
+                             const double *u0_new, const int32_t *status_new, const double *dpi_dp, int n_p, const double *log_std, double lo, double hi,
+                             double clip_range, double ent_coef, double lr, int normalize_adv, void *workspace, double *msg, void *stream) {
+    if (!idx || M < 1 || n_rows < 1 || !ACT || !LOGP || !ADV || !OK || !u0_new || !status_new || !dpi_dp || n_p < 1 || !log_std || !(hi > lo) ||
+        !(clip_range > 0.0) || !workspace || !msg)
+        return MPCRL_E_ARG;
+    ON_DEVICE_OF(msg);
+    PpoSurrogateArgs a;
+    a.idx = idx, a.M = M, a.n_p = n_p, a.n_rows = n_rows, a.ACT = ACT, a.LOGP = LOGP, a.ADV = ADV, a.OK = OK, a.u0_new = u0_new;
+    a.status_new = (const int *)status_new, a.dpi = dpi_dp, a.log_std = log_std, a.lo = lo, a.hi = hi, a.clip = clip_range, a.ent_coef = ent_coef, a.lr = lr;
+    a.normalize = normalize_adv, a.ticket = (unsigned int *)workspace, a.partial = (double *)((char *)workspace + 16), a.msg = msg;
+    hipLaunchKernelGGL(ppo_adv_stats_kernel, dim3(1), dim3(PPO_STAT_THREADS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(ppo_surrogate_kernel, dim3((M + PPO_ROWS - 1) / PPO_ROWS), dim3(PPO_ROWS), 0, (hipStream_t)stream, a);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int mpcrl_ppo_log_std_apply(const double *msg, int n_p, double *log_std, void *stream) {
+    if (!msg || n_p < 1 || !log_std) return MPCRL_E_ARG;
+    ON_DEVICE_OF(log_std);
+    hipLaunchKernelGGL(ppo_log_std_apply_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, msg, n_p, log_std);
     HIP_OK(hipGetLastError());
     return 0;
 }

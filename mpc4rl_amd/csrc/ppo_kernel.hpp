@@ -1,0 +1,285 @@
+// Batched PPO with the MPC as Gaussian actor, cartpole environment, nu = 1 (mpc4rl_amd/ppo.py): what the reference's
+// MPCActorCriticPolicy (rlmpc/ppo/policies.py:26-134) leaves as NotImplementedError, around the solves, on the device.  The policy is
+// a ~ N(mu, sigma^2), mu = scale_action(u0*) of the solve, sigma = exp(log_std) with one learnable, state-independent log_std.
+//   ppo_cartpole_collect_kernel   one roll-out step after the policy's solve, one lane per environment: the sample and its log
+//                                 probability, the environment step, row t of the roll-out tables, the reset of the environments that
+//                                 ended, the observation and the cold mask of the next solve
+//   ppo_gae_kernel                generalised advantage estimates, one lane per environment, serial over t = T-1 ... 0
+//   ppo_adv_stats_kernel          count, sum and centred sum of squares of the advantages over the valid rows of a minibatch
+//   ppo_surrogate_kernel          the clipped surrogate's terms and the message [-lr sum g_mu 2/(hi-lo) dpi/dp, -lr sum g_ls, count,
+//                                 statistics], summed in a fixed order (no floating-point atomics)
+//   ppo_log_std_apply_kernel      log_std += message / max(1, count), after the collective
+// All PPO arithmetic is fp64.  The environment step is the shared device function of env_kernel.hpp (the same bits as
+// mpcrl_env_cartpole_step); mean and log probability are the device functions below, shared by the roll-out and the surrogate, so a
+// re-solve that returns the roll-out's u0 gives a ratio of exactly 1.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "env_kernel.hpp"
+#include "replay_kernel.hpp"   // nan_to_num_d
+
+namespace mpcrl {
+
+// the accept_status2 rule of mpcrl_policy_action: the solve converged or ran out of iterations, and u0 is a number
+__device__ __forceinline__ bool ppo_solve_ok(int status, double u0) { return (status == 0 || status == 2) && isfinite(u0); }
+
+// scale_action in fp64 (the fp64 part of policy_action_one); a rejected solve gives the zero action
+__device__ __forceinline__ double ppo_mean(double u0, bool ok, double lo, double hi) {
+#pragma clang fp contract(off)
+    return ok ? 2.0 * ((u0 - lo) / (hi - lo)) - 1.0 : 0.0;
+}
+
+// log N(a; mu, sigma^2) with sigma = exp(log_std): -(a - mu)^2 / (2 sigma^2) - log_std - 1/2 log 2 pi
+__device__ __forceinline__ double ppo_log_prob(double a, double mu, double sigma, double log_std) {
+#pragma clang fp contract(off)
+    const double d = a - mu;
+    return -(d * d) / (2.0 * (sigma * sigma)) - log_std - 0.9189385332046727;
+}
+
+struct PpoCollectArgs {
+    CartpoleEnvPar par;
+    int E, T, t;
+    double *state;            // [E][4] the environments' states
+    int64_t *steps;           // [E]
+    const double *u0;         // [E] the policy's solve: control
+    const int *status;        // [E]
+    const float *eps;         // [E] standard-normal draws
+    const double *u01;        // [E] uniform draws (resets)
+    const double *value;      // [E] the critic at the observation just solved
+    const double *log_std;    // [1]
+    double lo, hi, reward_scale;
+    double *OBS, *ACT, *LOGP, *VAL, *REW, *NEXT;      // [T][E] ([..][4] for OBS, NEXT)
+    uint8_t *TERM, *DONE, *OK;                        // [T][E]
+    double *obs;              // [E][4] out: the next solve's x0 (after resets)
+    int32_t *ended;           // [E] out: 1 = the episode ended (the next solve starts that instance cold)
+};
+
+__global__ void __launch_bounds__(256) ppo_cartpole_collect_kernel(const PpoCollectArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.E) return;
+    const double ls = a.log_std[0], sigma = exp(ls);
+    const double u = a.u0[i];
+    const bool ok = ppo_solve_ok(a.status[i], u);
+    const double mu = ppo_mean(u, ok, a.lo, a.hi);
+    double act;
+    {
+#pragma clang fp contract(off)      // mu + sigma eps as the torch expression: product, sum
+        act = sigma * (double)a.eps[i];
+        act = mu + act;
+    }
+    const double logp = ppo_log_prob(act, mu, sigma, ls);
+    const double2 s01 = reinterpret_cast<const double2 *>(a.state)[2 * i], s23 = reinterpret_cast<const double2 *>(a.state)[2 * i + 1];
+    // the stored sample is unclipped; the environment sees clip(a, -1, 1) (a NaN sample — log_std not finite — steps with NaN, as in torch)
+    const double applied = act < -1.0 ? -1.0 : (act > 1.0 ? 1.0 : act);
+    const CartpoleStepOut o = cartpole_env_step(a.par, s01.x, s01.y, s23.x, s23.y, applied);
+    const int64_t n = a.steps[i] + 1;
+    const bool done = o.terminated || n >= a.par.max_episode_steps;
+    const long k = (long)a.t * a.E + i;
+    reinterpret_cast<double2 *>(a.OBS)[2 * k] = s01;
+    reinterpret_cast<double2 *>(a.OBS)[2 * k + 1] = s23;
+    reinterpret_cast<double2 *>(a.NEXT)[2 * k] = make_double2(o.nx, o.nxd);       // before any reset: the bootstrap value is taken here
+    reinterpret_cast<double2 *>(a.NEXT)[2 * k + 1] = make_double2(o.nth, o.nthd);
+    a.ACT[k] = act, a.LOGP[k] = logp, a.VAL[k] = a.value[i], a.REW[k] = a.reward_scale * o.reward;
+    a.TERM[k] = o.terminated ? 1 : 0, a.DONE[k] = done ? 1 : 0, a.OK[k] = ok ? 1 : 0;
+    // the environment goes on, or starts again (mpcrl_env_cartpole_reset)
+    double x = o.nx, xd = o.nxd, th = o.nth, thd = o.nthd;
+    int64_t cnt = n;
+    if (done) x = 0.0, xd = 0.0, th = (0.9 + 0.2 * a.u01[i]) * 3.141592653589793, thd = 0.0, cnt = 0;
+    reinterpret_cast<double2 *>(a.state)[2 * i] = make_double2(x, xd);
+    reinterpret_cast<double2 *>(a.state)[2 * i + 1] = make_double2(th, thd);
+    a.steps[i] = cnt;
+    reinterpret_cast<double2 *>(a.obs)[2 * i] = make_double2(x, xd);
+    reinterpret_cast<double2 *>(a.obs)[2 * i + 1] = make_double2(th, thd);
+    a.ended[i] = done ? 1 : 0;
+}
+
+// stable_baselines3's RolloutBuffer.compute_returns_and_advantage with the time-limit bootstrap written as VNEXT on truncated rows:
+//     delta_t = REW_t + gamma (1 - TERM_t) VNEXT_t - VAL_t;  adv_t = delta_t + gamma lambda (1 - DONE_t) adv_{t+1}, adv_T = 0;  ret_t = adv_t + VAL_t
+// (every product and sum its own rounding, in the order of the torch statement ppo_gae)
+__global__ void __launch_bounds__(256) ppo_gae_kernel(const double *REW, const double *VAL, const double *VNEXT, const uint8_t *TERM, const uint8_t *DONE,
+                                                      int T, int E, double gamma, double lam, double *ADV, double *RET) {
+#pragma clang fp contract(off)
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    const double gl = gamma * lam;
+    double adv = 0.0;
+    for (int t = T - 1; t >= 0; --t) {
+        const long k = (long)t * E + e;
+        const double v = VAL[k];
+        const double nt = TERM[k] ? 0.0 : 1.0, nd = DONE[k] ? 0.0 : 1.0;
+        const double delta = (REW[k] + (gamma * nt) * VNEXT[k]) - v;
+        adv = delta + (gl * nd) * adv;
+        ADV[k] = adv, RET[k] = adv + v;
+    }
+}
+
+// The policy half of one minibatch update.  Rows b < M of the minibatch, j = idx[b] its row of the flattened [T E] tables:
+//     valid_b = 0 <= j < n_rows, OK[j], the re-solve accepted (status 0 or 2, u0_new finite), ACT, LOGP, ADV[j] finite
+//     A_b     = normalize_adv and more than one valid row ? (ADV[j] - mean) / (std + 1e-8) : ADV[j]      (unbiased std, as torch.std)
+//     r_b     = exp(logp_b - LOGP[j]);   loss_b = -min(r_b A_b, clip(r_b, 1 - eps, 1 + eps) A_b)
+//     g_mu = -A r (a - mu) / sigma^2,  g_ls = -A r ((a - mu)^2 / sigma^2 - 1);  both 0 where the clipped branch is the minimum
+// An invalid row is selected out (its u0_new / dpi_dp may be NaN); dpi_dp is read as nan_to_num does.
+constexpr int PPO_ROWS = 128, PPO_PMAX = 256, PPO_NS = 6, PPO_STAT_THREADS = 1024;
+// message / partial columns after the n_p gradient entries: sum g_ls, count, sum loss, sum (r - 1) - log r, clipped rows, sum r;
+// the message then carries the two advantage statistics: sum ADV and sum (ADV - mean)^2 over the valid rows
+constexpr int PPO_MSG_EXTRA = 8;
+
+struct PpoSurrogateArgs {
+    const int64_t *idx;           // [M]
+    int M, n_p;
+    int64_t n_rows;               // rows of the flattened tables
+    const double *ACT, *LOGP, *ADV;
+    const uint8_t *OK;
+    const double *u0_new;         // [M]
+    const int *status_new;        // [M]
+    const double *dpi;            // [M][1][n_p]
+    const double *log_std;        // [1]
+    double lo, hi, clip, ent_coef, lr;
+    int normalize;
+    double *partial;              // [n_blocks][n_p + PPO_NS]
+    unsigned int *ticket;         // [1], zero before the first launch (the kernel leaves it zero)
+    double *msg;                  // [n_p + PPO_MSG_EXTRA]
+};
+
+__device__ __forceinline__ bool ppo_row_valid(const PpoSurrogateArgs &a, int b, long &j) {
+    j = (long)a.idx[b];
+    if (j < 0 || j >= a.n_rows) return false;
+    return a.OK[j] != 0 && ppo_solve_ok(a.status_new[b], a.u0_new[b]) && isfinite(a.ACT[j]) && isfinite(a.LOGP[j]) && isfinite(a.ADV[j]);
+}
+
+// sum of v over the workgroup in a fixed order (a tree over the lanes' slots); every lane returns the total
+__device__ __forceinline__ double ppo_block_sum(double v, double *red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int m = PPO_STAT_THREADS / 2; m >= 1; m >>= 1) {
+        if ((int)threadIdx.x < m) red[threadIdx.x] += red[threadIdx.x + m];
+        __syncthreads();
+    }
+    const double s = red[0];
+    __syncthreads();
+    return s;
+}
+
+// one workgroup: msg[n_p + 1] = valid rows, msg[n_p + 6] = sum ADV, msg[n_p + 7] = sum (ADV - mean)^2 over them (two passes)
+__global__ void __launch_bounds__(PPO_STAT_THREADS) ppo_adv_stats_kernel(const PpoSurrogateArgs a) {
+    __shared__ double red[PPO_STAT_THREADS];
+    double n = 0.0, s = 0.0;
+    for (int b = threadIdx.x; b < a.M; b += PPO_STAT_THREADS) {
+        long j;
+        if (ppo_row_valid(a, b, j)) n += 1.0, s += a.ADV[j];
+    }
+    n = ppo_block_sum(n, red), s = ppo_block_sum(s, red);
+    const double mean = s / (n > 1.0 ? n : 1.0);
+    double q = 0.0;
+    for (int b = threadIdx.x; b < a.M; b += PPO_STAT_THREADS) {
+        long j;
+        if (ppo_row_valid(a, b, j)) {
+            const double d = a.ADV[j] - mean;
+            q += d * d;
+        }
+    }
+    q = ppo_block_sum(q, red);
+    if (threadIdx.x == 0) a.msg[a.n_p + 1] = n, a.msg[a.n_p + 6] = s, a.msg[a.n_p + 7] = q;
+}
+
+// Every workgroup sums PPO_ROWS rows into its partial; the last one to finish (a ticket) adds the partials in four slices of the
+// blocks, added in order (the scheme of qlearning_td_grad_kernel): the same inputs give the same bits.
+__global__ void __launch_bounds__(128) ppo_surrogate_kernel(const PpoSurrogateArgs a) {
+    __shared__ double w[PPO_ROWS];
+    __shared__ double sc[PPO_NS][PPO_ROWS];
+    __shared__ bool last;
+    __shared__ double fin[4][PPO_PMAX];
+    const long b0 = (long)blockIdx.x * PPO_ROWS;
+    const int P2 = a.n_p + PPO_NS;
+    const double n_valid = a.msg[a.n_p + 1];
+    double mean = 0.0, den = 1.0;
+    if (a.normalize && n_valid > 1.0) {
+        mean = a.msg[a.n_p + 6] / n_valid;
+        den = sqrt(a.msg[a.n_p + 7] / (n_valid - 1.0)) + 1e-8;
+    }
+    {
+        const long b = b0 + threadIdx.x;
+        double wj = 0.0, v[PPO_NS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        long j;
+        if (b < a.M && ppo_row_valid(a, (int)b, j)) {
+            const double ls = a.log_std[0], sigma = exp(ls), var = sigma * sigma;
+            const double A = (a.ADV[j] - mean) / den;
+            const double act = a.ACT[j];
+            const double mu = ppo_mean(a.u0_new[b], true, a.lo, a.hi);
+            const double logr = ppo_log_prob(act, mu, sigma, ls) - a.LOGP[j];
+            const double r = exp(logr);
+            const double rc = r < 1.0 - a.clip ? 1.0 - a.clip : (r > 1.0 + a.clip ? 1.0 + a.clip : r);
+            const double l1 = r * A, l2 = rc * A;
+            const bool flat = (A > 0.0 && r > 1.0 + a.clip) || (A < 0.0 && r < 1.0 - a.clip);      // the clipped branch is the minimum
+            const double d = act - mu;
+            const double g_mu = flat ? 0.0 : -(A * r) * (d / var);
+            const double g_ls = flat ? 0.0 : -(A * r) * (d * d / var - 1.0);
+            wj = g_mu * (2.0 / (a.hi - a.lo));
+            v[0] = g_ls, v[1] = 1.0, v[2] = -(l1 < l2 ? l1 : l2), v[3] = (r - 1.0) - logr, v[4] = fabs(r - 1.0) > a.clip ? 1.0 : 0.0, v[5] = r;
+        }
+        w[threadIdx.x] = wj;
+#pragma unroll
+        for (int q = 0; q < PPO_NS; ++q) sc[q][threadIdx.x] = v[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < PPO_NS) {
+        double s = 0.0;
+        for (int r = 0; r < PPO_ROWS; ++r) s += sc[threadIdx.x][r];
+        a.partial[(long)blockIdx.x * P2 + a.n_p + threadIdx.x] = s;
+    }
+    const int nr = (int)(a.M - b0 < PPO_ROWS ? a.M - b0 : PPO_ROWS);
+    const double *base = a.dpi + b0 * a.n_p;
+    for (int p = threadIdx.x; p < a.n_p; p += 128) {
+        double acc = 0.0;
+        int k = 0;
+        for (; k + 8 <= nr; k += 8) {
+            double v[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) v[q] = base[(long)(k + q) * a.n_p + p];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) acc = fma(w[k + q], nan_to_num_d(v[q]), acc);
+        }
+        for (; k < nr; ++k) acc = fma(w[k], nan_to_num_d(base[(long)k * a.n_p + p]), acc);
+        a.partial[(long)blockIdx.x * P2 + p] = acc;
+    }
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) last = atomicAdd(a.ticket, 1u) == gridDim.x - 1;
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    const int nb = gridDim.x, per = (nb + 3) / 4;
+    for (int p0 = 0; p0 < P2; p0 += PPO_PMAX) {
+        const int np = P2 - p0 < PPO_PMAX ? P2 - p0 : PPO_PMAX;
+        for (int e = threadIdx.x; e < 4 * np; e += 128) {
+            const int sl = e / np, p = p0 + e - sl * np;
+            const int lo = sl * per, hi = lo + per < nb ? lo + per : nb;
+            double acc = 0.0;
+            for (int k = lo; k < hi; ++k) acc += a.partial[(long)k * P2 + p];
+            fin[sl][e - sl * np] = acc;
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < np; e += 128) {
+            const int p = p0 + e;
+            double s = ((fin[0][e] + fin[1][e]) + fin[2][e]) + fin[3][e];
+            // the step of theta and of log_std: -lr x the sums (the entropy bonus adds -ent_coef to every valid row's g_ls)
+            if (p < a.n_p) s = -a.lr * s;
+            if (p == a.n_p) s = -a.lr * (s - a.ent_coef * n_valid);
+            a.msg[p] = s;
+        }
+        __syncthreads();
+    }
+    // the workspace is left all zero
+    for (long e = threadIdx.x; e < (long)nb * P2; e += 128) a.partial[e] = 0.0;
+    if (threadIdx.x == 0) *a.ticket = 0u;
+}
+
+// After the collective: log_std += msg[n_p] / max(1, msg[n_p + 1]) — the masked mean mpcrl_qlearning_apply takes for theta
+__global__ void ppo_log_std_apply_kernel(const double *msg, int n_p, double *log_std) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const double c = msg[n_p + 1] > 1.0 ? msg[n_p + 1] : 1.0;
+        log_std[0] = log_std[0] + msg[n_p] / c;
+    }
+}
+
+}  // namespace mpcrl

@@ -1,0 +1,409 @@
+"""Batched PPO with the MPC as Gaussian actor: the learner the reference declares and never finishes.
+
+``rlmpc/ppo/policies.py:26-134`` defines ``MPCActorCriticPolicy(ActorCriticPolicy)`` whose ``forward``, ``evaluate_actions`` and
+``predict_values`` raise NotImplementedError; only ``_predict`` works, one observation at a time through ``mpc.get_action``.  What the
+stub lacks is what the engine has: the policy mean and its parameter Jacobian du0*/dp for a whole batch in one call.  The policy is
+    a ~ N(mu, sigma^2),   mu = scale_action(u0*(s; theta)),   sigma = exp(log_std)        (one learnable, state-independent log_std)
+and PPO's clipped surrogate is differentiated through mu with dpi/dp of the re-solve.  Per roll-out step the loop is ONE batched solve
+over the E environments, one critic forward, ONE launch of mpcrl_ppo_cartpole_collect (sample, log probability, environment step, row t
+of the roll-out tables, resets, the next observation and cold mask) and one mpcrl_get_iterate_rows; after the roll-out one critic
+forward over the next states and ONE launch of mpcrl_ppo_gae.  Per minibatch of an epoch: mpcrl_set_iterate_rows (the re-solve starts
+from the iterate the roll-out's solve ended with), ONE solve with du0*/dp, mpcrl_ppo_surrogate_grad (the message [-lr sum g dpi/dp,
+-lr sum g_log_std, count, statistics]), the all-reduce of that message when there are ranks, mpcrl_qlearning_apply (theta, a masked
+mean) and mpcrl_ppo_log_std_apply, and the value network's MSE step.
+
+The value function is a 4 -> 64 -> 64 -> 1 tanh MLP in torch (activation_fn = nn.Tanh, Adam with eps = 1e-5, as the reference
+constructor says): framework plumbing, like TD3's critics before their kernels.  All PPO arithmetic outside it is fp64.
+``ppo_collect_terms``, ``ppo_gae`` and ``ppo_surrogate_terms`` state the three kernels in torch float64 (CPU-capable; what the tests
+hold the kernels to).  There is no CPU path for the learner: the solver has none.
+
+Differences from stable_baselines3's PPO, on purpose: the stored action is the unclipped sample and the environment sees its clip to
+[-1, 1] (SB3 does the same); a row whose roll-out solve or re-solve was not accepted (status other than 0 / 2, or u0 not finite) is left
+out of the surrogate — selected out, never multiplied by 0; advantages are normalised over the valid rows of the minibatch; the policy
+step is plain gradient descent with ``lr`` on theta's learnable entries and log_std (the MPC's parameters are a handful of physical
+quantities, the Q-learning and TD3 loops step them the same way), Adam is kept for the value network; there is no gradient clipping
+and no value clipping.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional, Tuple
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .batch import MPCBatch, _ptr
+from .envs import BatchedCartPoleSwingUpEnv
+
+_HALF_LOG_2PI = 0.9189385332046727
+MSG_EXTRA = 8        # message entries after the n_p gradient entries (include/mpcrl.h, mpcrl_ppo_surrogate_grad)
+
+
+# ---------------------------------------------------------------------- the kernels' arithmetic in torch float64
+def _solve_ok(u0: torch.Tensor, status: torch.Tensor) -> torch.Tensor:
+    return ((status == 0) | (status == 2)) & torch.isfinite(u0)
+
+
+def _mean(u0: torch.Tensor, ok: torch.Tensor, lo: float, hi: float) -> torch.Tensor:
+    u = torch.where(ok, u0, torch.zeros_like(u0))                  # selected: u0 of a rejected solve may be NaN
+    return torch.where(ok, 2.0 * ((u - lo) / (hi - lo)) - 1.0, torch.zeros_like(u))
+
+
+def _log_prob(a: torch.Tensor, mu: torch.Tensor, log_std: torch.Tensor) -> torch.Tensor:
+    sigma = torch.exp(log_std)
+    d = a - mu
+    return -(d * d) / (2.0 * (sigma * sigma)) - log_std - _HALF_LOG_2PI
+
+
+def _f64(t, like: Optional[torch.Tensor] = None) -> torch.Tensor:
+    return torch.as_tensor(t, dtype=torch.float64, device=None if like is None else like.device)
+
+
+def ppo_collect_terms(u0: torch.Tensor, status: torch.Tensor, eps: torch.Tensor, log_std, lo: float, hi: float
+                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The policy half of one roll-out step in torch (what mpcrl_ppo_cartpole_collect computes before the environment step).  u0 [E]
+    (or [E, 1]), status [E], eps [E] standard-normal draws, log_std a scalar (tensor or float).  Returns
+        mu [E] = ok ? 2 (u0 - lo) / (hi - lo) - 1 : 0,   act [E] = mu + exp(log_std) eps (unclipped),   logp [E],   ok [E] bool."""
+    u = _f64(u0).reshape(-1)
+    ls = _f64(log_std, u).reshape(())
+    ok = _solve_ok(u, status.reshape(-1))
+    mu = _mean(u, ok, lo, hi)
+    act = mu + torch.exp(ls) * eps.reshape(-1).to(torch.float64)
+    return mu, act, _log_prob(act, mu, ls), ok
+
+
+def ppo_gae(rew: torch.Tensor, val: torch.Tensor, vnext: torch.Tensor, term: torch.Tensor, done: torch.Tensor, gamma: float,
+            gae_lambda: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Generalised advantage estimates in torch (what mpcrl_ppo_gae computes); all [T, E]:
+        delta_t = rew_t + gamma (1 - term_t) vnext_t - val_t;  adv_t = delta_t + gamma lambda (1 - done_t) adv_{t+1}, adv_T = 0;  ret = adv + val
+    Returns adv, ret."""
+    T = rew.shape[0]
+    nt, nd = 1.0 - term.to(torch.float64), 1.0 - done.to(torch.float64)
+    adv = torch.zeros_like(rew)
+    run = torch.zeros_like(rew[0])
+    gl = gamma * gae_lambda
+    for t in range(T - 1, -1, -1):
+        delta = (rew[t] + (gamma * nt[t]) * vnext[t]) - val[t]
+        run = delta + (gl * nd[t]) * run
+        adv[t] = run
+    return adv, adv + val
+
+
+def ppo_surrogate_terms(idx: torch.Tensor, act: torch.Tensor, logp: torch.Tensor, adv: torch.Tensor, ok: torch.Tensor,
+                        u0_new: torch.Tensor, status_new: torch.Tensor, dpi_dp: torch.Tensor, log_std, lo: float, hi: float,
+                        clip_range: float, ent_coef: float, lr: float, normalize_adv: bool) -> torch.Tensor:
+    """The policy half of one minibatch update in torch (what mpcrl_ppo_surrogate_grad computes).  idx [M] rows of the flattened tables
+    act, logp, adv, ok; u0_new [M] (or [M, 1]), status_new [M], dpi_dp [M, 1, n_p] of the re-solve.  Returns msg [n_p + 8]:
+        [-lr sum g_mu 2/(hi-lo) dpi/dp (n_p), -lr (sum g_ls - ent_coef count), count, sum loss, sum (r - 1) - log r, rows with |r - 1| > eps,
+         sum r, sum ADV, sum (ADV - mean)^2]     over the valid rows (include/mpcrl.h)."""
+    act, logp, adv, okf = act.reshape(-1), logp.reshape(-1), adv.reshape(-1), ok.reshape(-1)
+    n_rows, M = act.numel(), idx.numel()
+    zero = torch.zeros(M, dtype=torch.float64, device=act.device)
+    inr = (idx >= 0) & (idx < n_rows)
+    j = idx.clamp(0, n_rows - 1)
+    a, lp_old, ad = act[j], logp[j], adv[j]
+    u = _f64(u0_new).reshape(-1)
+    ls = _f64(log_std, act).reshape(())
+    valid = inr & (okf[j] != 0) & _solve_ok(u, status_new.reshape(-1)) & torch.isfinite(a) & torch.isfinite(lp_old) & torch.isfinite(ad)
+    sel = lambda t: torch.where(valid, t, zero)                       # noqa: E731  (selected out, never multiplied by 0)
+    a, lp_old, ad = sel(a), sel(lp_old), sel(ad)
+    n = valid.sum().to(torch.float64)
+    s1 = ad.sum()
+    mean = s1 / torch.clamp(n, min=1.0)
+    s2 = sel((ad - mean) ** 2).sum()
+    A = ad
+    if normalize_adv:
+        std = torch.sqrt(s2 / torch.clamp(n - 1.0, min=1.0))
+        A = torch.where(n > 1.0, (ad - mean) / (std + 1e-8), ad)
+    mu = _mean(u, valid, lo, hi)
+    logr = _log_prob(a, mu, ls) - lp_old
+    r = torch.exp(logr)
+    l1, l2 = r * A, torch.clamp(r, 1.0 - clip_range, 1.0 + clip_range) * A
+    flat = ((A > 0.0) & (r > 1.0 + clip_range)) | ((A < 0.0) & (r < 1.0 - clip_range))     # the clipped branch is the minimum
+    var = torch.exp(ls) ** 2
+    d = a - mu
+    live = valid & ~flat
+    g_mu = torch.where(live, -(A * r) * (d / var), zero)
+    g_ls = torch.where(live, -(A * r) * (d * d / var - 1.0), zero)
+    G = torch.nan_to_num(dpi_dp.reshape(M, -1))
+    G = torch.where(valid[:, None], G, torch.zeros_like(G))
+    grad = ((g_mu * (2.0 / (hi - lo)))[:, None] * G).sum(0)
+    tail = torch.stack([-lr * (g_ls.sum() - ent_coef * n), n, sel(-torch.minimum(l1, l2)).sum(), sel((r - 1.0) - logr).sum(),
+                        sel(((r - 1.0).abs() > clip_range).to(torch.float64)).sum(), sel(r).sum(), s1, s2])
+    return torch.cat([-lr * grad, tail])
+
+
+# ---------------------------------------------------------------------- the policy
+class MPCActorCriticPolicy:
+    """The surface of rlmpc/ppo/policies.py:26-134 (``MPCActorCriticPolicy(ActorCriticPolicy)``), batched and without stable-baselines3:
+    ``_predict``, ``forward``, ``evaluate_actions``, ``predict_values`` with the reference's argument names.  ``mpc`` is an
+    ``OcpDescription`` (the reference passes its MPC object: here the policy owns a batched handle of ``batch`` instances built from
+    it); ``observation_space`` / ``action_space`` only need ``.shape``; ``lr_schedule`` is a callable of the remaining progress.
+    Every method is ONE batched solve where the reference solves one observation (or raises).  Actions are the scaled ones in [-1, 1]
+    (``MPC.scale_action``), float64 [B, 1]; the Gaussian's mean is the MPC's action, ``log_std`` a learnable scalar on the device
+    (``log_std_init`` as in the reference signature), the value function a 4 -> 64 -> 64 -> 1 ``activation_fn`` MLP with the
+    reference's optimiser settings (Adam, eps = 1e-5)."""
+
+    def __init__(self, observation_space, action_space, lr_schedule, mpc, batch: int = 1, device=None, activation_fn=nn.Tanh,
+                 ortho_init: bool = True, log_std_init: float = 0.0, net_arch=(64, 64), optimizer_class=torch.optim.Adam,
+                 optimizer_kwargs=None, generator: Optional[torch.Generator] = None):
+        if getattr(mpc, "nu", None) != 1:
+            raise ValueError("MPCActorCriticPolicy: one control (nu = 1)")
+        self.observation_space, self.action_space, self.ocp = observation_space, action_space, mpc
+        self.mpc = MPCBatch(mpc, batch, device)
+        dev = self.mpc.device
+        self.device = dev
+        self.lo, self.hi = float(mpc.lbu[0]), float(mpc.ubu[0])
+        self.theta = torch.as_tensor(mpc.p0, dtype=torch.float64, device=dev).clone()
+        self.log_std = torch.full((1,), float(log_std_init), dtype=torch.float64, device=dev)      # never rebound: kernels hold its address
+        obs_dim = int(observation_space.shape[0]) if observation_space is not None else mpc.nx
+        layers, last = [], obs_dim
+        for h in net_arch:
+            layers += [nn.Linear(last, h), activation_fn()]
+            last = h
+        layers.append(nn.Linear(last, 1))
+        self.value_net = nn.Sequential(*layers)
+        if ortho_init:       # SB3's ActorCriticPolicy._build: gain sqrt(2) for the hidden layers, 1 for the value head
+            lin = [m for m in self.value_net if isinstance(m, nn.Linear)]
+            for k, m in enumerate(lin):
+                nn.init.orthogonal_(m.weight, gain=1.0 if k == len(lin) - 1 else math.sqrt(2.0))
+                nn.init.zeros_(m.bias)
+        self.value_net.to(dev)
+        if optimizer_kwargs is None:
+            optimizer_kwargs = {}
+            if optimizer_class == torch.optim.Adam:
+                optimizer_kwargs["eps"] = 1e-5                           # policies.py:50-54
+                if dev.type == "cuda":                                   # no host synchronisation in a step
+                    optimizer_kwargs.update(fused=True, capturable=True)
+        self.optimizer = optimizer_class(self.value_net.parameters(), lr=float(lr_schedule(1)), **optimizer_kwargs)
+        self.gen = generator
+        self.training = True
+
+    def _solve_mean(self, obs: torch.Tensor):
+        r = self.mpc.solve(obs.to(torch.float64))
+        u = r.u0.reshape(-1)
+        ok = _solve_ok(u, r.status)
+        return _mean(u, ok, self.lo, self.hi), ok
+
+    def _sample(self, mu: torch.Tensor, deterministic: bool) -> torch.Tensor:
+        if deterministic:
+            return mu
+        eps = torch.randn(mu.shape, dtype=torch.float32, device=mu.device, generator=self.gen)
+        return mu + torch.exp(self.log_std[0]) * eps.to(torch.float64)
+
+    def predict_values(self, obs: torch.Tensor) -> torch.Tensor:
+        """[B, 1] float64: the value network at the observations."""
+        return self.value_net(obs.to(torch.float32)).to(torch.float64)
+
+    def _predict(self, observation: torch.Tensor, deterministic: bool = True) -> torch.Tensor:
+        mu, _ = self._solve_mean(observation)
+        return self._sample(mu, deterministic)[:, None]
+
+    def forward(self, obs: torch.Tensor, deterministic: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """actions [B, 1] (the unclipped sample, or the mean), values [B, 1], log_prob [B]."""
+        mu, _ = self._solve_mean(obs)
+        a = self._sample(mu, deterministic)
+        return a[:, None], self.predict_values(obs), _log_prob(a, mu, self.log_std[0])
+
+    __call__ = forward
+
+    def evaluate_actions(self, obs: torch.Tensor, actions: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """values [B, 1], log_prob [B] of ``actions`` under the current policy, entropy [B] of the Gaussian (log_std + 1/2 log 2 pi e)."""
+        mu, _ = self._solve_mean(obs)
+        a = actions.to(torch.float64).reshape(-1)
+        ent = (self.log_std[0] + (0.5 + _HALF_LOG_2PI)).expand(a.shape[0])
+        return self.predict_values(obs), _log_prob(a, mu, self.log_std[0]), ent
+
+    def set_training_mode(self, mode: bool) -> None:
+        self.value_net.train(mode)
+        self.training = mode
+
+
+class _Box:
+    def __init__(self, n: int):
+        self.shape = (n,)
+
+
+# ---------------------------------------------------------------------- the learner
+class BatchedPPO:
+    """PPO (clipped surrogate, GAE) of the cartpole MPC's parameters over E = ``env.num_envs`` parallel environments per rank.
+
+    ``collect()`` rolls out ``n_steps`` = T steps of all environments into [T, E] tables on the device and computes advantages and
+    returns; ``train()`` runs ``n_epochs`` passes over the T E samples in minibatches of ``batch_size``; ``learn(n)`` loops the two.
+    Neither synchronises with the host; ``last_stats()`` reads the statistics when asked.  The reference environment's ``reward`` is the
+    quadratic cost x^2 + theta^2: the default ``reward_scale = -1`` makes PPO maximise its negative (as BatchedTD3).  theta's
+    learnable entries are the OCP's model block (M, m, l); ``lr`` steps them and log_std, ``lr_value`` the value network (loss
+    ``vf_coef`` x MSE against the returns).  With a process ``group`` every rank owns its environments and handles; per minibatch the
+    surrogate's message and the value gradients are all-reduced, so all ranks hold the same theta, log_std and value network."""
+
+    def __init__(self, ocp, env, n_steps: int = 32, batch_size: int = 256, n_epochs: int = 4, gamma: float = 0.99, gae_lambda: float = 0.95,
+                 clip_range: float = 0.2, ent_coef: float = 0.0, vf_coef: float = 0.5, lr: float = 1e-4, lr_value: float = 3e-4,
+                 reward_scale: float = -1.0, normalize_advantage: bool = True, seed: int = 0, device=None, group=None,
+                 log_std_init: float = 0.0):
+        if getattr(ocp, "model", None) != _lib.MODEL_CARTPOLE or ocp.nu != 1 or ocp.nx != 4:
+            raise ValueError("BatchedPPO needs the cartpole OCP (cartpole_ocp())")
+        if not isinstance(env, BatchedCartPoleSwingUpEnv):
+            raise TypeError("BatchedPPO needs a BatchedCartPoleSwingUpEnv")
+        for name, v in (("n_steps", n_steps), ("batch_size", batch_size), ("n_epochs", n_epochs)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"{name} must be an int >= 1")
+        if (n_steps * env.num_envs) % batch_size != 0:
+            raise ValueError(f"n_steps * num_envs = {n_steps * env.num_envs} is not a multiple of batch_size = {batch_size}")
+        if not (0.0 < gamma <= 1.0) or not (0.0 <= gae_lambda <= 1.0):
+            raise ValueError("gamma must lie in (0, 1], gae_lambda in [0, 1]")
+        if not (math.isfinite(clip_range) and clip_range > 0.0):
+            raise ValueError("clip_range must be finite and > 0")
+        for name, v in (("ent_coef", ent_coef), ("vf_coef", vf_coef), ("lr", lr), ("lr_value", lr_value), ("log_std_init", log_std_init)):
+            if not math.isfinite(v):
+                raise ValueError(f"{name} must be finite")
+        if not (math.isfinite(reward_scale) and reward_scale != 0.0):
+            raise ValueError("reward_scale must be finite and not 0")
+        dev = env.device if device is None else torch.device(device)
+        if dev.type != "cuda" or env.device.type != "cuda":
+            raise RuntimeError("BatchedPPO runs on a HIP device (the environment's state too); there is no CPU fallback")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if env.device.index is not None and env.device != dev:
+            raise ValueError("the environment must live on the learner's device (its state is updated in place by the library)")
+        self.ocp, self.env, self.device, self.group = ocp, env, dev, group
+        self.T, self.E, self.B, self.n_epochs = n_steps, env.num_envs, batch_size, n_epochs
+        self.gamma, self.gae_lambda, self.clip_range, self.ent_coef, self.vf_coef = float(gamma), float(gae_lambda), float(clip_range), float(ent_coef), float(vf_coef)
+        self.lr, self.reward_scale, self.normalize_advantage = float(lr), float(reward_scale), bool(normalize_advantage)
+        T, E, B = self.T, self.E, self.B
+        rank = torch.distributed.get_rank(group) if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0
+        self.gen = torch.Generator(device=dev).manual_seed(seed + 1000 * rank)     # exploration / shuffling differ per rank
+        torch.manual_seed(seed)                                                    # identical value network on every rank
+        self.policy = MPCActorCriticPolicy(_Box(ocp.nx), _Box(ocp.nu), lambda _: lr_value, ocp, batch=E, device=dev, log_std_init=log_std_init,
+                                           generator=self.gen)
+        self.rollout_mpc = self.policy.mpc                        # keeps one warm-start iterate per environment
+        self.sample_mpc = MPCBatch(ocp, B, dev)                   # the minibatch re-solves: mu and dpi/dp
+        self.theta, self.log_std = self.policy.theta, self.policy.log_std          # updated in place
+        self.n_p = ocp.n_p
+        self.learn_mask = torch.zeros_like(self.theta)
+        self.learn_mask[: ocp.n_model_p] = 1.0                    # (M, m, l)
+        self.lo, self.hi = self.policy.lo, self.policy.hi
+        f64 = dict(dtype=torch.float64, device=dev)
+        u8 = dict(dtype=torch.uint8, device=dev)
+        # the roll-out tables, [T, E]; every buffer keeps its address
+        self.OBS, self.NEXT = torch.zeros(T, E, 4, **f64), torch.zeros(T, E, 4, **f64)
+        self.ACT, self.LOGP, self.VAL, self.REW = (torch.zeros(T, E, **f64) for _ in range(4))
+        self.ADV, self.RET, self.VNEXT = (torch.zeros(T, E, **f64) for _ in range(3))
+        self.TERM, self.DONE, self.OK = (torch.zeros(T, E, **u8) for _ in range(3))
+        # the iterates the roll-out's solves ended with, row t E + e (what the minibatch re-solves start from)
+        N, nw = ocp.N, ocp.nx + ocp.nu
+        self.iters = tuple(torch.zeros(T * E, n, **f64) for n in ((N + 1) * ocp.nx, N * ocp.nu, N * ocp.nx, 10 * (N + 1) * nw))
+        self._rows = torch.arange(T * E, dtype=torch.int64, device=dev).reshape(T, E)
+        self.obs = env.reset().to(dev).to(torch.float64).contiguous()
+        self.ended = torch.ones(E, dtype=torch.int32, device=dev)             # the first solve starts every instance cold
+        self.msg = torch.zeros(self.n_p + MSG_EXTRA, **f64)
+        self.step_out = torch.zeros(self.n_p, **f64)
+        self._stat = torch.zeros(MSG_EXTRA - 1, **f64)              # since the last train(): count, loss, kl, clipped, r, ADV sums
+        self._stat_rows = 0
+        self._lib = _lib.load()
+        nb = int(self._lib.mpcrl_ppo_surrogate_workspace_bytes(B, self.n_p))
+        if nb < 0:
+            raise RuntimeError(f"mpcrl_ppo_surrogate_workspace_bytes failed with {nb}")
+        self._ws = torch.zeros(nb, dtype=torch.uint8, device=dev)
+        # the roll-out handle holds an iterate from here on, so that its first solve is the per-instance cold start of the cold mask
+        self.rollout_mpc.solve(self.obs, cold=True)
+        self.iterations = 0
+
+    # ------------------------------------------------------------------ pieces
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _collect_step(self, t: int) -> None:
+        env, dev = self.env, self.device
+        r = self.rollout_mpc.solve(self.obs, cold_mask=self.ended)            # the policy mean of every environment, one launch
+        with torch.no_grad():
+            value = self.policy.predict_values(self.obs).reshape(self.E).contiguous()
+        eps = torch.randn(self.E, dtype=torch.float32, device=dev, generator=self.gen)
+        u01 = torch.rand(self.E, generator=env.gen, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            rc = self._lib.mpcrl_ppo_cartpole_collect(
+                env._par(), self.E, self.T, t, _ptr(env.state), _ptr(env.steps), _ptr(r.u0), _ptr(r.status), _ptr(eps), _ptr(u01), _ptr(value),
+                _ptr(self.log_std), self.lo, self.hi, self.reward_scale, _ptr(self.OBS), _ptr(self.ACT), _ptr(self.LOGP), _ptr(self.VAL),
+                _ptr(self.REW), _ptr(self.NEXT), _ptr(self.TERM), _ptr(self.DONE), _ptr(self.OK), _ptr(self.obs), _ptr(self.ended), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"mpcrl_ppo_cartpole_collect failed with {rc}")
+        self.rollout_mpc.get_iterate_rows(*self.iters, index=self._rows[t])
+
+    def collect(self) -> None:
+        """One roll-out: T steps of all E environments into the tables, then advantages and returns."""
+        for t in range(self.T):
+            self._collect_step(t)
+        with torch.no_grad():
+            self.VNEXT.copy_(self.policy.predict_values(self.NEXT.reshape(-1, 4)).reshape(self.T, self.E))
+        with torch.cuda.device(self.device):
+            rc = self._lib.mpcrl_ppo_gae(_ptr(self.REW), _ptr(self.VAL), _ptr(self.VNEXT), _ptr(self.TERM), _ptr(self.DONE), self.T, self.E,
+                                         self.gamma, self.gae_lambda, _ptr(self.ADV), _ptr(self.RET), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"mpcrl_ppo_gae failed with {rc}")
+
+    def _world(self) -> int:
+        import torch.distributed as dist
+        return dist.get_world_size(self.group) if (dist.is_available() and dist.is_initialized()) else 1
+
+    def _minibatch(self, idx: torch.Tensor) -> None:
+        import torch.distributed as dist
+        dev, B = self.device, self.B
+        obs = self.OBS.reshape(-1, 4).index_select(0, idx)
+        cold = (self.OK.reshape(-1).index_select(0, idx) == 0).to(torch.int32)     # no accepted roll-out solve: no iterate worth starting from
+        self.sample_mpc.set_iterate_rows(*self.iters, index=idx)
+        r = self.sample_mpc.solve(obs, sens_pi=True, cold_mask=cold)
+        with torch.cuda.device(dev):
+            rc = self._lib.mpcrl_ppo_surrogate_grad(
+                _ptr(idx), B, self.T * self.E, _ptr(self.ACT), _ptr(self.LOGP), _ptr(self.ADV), _ptr(self.OK), _ptr(r.u0), _ptr(r.status),
+                _ptr(r.dpi_dp), self.n_p, _ptr(self.log_std), self.lo, self.hi, self.clip_range, self.ent_coef, self.lr,
+                int(self.normalize_advantage), _ptr(self._ws), _ptr(self.msg), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"mpcrl_ppo_surrogate_grad failed with {rc}")
+        world = self._world()
+        if world > 1:
+            dist.all_reduce(self.msg, op=dist.ReduceOp.SUM, group=self.group)      # the one collective of the policy step
+        self._stat += self.msg[self.n_p + 1:]
+        self._stat_rows += B * world
+        with torch.cuda.device(dev):
+            rc = self._lib.mpcrl_qlearning_apply(_ptr(self.msg), self.n_p, _ptr(self.learn_mask), _ptr(self.theta), _ptr(self.step_out), self._stream())
+            rc2 = self._lib.mpcrl_ppo_log_std_apply(_ptr(self.msg), self.n_p, _ptr(self.log_std), self._stream())
+        if rc != 0 or rc2 != 0:
+            raise RuntimeError(f"mpcrl_qlearning_apply / mpcrl_ppo_log_std_apply failed with {rc} / {rc2}")
+        for m in (self.rollout_mpc, self.sample_mpc):
+            m.set_theta(self.theta)
+        # the value network's step on the returns
+        ret = self.RET.reshape(-1).index_select(0, idx).to(torch.float32)
+        opt = self.policy.optimizer
+        opt.zero_grad(set_to_none=False)
+        loss = self.vf_coef * torch.nn.functional.mse_loss(self.policy.value_net(obs.to(torch.float32)).reshape(B), ret)
+        loss.backward()
+        if world > 1:
+            for p in self.policy.value_net.parameters():
+                dist.all_reduce(p.grad, op=dist.ReduceOp.SUM, group=self.group)
+                p.grad /= world
+        opt.step()
+
+    def train(self) -> None:
+        """n_epochs passes over the roll-out's T E samples in shuffled minibatches of batch_size."""
+        self._stat.zero_()
+        self._stat_rows = 0
+        n = self.T * self.E
+        for _ in range(self.n_epochs):
+            perm = torch.randperm(n, generator=self.gen, device=self.device)
+            for k in range(n // self.B):
+                self._minibatch(perm[k * self.B:(k + 1) * self.B])
+
+    def learn(self, n_iterations: int = 1) -> "BatchedPPO":
+        for _ in range(n_iterations):
+            self.collect()
+            self.train()
+            self.iterations += 1
+        return self
+
+    def last_stats(self) -> dict:
+        """Statistics of the last train() (means over the valid rows of its minibatches) and of the last roll-out.  Reads the device."""
+        cnt, loss, kl, clipped, ratio, _, _ = self._stat.tolist()
+        c = max(1.0, cnt)
+        return {"policy_loss": loss / c, "approx_kl": kl / c, "clip_fraction": clipped / c, "mean_ratio": ratio / c,
+                "valid_fraction": cnt / max(1, self._stat_rows), "mean_reward": float(self.REW.mean().item()) / self.reward_scale,
+                "log_std": float(self.log_std.item())}
