@@ -35,8 +35,8 @@
  *     scripts/cartpole_mpc_qlearning.py:255-269
  *   MPCActorCriticPolicy.forward / evaluate_actions /          mpcrl_ppo_cartpole_collect, mpcrl_ppo_gae,
  *   predict_values (NotImplementedError in the reference)       mpcrl_ppo_surrogate_grad / mpcrl_ppo_surrogate_workspace_bytes,
- *   and the PPO roll-out / update around them                   mpcrl_ppo_log_std_apply
- *     rlmpc/ppo/policies.py:26-134
+ *   and the PPO roll-out / update around them                   mpcrl_ppo_log_std_apply,
+ *     rlmpc/ppo/policies.py:26-134                               mpcrl_value_forward, mpcrl_value_mse_grad / mpcrl_value_workspace_bytes
  *
  * Conventions
  *   - plain C, no torch types.  Every array argument of mpcrl_solve / *_iterate / mpcrl_reset /
@@ -91,7 +91,8 @@ extern "C" {
  *        message there no longer turns a frozen theta_i into NaN (behaviour; the signature is unchanged)
  *        additions under 132 (no existing export changed, so no bump): mpcrl_ppo_cartpole_collect; mpcrl_ppo_gae;
  *        mpcrl_ppo_surrogate_grad / mpcrl_ppo_surrogate_workspace_bytes; mpcrl_ppo_log_std_apply (batched PPO with the MPC as
- *        Gaussian actor, cartpole) */
+ *        Gaussian actor, cartpole); round 8: mpcrl_value_forward; mpcrl_value_mse_grad / mpcrl_value_workspace_bytes (PPO's value
+ *        function as library kernels) */
 #define MPCRL_ABI_VERSION 132
 
 enum { MPCRL_MODEL_CARTPOLE = 0, MPCRL_MODEL_LINEAR = 1, MPCRL_MODEL_CHAIN = 2 };
@@ -439,6 +440,31 @@ int mpcrl_ppo_surrogate_grad(const int64_t *idx, int M, int64_t n_rows, const do
 /* Added under ABI 132.  After the collective (and next to mpcrl_qlearning_apply, which steps theta from the same message as a masked mean):
  * log_std[0] += msg[n_p] / max(1, msg[n_p + 1]). */
 int mpcrl_ppo_log_std_apply(const double *msg, int n_p, double *log_std, void *stream);
+
+/* Added under ABI 132.  PPO's value function (value_kernel.hpp): the MLP MPCActorCriticPolicy builds by default, nx -> 64 -> 64 -> 1 with
+ * tanh, float; `params` holds it in torch's parameter order, W1 [64][nx] | b1 [64] | W2 [64][64] | b2 [64] | W3 [64] | b3 [1] (row-major
+ * [out][in]: the per-net layout of mpcrl_critic_td_grad), n_params = 64 nx + 4289.  Inputs are PPO's double tables, rounded to float on
+ * load; the network is evaluated in float, every sum over rows is accumulated in double in a fixed order.  All device pointers.
+ *
+ * values[b] = V(obs[b]) for n rows: obs [n][nx] double, values [n] double.  No masking: a non-finite row gives a non-finite value,
+ * as the framework path does.  One launch (n = 0: none). */
+int mpcrl_value_forward(const double *obs, int64_t n, int nx, const float *params, double *values, void *stream);
+
+/* Added under ABI 132.  One minibatch of the value loss, two launches.  OBS [n_rows][nx] double, RET [n_rows] double (PPO's tables,
+ * flattened), idx [M] int64.
+ *   valid_b = 0 <= idx[b] < n_rows and the nx entries of OBS[idx[b]] and RET[idx[b]] are finite        (selected out, never multiplied by 0)
+ *   e_b     = valid_b ? V(OBS[idx[b]]) - (float)RET[idx[b]] : 0
+ *   loss    = vf_coef * sum_b e_b^2 / max(1, sum_b valid_b)                    -> out[n_params]
+ *   count   = sum_b valid_b                                                     -> out[n_params + 1]
+ *   grad    = out_scale * d loss / d params (double, order of `params`)         -> out[0 .. n_params)
+ *   workspace: mpcrl_value_workspace_bytes(M, nx) bytes of device memory owned by the caller; it needs no initialisation, before or
+ *   between calls (every entry read is written by the same call).
+ * The partial sums are reduced in a fixed order (no atomics, no ticket): the same inputs give the same bits.  1 <= nx <= 16, hidden width
+ * 64, tanh only; MPCRL_E_ARG otherwise, and for M < 1, a NULL pointer or a negative n_rows.  Handle-less (launched on the device that owns
+ * `out`), capture-safe: no allocation, no host synchronisation. */
+int64_t mpcrl_value_workspace_bytes(int M, int nx);
+int mpcrl_value_mse_grad(const double *OBS, const double *RET, const int64_t *idx, int M, int64_t n_rows, int nx, const float *params,
+                         double vf_coef, double out_scale, void *workspace, double *out, void *stream);
 
 /* Bytes of device memory held by the handle; library version (MPCRL_ABI_VERSION of the header it was built from). */
 int64_t mpcrl_workspace_bytes(mpcrl_handle h);

@@ -21,6 +21,7 @@
 #include "td3_kernel.hpp"
 #include "qlearning_kernel.hpp"
 #include "ppo_kernel.hpp"
+#include "value_kernel.hpp"
 
 using namespace mpcrl;
 
@@ -790,6 +791,35 @@ int mpcrl_ppo_log_std_apply(const double *msg, int n_p, double *log_std, void *s
     if (!msg || n_p < 1 || !log_std) return MPCRL_E_ARG;
     ON_DEVICE_OF(log_std);
     hipLaunchKernelGGL(ppo_log_std_apply_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, msg, n_p, log_std);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int mpcrl_value_forward(const double *obs, int64_t n, int nx, const float *params, double *values, void *stream) {
+    if (!obs || !params || !values || n < 0 || nx < 1 || nx > VALUE_DMAX || (n + VALUE_S - 1) / VALUE_S > 0x7fffffffLL) return MPCRL_E_ARG;
+    if (n == 0) return 0;
+    ON_DEVICE_OF(values);
+    hipLaunchKernelGGL(value_forward_kernel, dim3((unsigned)((n + VALUE_S - 1) / VALUE_S)), dim3(VALUE_NT), 0, (hipStream_t)stream, obs, (long)n, nx, params,
+                       values);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int64_t mpcrl_value_workspace_bytes(int M, int nx) {
+    if (M < 1 || nx < 1 || nx > VALUE_DMAX) return MPCRL_E_ARG;
+    return (((int64_t)M + VALUE_S - 1) / VALUE_S) * (value_n_params(nx) + 2) * (int64_t)sizeof(double);
+}
+
+int mpcrl_value_mse_grad(const double *OBS, const double *RET, const int64_t *idx, int M, int64_t n_rows, int nx, const float *params, double vf_coef,
+                         double out_scale, void *workspace, double *out, void *stream) {
+    if (!OBS || !RET || !idx || !params || !workspace || !out || M < 1 || n_rows < 0 || nx < 1 || nx > VALUE_DMAX) return MPCRL_E_ARG;
+    ON_DEVICE_OF(out);
+    ValueMseArgs a;
+    a.OBS = OBS, a.RET = RET, a.idx = idx, a.M = M, a.nx = nx, a.n_rows = (long)n_rows, a.params = params, a.partial = (double *)workspace;
+    const int n_blocks = (int)(((int64_t)M + VALUE_S - 1) / VALUE_S), n_params = value_n_params(nx);
+    hipLaunchKernelGGL(value_mse_partial_kernel, dim3(n_blocks), dim3(VALUE_NT), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(value_mse_reduce_kernel, dim3((n_params + 1 + 63) / 64), dim3(256), 0, (hipStream_t)stream, (const double *)workspace, n_blocks, nx,
+                       vf_coef, out_scale, out);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -12,10 +12,15 @@ from the iterate the roll-out's solve ended with), ONE solve with du0*/dp, mpcrl
 -lr sum g_log_std, count, statistics]), the all-reduce of that message when there are ranks, mpcrl_qlearning_apply (theta, a masked
 mean) and mpcrl_ppo_log_std_apply, and the value network's MSE step.
 
-The value function is a 4 -> 64 -> 64 -> 1 tanh MLP in torch (activation_fn = nn.Tanh, Adam with eps = 1e-5, as the reference
-constructor says): framework plumbing, like TD3's critics before their kernels.  All PPO arithmetic outside it is fp64.
-``ppo_collect_terms``, ``ppo_gae`` and ``ppo_surrogate_terms`` state the three kernels in torch float64 (CPU-capable; what the tests
-hold the kernels to).  There is no CPU path for the learner: the solver has none.
+The value function is a 4 -> 64 -> 64 -> 1 tanh MLP (activation_fn = nn.Tanh, Adam with eps = 1e-5, as the reference constructor
+says), float32; all PPO arithmetic outside it is fp64.  By default it is a torch module run by the framework.  With
+``value_kernels=True`` (csrc/value_kernel.hpp) its parameters and gradients are views of two flat float32 buffers, ``predict_values``
+is ONE launch of mpcrl_value_forward on the float64 observations (one per roll-out step, one over all T E next states), and a
+minibatch's value step is mpcrl_value_mse_grad on the tables themselves with ``idx`` (two launches: the forward pass, the MSE over the
+valid rows and the backward pass by hand, message [gradient / world, loss, count]), ONE all-reduce of that message when there are
+ranks, one cast-copy into the flat gradient buffer and the same fused Adam step.  The default stays the framework path.
+``ppo_collect_terms``, ``ppo_gae``, ``ppo_surrogate_terms`` and ``ppo_value_terms`` state the kernels in torch (CPU-capable; what the
+tests hold the kernels to).  There is no CPU path for the learner: the solver has none.
 
 Differences from stable_baselines3's PPO, on purpose: the stored action is the unclipped sample and the environment sees its clip to
 [-1, 1] (SB3 does the same); a row whose roll-out solve or re-solve was not accepted (status other than 0 / 2, or u0 not finite) is left
@@ -134,6 +139,36 @@ def ppo_surrogate_terms(idx: torch.Tensor, act: torch.Tensor, logp: torch.Tensor
     return torch.cat([-lr * grad, tail])
 
 
+def ppo_value_terms(OBS: torch.Tensor, RET: torch.Tensor, idx: torch.Tensor, value_net: nn.Module, vf_coef: float
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The value half of one minibatch update in torch (what mpcrl_value_mse_grad computes).  OBS [..., nx] and RET [...] are the
+    roll-out tables (flattened here), idx [M] rows of them, ``value_net`` the MLP in any dtype (float64: the yardstick of the tests).
+        valid_b = 0 <= idx[b] < n_rows and OBS[idx[b]], RET[idx[b]] finite          (selected out, never multiplied by 0)
+        e_b     = valid_b ? V(OBS[idx[b]]) - RET[idx[b]] : 0,      loss = vf_coef sum e_b^2 / max(1, count)
+    with OBS and RET rounded to float32 first, as the kernel loads them.  Returns loss (0-dim), count (0-dim int64) and d loss / d
+    parameters through autograd, flat in ``value_net.parameters()`` order."""
+    params = list(value_net.parameters())
+    dt = params[0].dtype
+    nx = OBS.shape[-1]
+    obs, ret = OBS.reshape(-1, nx), RET.reshape(-1)
+    n_rows, M = ret.numel(), idx.numel()
+    inr = (idx >= 0) & (idx < n_rows)
+    if n_rows > 0:
+        j = idx.clamp(0, n_rows - 1)
+        o, r = obs[j], ret[j]
+    else:
+        o, r = obs.new_zeros(M, nx), ret.new_zeros(M)
+    valid = inr & torch.isfinite(o).all(dim=1) & torch.isfinite(r)
+    x = torch.where(valid[:, None], o, torch.zeros_like(o)).to(torch.float32).to(dt)
+    y = torch.where(valid, r, torch.zeros_like(r)).to(torch.float32).to(dt)
+    v = value_net(x).reshape(M)
+    e = torch.where(valid, v - y, torch.zeros_like(v))
+    n = valid.sum()
+    loss = vf_coef * (e * e).sum() / torch.clamp(n, min=1).to(dt)
+    grads = torch.autograd.grad(loss, params)
+    return loss.detach(), n, torch.cat([g.reshape(-1) for g in grads])
+
+
 # ---------------------------------------------------------------------- the policy
 class MPCActorCriticPolicy:
     """The surface of rlmpc/ppo/policies.py:26-134 (``MPCActorCriticPolicy(ActorCriticPolicy)``), batched and without stable-baselines3:
@@ -143,21 +178,31 @@ class MPCActorCriticPolicy:
     Every method is ONE batched solve where the reference solves one observation (or raises).  Actions are the scaled ones in [-1, 1]
     (``MPC.scale_action``), float64 [B, 1]; the Gaussian's mean is the MPC's action, ``log_std`` a learnable scalar on the device
     (``log_std_init`` as in the reference signature), the value function a 4 -> 64 -> 64 -> 1 ``activation_fn`` MLP with the
-    reference's optimiser settings (Adam, eps = 1e-5)."""
+    reference's optimiser settings (Adam, eps = 1e-5).  ``value_kernels=True`` (net_arch (64, 64), nn.Tanh, at most 16 observations;
+    ValueError otherwise): the network's parameters and gradients are views of the flat float32 buffers ``value_flat`` /
+    ``value_grad_flat`` (``td3.flatten_parameters``) and ``predict_values`` is one mpcrl_value_forward launch without an autograd
+    graph; the module stays usable as a torch module (nothing may rebind its ``p.data`` or ``p.grad``)."""
 
     def __init__(self, observation_space, action_space, lr_schedule, mpc, batch: int = 1, device=None, activation_fn=nn.Tanh,
                  ortho_init: bool = True, log_std_init: float = 0.0, net_arch=(64, 64), optimizer_class=torch.optim.Adam,
-                 optimizer_kwargs=None, generator: Optional[torch.Generator] = None):
+                 optimizer_kwargs=None, generator: Optional[torch.Generator] = None, value_kernels: bool = False):
         if getattr(mpc, "nu", None) != 1:
             raise ValueError("MPCActorCriticPolicy: one control (nu = 1)")
+        obs_dim = int(observation_space.shape[0]) if observation_space is not None else mpc.nx
+        self.value_kernels = bool(value_kernels)
+        if self.value_kernels and (tuple(net_arch) != (64, 64) or activation_fn is not nn.Tanh or not 1 <= obs_dim <= 16):
+            raise ValueError("value_kernels=True: the library kernels are written for net_arch=(64, 64), activation_fn=nn.Tanh and "
+                             f"1 <= observations <= 16 (got {tuple(net_arch)}, {getattr(activation_fn, '__name__', activation_fn)}, {obs_dim})")
         self.observation_space, self.action_space, self.ocp = observation_space, action_space, mpc
         self.mpc = MPCBatch(mpc, batch, device)
         dev = self.mpc.device
         self.device = dev
+        if self.value_kernels and not (dev.type == "cuda" and torch.version.hip):
+            raise RuntimeError("value_kernels=True needs a HIP device; there is no CPU fallback")
         self.lo, self.hi = float(mpc.lbu[0]), float(mpc.ubu[0])
         self.theta = torch.as_tensor(mpc.p0, dtype=torch.float64, device=dev).clone()
         self.log_std = torch.full((1,), float(log_std_init), dtype=torch.float64, device=dev)      # never rebound: kernels hold its address
-        obs_dim = int(observation_space.shape[0]) if observation_space is not None else mpc.nx
+        self.obs_dim = obs_dim
         layers, last = [], obs_dim
         for h in net_arch:
             layers += [nn.Linear(last, h), activation_fn()]
@@ -170,6 +215,11 @@ class MPCActorCriticPolicy:
                 nn.init.orthogonal_(m.weight, gain=1.0 if k == len(lin) - 1 else math.sqrt(2.0))
                 nn.init.zeros_(m.bias)
         self.value_net.to(dev)
+        self.value_flat = self.value_grad_flat = None
+        if self.value_kernels:
+            from .td3 import flatten_parameters
+            self.value_flat, self.value_grad_flat = flatten_parameters(self.value_net)
+            self._lib = _lib.load()
         if optimizer_kwargs is None:
             optimizer_kwargs = {}
             if optimizer_class == torch.optim.Adam:
@@ -193,8 +243,16 @@ class MPCActorCriticPolicy:
         return mu + torch.exp(self.log_std[0]) * eps.to(torch.float64)
 
     def predict_values(self, obs: torch.Tensor) -> torch.Tensor:
-        """[B, 1] float64: the value network at the observations."""
-        return self.value_net(obs.to(torch.float32)).to(torch.float64)
+        """[B, 1] float64: the value network at the observations (``value_kernels``: one launch, no autograd graph)."""
+        if not self.value_kernels:
+            return self.value_net(obs.to(torch.float32)).to(torch.float64)
+        o = obs.to(device=self.device, dtype=torch.float64).reshape(-1, self.obs_dim).contiguous()
+        out = torch.empty(o.shape[0], 1, dtype=torch.float64, device=self.device)
+        rc = self._lib.mpcrl_value_forward(_ptr(o), o.shape[0], self.obs_dim, _ptr(self.value_flat), _ptr(out),
+                                           torch.cuda.current_stream(self.device).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"mpcrl_value_forward failed with {rc}")
+        return out
 
     def _predict(self, observation: torch.Tensor, deterministic: bool = True) -> torch.Tensor:
         mu, _ = self._solve_mean(observation)
@@ -235,12 +293,14 @@ class BatchedPPO:
     quadratic cost x^2 + theta^2: the default ``reward_scale = -1`` makes PPO maximise its negative (as BatchedTD3).  theta's
     learnable entries are the OCP's model block (M, m, l); ``lr`` steps them and log_std, ``lr_value`` the value network (loss
     ``vf_coef`` x MSE against the returns).  With a process ``group`` every rank owns its environments and handles; per minibatch the
-    surrogate's message and the value gradients are all-reduced, so all ranks hold the same theta, log_std and value network."""
+    surrogate's message and the value gradients are all-reduced, so all ranks hold the same theta, log_std and value network.
+    ``value_kernels=True`` runs the value function as library kernels (the module docstring; ``MPCActorCriticPolicy``); the default is
+    the framework path."""
 
     def __init__(self, ocp, env, n_steps: int = 32, batch_size: int = 256, n_epochs: int = 4, gamma: float = 0.99, gae_lambda: float = 0.95,
                  clip_range: float = 0.2, ent_coef: float = 0.0, vf_coef: float = 0.5, lr: float = 1e-4, lr_value: float = 3e-4,
                  reward_scale: float = -1.0, normalize_advantage: bool = True, seed: int = 0, device=None, group=None,
-                 log_std_init: float = 0.0):
+                 log_std_init: float = 0.0, value_kernels: bool = False):
         if getattr(ocp, "model", None) != _lib.MODEL_CARTPOLE or ocp.nu != 1 or ocp.nx != 4:
             raise ValueError("BatchedPPO needs the cartpole OCP (cartpole_ocp())")
         if not isinstance(env, BatchedCartPoleSwingUpEnv):
@@ -275,7 +335,8 @@ class BatchedPPO:
         self.gen = torch.Generator(device=dev).manual_seed(seed + 1000 * rank)     # exploration / shuffling differ per rank
         torch.manual_seed(seed)                                                    # identical value network on every rank
         self.policy = MPCActorCriticPolicy(_Box(ocp.nx), _Box(ocp.nu), lambda _: lr_value, ocp, batch=E, device=dev, log_std_init=log_std_init,
-                                           generator=self.gen)
+                                           generator=self.gen, value_kernels=value_kernels)
+        self.value_kernels = self.policy.value_kernels
         self.rollout_mpc = self.policy.mpc                        # keeps one warm-start iterate per environment
         self.sample_mpc = MPCBatch(ocp, B, dev)                   # the minibatch re-solves: mu and dpi/dp
         self.theta, self.log_std = self.policy.theta, self.policy.log_std          # updated in place
@@ -305,6 +366,15 @@ class BatchedPPO:
         if nb < 0:
             raise RuntimeError(f"mpcrl_ppo_surrogate_workspace_bytes failed with {nb}")
         self._ws = torch.zeros(nb, dtype=torch.uint8, device=dev)
+        self._vloss = torch.zeros((), dtype=torch.float32, device=dev)      # vf_coef x MSE of the last minibatch (summed over the ranks)
+        if self.value_kernels:
+            nb = int(self._lib.mpcrl_value_workspace_bytes(B, ocp.nx))
+            if nb < 0:
+                raise RuntimeError(f"mpcrl_value_workspace_bytes failed with {nb}")
+            self.n_value = self.policy.value_flat.numel()
+            self._vws = torch.empty(nb, dtype=torch.uint8, device=dev)      # written in full by every call: no initialisation
+            self.vmsg = torch.zeros(self.n_value + 2, **f64)               # [gradient / world, loss, count]
+            self._vloss = self.vmsg[self.n_value]
         # the roll-out handle holds an iterate from here on, so that its first solve is the per-instance cold start of the cold mask
         self.rollout_mpc.solve(self.obs, cold=True)
         self.iterations = 0
@@ -371,12 +441,30 @@ class BatchedPPO:
             raise RuntimeError(f"mpcrl_qlearning_apply / mpcrl_ppo_log_std_apply failed with {rc} / {rc2}")
         for m in (self.rollout_mpc, self.sample_mpc):
             m.set_theta(self.theta)
-        # the value network's step on the returns
+        self._value_step(idx, obs, world)
+
+    def _value_step(self, idx: torch.Tensor, obs: torch.Tensor, world: int) -> None:
+        """The value network's step on the returns of the minibatch ``idx`` (``obs``: its observations, float64 [B, 4])."""
+        import torch.distributed as dist
+        dev, B = self.device, self.B
+        if self.value_kernels:
+            with torch.cuda.device(dev):
+                rc = self._lib.mpcrl_value_mse_grad(_ptr(self.OBS), _ptr(self.RET), _ptr(idx), B, self.T * self.E, self.ocp.nx,
+                                                    _ptr(self.policy.value_flat), self.vf_coef, 1.0 / world, _ptr(self._vws), _ptr(self.vmsg),
+                                                    self._stream())
+            if rc != 0:
+                raise RuntimeError(f"mpcrl_value_mse_grad failed with {rc}")
+            if world > 1:
+                dist.all_reduce(self.vmsg, op=dist.ReduceOp.SUM, group=self.group)     # the one collective of the value step
+            self.policy.value_grad_flat.copy_(self.vmsg[: self.n_value])
+            self.policy.optimizer.step()
+            return
         ret = self.RET.reshape(-1).index_select(0, idx).to(torch.float32)
         opt = self.policy.optimizer
         opt.zero_grad(set_to_none=False)
         loss = self.vf_coef * torch.nn.functional.mse_loss(self.policy.value_net(obs.to(torch.float32)).reshape(B), ret)
         loss.backward()
+        self._vloss = loss.detach()
         if world > 1:
             for p in self.policy.value_net.parameters():
                 dist.all_reduce(p.grad, op=dist.ReduceOp.SUM, group=self.group)
@@ -401,9 +489,11 @@ class BatchedPPO:
         return self
 
     def last_stats(self) -> dict:
-        """Statistics of the last train() (means over the valid rows of its minibatches) and of the last roll-out.  Reads the device."""
+        """Statistics of the last train() (means over the valid rows of its minibatches) and of the last roll-out; ``value_loss`` is the
+        MSE of the last minibatch's value step (its loss / vf_coef; NaN when vf_coef = 0).  Reads the device."""
         cnt, loss, kl, clipped, ratio, _, _ = self._stat.tolist()
         c = max(1.0, cnt)
+        vl = float(self._vloss.item()) / (self._world() if self.value_kernels else 1)      # (the message's loss entry is summed over the ranks)
         return {"policy_loss": loss / c, "approx_kl": kl / c, "clip_fraction": clipped / c, "mean_ratio": ratio / c,
                 "valid_fraction": cnt / max(1, self._stat_rows), "mean_reward": float(self.REW.mean().item()) / self.reward_scale,
-                "log_std": float(self.log_std.item())}
+                "log_std": float(self.log_std.item()), "value_loss": vl / self.vf_coef if self.vf_coef != 0.0 else float("nan")}
