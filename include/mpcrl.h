@@ -37,6 +37,9 @@
  *   predict_values (NotImplementedError in the reference)       mpcrl_ppo_surrogate_grad / mpcrl_ppo_surrogate_workspace_bytes,
  *   and the PPO roll-out / update around them                   mpcrl_ppo_log_std_apply,
  *     rlmpc/ppo/policies.py:26-134                               mpcrl_value_forward, mpcrl_value_mse_grad / mpcrl_value_workspace_bytes
+ *   mpc.get_action + env.step + replay_buffer.add of the       mpcrl_qlearning_linear_collect  (PPO on the same plant:
+ *   linear system's Q-learning roll-out                          mpcrl_ppo_linear_collect)
+ *     rlmpc/examples/linear_system_mpc_qlearning.py:160-172
  *
  * Conventions
  *   - plain C, no torch types.  Every array argument of mpcrl_solve / *_iterate / mpcrl_reset /
@@ -92,7 +95,8 @@ extern "C" {
  *        additions under 132 (no existing export changed, so no bump): mpcrl_ppo_cartpole_collect; mpcrl_ppo_gae;
  *        mpcrl_ppo_surrogate_grad / mpcrl_ppo_surrogate_workspace_bytes; mpcrl_ppo_log_std_apply (batched PPO with the MPC as
  *        Gaussian actor, cartpole); round 8: mpcrl_value_forward; mpcrl_value_mse_grad / mpcrl_value_workspace_bytes (PPO's value
- *        function as library kernels) */
+ *        function as library kernels); mpcrl_qlearning_linear_collect; mpcrl_ppo_linear_collect (the linear system's Q-learning and
+ *        PPO roll-out steps) */
 #define MPCRL_ABI_VERSION 132
 
 enum { MPCRL_MODEL_CARTPOLE = 0, MPCRL_MODEL_LINEAR = 1, MPCRL_MODEL_CHAIN = 2 };
@@ -465,6 +469,37 @@ int mpcrl_value_forward(const double *obs, int64_t n, int nx, const float *param
 int64_t mpcrl_value_workspace_bytes(int M, int nx);
 int mpcrl_value_mse_grad(const double *OBS, const double *RET, const int64_t *idx, int M, int64_t n_rows, int nx, const float *params,
                          double vf_coef, double out_scale, void *workspace, double *out, void *stream);
+
+/* Added under ABI 132.  The linear system's learner loops around the solves (linear_loop_kernel.hpp; mpc4rl_amd/qlearning_linear.py,
+ * mpc4rl_amd/ppo.py), nu = 1, one lane per environment, all arithmetic fp64.  par: the 12 HOST doubles of mpcrl_env_linear_step, state
+ * [E][2] as there; the environment step is that call's arithmetic (a shared device function: the same bits).  Handle-less (launched on the
+ * device that owns `state` / `OBS`), asynchronous on `stream`, capture-safe.  E = 0: nothing is launched.
+ *
+ * One roll-out step of the Q-learning loop after the policy's solve, one launch — rlmpc/examples/linear_system_mpc_qlearning.py:160-172
+ * per step after mpc.get_action.  u0, status [E]: the solve; eps [T][E] float standard-normal draws and u01 [T][E] uniform draws (the
+ * environment's noise), row r = row[env] of both read; lo < hi = lbu, ubu.
+ *   a = status in {0, 2} and u0 finite ? u0 : 0;   sigma > 0: a = clip(a + (double)(float(sigma) eps), lo, hi)   (the float product is
+ *   rounded first, then the fp64 sum and the clip; sigma = 0: a is u0 itself — the example explores nothing and scales no action);
+ *   the environment is stepped with a and u01.
+ * Row r of the episode table: S [T][E][2] = s_r (the state BEFORE the step), A [T][E] = a, C [T][E] = the step's cost.  state is updated in
+ * place, obs [E][2] = the new state (the next solve's x0), cold [E] int32 = 0, row [E] int32 advances by one; an environment whose row is
+ * outside [0, T) is left alone: nothing is written, nothing is stepped.  The environment never terminates: there is no liveness. */
+int mpcrl_qlearning_linear_collect(const double *par, int E, int T, double *state, const double *u0, const int32_t *status, const float *eps,
+                                   const double *u01, double lo, double hi, double sigma, double *obs, int32_t *row, int32_t *cold, double *S,
+                                   double *A, double *C, void *stream);
+
+/* Added under ABI 132.  One roll-out step of PPO on the linear system after the policy's solve, one launch: mpcrl_ppo_cartpole_collect with
+ * this plant.  u0, status, eps [E], value, log_std, lo < hi, reward_scale, 0 <= t < T and the tables' row t as there (OBS, NEXT [T][E][2]);
+ * u01 [E]: the environment's noise of this step.  mu, a, logp, OK as there; the environment is stepped with clip(a, -1, 1);
+ * REW = reward_scale * cost; TERM = 0 (the plant never terminates); steps [E] int64 is the CALLER's count of steps since the last reset
+ * (the environment keeps none): DONE = steps + 1 >= episode_length (>= 1), a truncation, so mpcrl_ppo_gae bootstraps through it from NEXT,
+ * the state BEFORE the reset.  A done environment restarts at reset_state (2 HOST doubles, read at the call) with steps = 0; obs [E][2] =
+ * the state after that, ended [E] int32 = DONE. */
+int mpcrl_ppo_linear_collect(const double *par, int E, int T, int t, double *state, int64_t *steps, const double *u0, const int32_t *status,
+                             const float *eps, const double *u01, const double *value, const double *log_std, double lo, double hi,
+                             double reward_scale, int64_t episode_length, const double *reset_state, double *OBS, double *ACT, double *LOGP,
+                             double *VAL, double *REW, double *NEXT, uint8_t *TERM, uint8_t *DONE, uint8_t *OK, double *obs, int32_t *ended,
+                             void *stream);
 
 /* Bytes of device memory held by the handle; library version (MPCRL_ABI_VERSION of the header it was built from). */
 int64_t mpcrl_workspace_bytes(mpcrl_handle h);

@@ -83,26 +83,38 @@ struct LinearEnvPar {
     double A[4], B[2], lb_noise, ub_noise, low[2], high[2];
 };
 
+// one environment's step (shared by env_linear_step_kernel and the roll-out kernels of linear_loop_kernel.hpp: the same expressions, the
+// same bits)
+struct LinearStepOut {
+    double s0, s1, cost;
+};
+__device__ __forceinline__ LinearStepOut linear_env_step(const LinearEnvPar &p, double x0, double x1, double a, double u01) {
+    const double n0 = p.lb_noise + (p.ub_noise - p.lb_noise) * u01;
+    const double s0 = (x0 * p.A[0] + x1 * p.A[1]) + a * p.B[0] + n0;
+    const double s1 = (x0 * p.A[2] + x1 * p.A[3]) + a * p.B[1];
+    const double lower = (p.low[0] - s0 > 0.0 || p.low[1] - s1 > 0.0) ? 1e2 : 0.0;
+    const double upper = (s0 - p.high[0] > 0.0 || s1 - p.high[1] > 0.0) ? 1e2 : 0.0;
+    LinearStepOut o;
+    o.s0 = s0, o.s1 = s1;
+    o.cost = 0.5 * (s0 * s0 + s1 * s1) + 0.5 * (a * a) + lower + upper;
+    return o;
+}
+
 template <class OBS>
 __global__ void __launch_bounds__(256) env_linear_step_kernel(const LinearEnvPar p, int B, double *state, const double *action, const double *u01,
                                                               OBS *obs, double *cost) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= B) return;
     const double2 s = reinterpret_cast<const double2 *>(state)[i];
-    const double a = action[i];
-    const double n0 = p.lb_noise + (p.ub_noise - p.lb_noise) * u01[i];
-    const double s0 = (s.x * p.A[0] + s.y * p.A[1]) + a * p.B[0] + n0;
-    const double s1 = (s.x * p.A[2] + s.y * p.A[3]) + a * p.B[1];
-    reinterpret_cast<double2 *>(state)[i] = make_double2(s0, s1);
+    const LinearStepOut o = linear_env_step(p, s.x, s.y, action[i], u01[i]);
+    reinterpret_cast<double2 *>(state)[i] = make_double2(o.s0, o.s1);
     if (obs) {
         if constexpr (sizeof(OBS) == 8)
-            reinterpret_cast<double2 *>(obs)[i] = make_double2(s0, s1);
+            reinterpret_cast<double2 *>(obs)[i] = make_double2(o.s0, o.s1);
         else
-            reinterpret_cast<float2 *>(obs)[i] = make_float2((float)s0, (float)s1);
+            reinterpret_cast<float2 *>(obs)[i] = make_float2((float)o.s0, (float)o.s1);
     }
-    const double lower = (p.low[0] - s0 > 0.0 || p.low[1] - s1 > 0.0) ? 1e2 : 0.0;
-    const double upper = (s0 - p.high[0] > 0.0 || s1 - p.high[1] > 0.0) ? 1e2 : 0.0;
-    cost[i] = 0.5 * (s0 * s0 + s1 * s1) + 0.5 * (a * a) + lower + upper;
+    cost[i] = o.cost;
 }
 
 // The actor's output stage for a batch (round 6): what rlmpc/td3/policies.py:186-213 + MPC.scale_action (rlmpc/mpc/common/mpc.py:290-301) + TD3's

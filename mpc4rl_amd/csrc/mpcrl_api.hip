@@ -22,6 +22,7 @@
 #include "qlearning_kernel.hpp"
 #include "ppo_kernel.hpp"
 #include "value_kernel.hpp"
+#include "linear_loop_kernel.hpp"
 
 using namespace mpcrl;
 
@@ -880,19 +881,61 @@ int mpcrl_critic_dq_da(const float *obs, int obs_stride, int B, int nx, int nu, 
     return 0;
 }
 
+// the 12 doubles of mpcrl_env_linear_step's `par` (host memory)
+static LinearEnvPar linear_env_par(const double *par) {
+    LinearEnvPar p;
+    for (int i = 0; i < 4; ++i) p.A[i] = par[i];
+    p.B[0] = par[4], p.B[1] = par[5], p.lb_noise = par[6], p.ub_noise = par[7];
+    p.low[0] = par[8], p.low[1] = par[9], p.high[0] = par[10], p.high[1] = par[11];
+    return p;
+}
+
 int mpcrl_env_linear_step(const double *par, int B, double *state, const double *action, const double *u01, void *obs, int obs_f32,
                           double *cost, void *stream) {
     if (!par || B < 0 || !state || !action || !u01 || !cost) return MPCRL_E_ARG;
     if (B == 0) return 0;
     ON_DEVICE_OF(state);
-    LinearEnvPar p;
-    for (int i = 0; i < 4; ++i) p.A[i] = par[i];
-    p.B[0] = par[4], p.B[1] = par[5], p.lb_noise = par[6], p.ub_noise = par[7];
-    p.low[0] = par[8], p.low[1] = par[9], p.high[0] = par[10], p.high[1] = par[11];
+    const LinearEnvPar p = linear_env_par(par);
     if (obs_f32)
         hipLaunchKernelGGL(env_linear_step_kernel<float>, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, p, B, state, action, u01, (float *)obs, cost);
     else
         hipLaunchKernelGGL(env_linear_step_kernel<double>, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, p, B, state, action, u01, (double *)obs, cost);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int mpcrl_qlearning_linear_collect(const double *par, int E, int T, double *state, const double *u0, const int32_t *status, const float *eps,
+                                   const double *u01, double lo, double hi, double sigma, double *obs, int32_t *row, int32_t *cold, double *S,
+                                   double *A, double *C, void *stream) {
+    if (!par || E < 0 || T < 1 || !state || !u0 || !status || !eps || !u01 || !obs || !row || !cold || !S || !A || !C || !(hi > lo)) return MPCRL_E_ARG;
+    if (E == 0) return 0;
+    ON_DEVICE_OF(state);
+    QlLinearCollectArgs a;
+    a.par = linear_env_par(par);
+    a.E = E, a.T = T, a.state = state, a.u0 = u0, a.status = (const int *)status, a.eps = eps, a.u01 = u01, a.lo = lo, a.hi = hi;
+    a.sigma = (float)sigma, a.obs = obs, a.row = row, a.cold = cold, a.S = S, a.A = A, a.C = C;
+    hipLaunchKernelGGL(qlearning_linear_collect_kernel, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int mpcrl_ppo_linear_collect(const double *par, int E, int T, int t, double *state, int64_t *steps, const double *u0, const int32_t *status,
+                             const float *eps, const double *u01, const double *value, const double *log_std, double lo, double hi,
+                             double reward_scale, int64_t episode_length, const double *reset_state, double *OBS, double *ACT, double *LOGP,
+                             double *VAL, double *REW, double *NEXT, uint8_t *TERM, uint8_t *DONE, uint8_t *OK, double *obs, int32_t *ended,
+                             void *stream) {
+    if (!par || E < 0 || T < 1 || t < 0 || t >= T || episode_length < 1 || !reset_state || !state || !steps || !u0 || !status || !eps || !u01 ||
+        !value || !log_std || !(hi > lo) || !OBS || !ACT || !LOGP || !VAL || !REW || !NEXT || !TERM || !DONE || !OK || !obs || !ended)
+        return MPCRL_E_ARG;
+    if (E == 0) return 0;
+    ON_DEVICE_OF(OBS);
+    PpoLinearCollectArgs a;
+    a.par = linear_env_par(par);
+    a.E = E, a.T = T, a.t = t, a.state = state, a.steps = steps, a.u0 = u0, a.status = (const int *)status, a.eps = eps, a.u01 = u01, a.value = value;
+    a.log_std = log_std, a.lo = lo, a.hi = hi, a.reward_scale = reward_scale, a.episode_length = episode_length;
+    a.reset0 = reset_state[0], a.reset1 = reset_state[1];
+    a.OBS = OBS, a.ACT = ACT, a.LOGP = LOGP, a.VAL = VAL, a.REW = REW, a.NEXT = NEXT, a.TERM = TERM, a.DONE = DONE, a.OK = OK, a.obs = obs, a.ended = ended;
+    hipLaunchKernelGGL(ppo_linear_collect_kernel, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -12,7 +12,7 @@ from the iterate the roll-out's solve ended with), ONE solve with du0*/dp, mpcrl
 -lr sum g_log_std, count, statistics]), the all-reduce of that message when there are ranks, mpcrl_qlearning_apply (theta, a masked
 mean) and mpcrl_ppo_log_std_apply, and the value network's MSE step.
 
-The value function is a 4 -> 64 -> 64 -> 1 tanh MLP (activation_fn = nn.Tanh, Adam with eps = 1e-5, as the reference constructor
+The value function is an nx -> 64 -> 64 -> 1 tanh MLP (activation_fn = nn.Tanh, Adam with eps = 1e-5, as the reference constructor
 says), float32; all PPO arithmetic outside it is fp64.  By default it is a torch module run by the framework.  With
 ``value_kernels=True`` (csrc/value_kernel.hpp) its parameters and gradients are views of two flat float32 buffers, ``predict_values``
 is ONE launch of mpcrl_value_forward on the float64 observations (one per roll-out step, one over all T E next states), and a
@@ -31,6 +31,7 @@ and no value clipping.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from typing import Optional, Tuple
 
@@ -39,7 +40,8 @@ import torch.nn as nn
 
 from . import _lib
 from .batch import MPCBatch, _ptr
-from .envs import BatchedCartPoleSwingUpEnv
+from .envs import BatchedCartPoleSwingUpEnv, BatchedLinearSystemEnv
+from .qlearning_linear import linear_env_par, linear_env_step_terms
 
 _HALF_LOG_2PI = 0.9189385332046727
 MSG_EXTRA = 8        # message entries after the n_p gradient entries (include/mpcrl.h, mpcrl_ppo_surrogate_grad)
@@ -76,6 +78,22 @@ def ppo_collect_terms(u0: torch.Tensor, status: torch.Tensor, eps: torch.Tensor,
     mu = _mean(u, ok, lo, hi)
     act = mu + torch.exp(ls) * eps.reshape(-1).to(torch.float64)
     return mu, act, _log_prob(act, mu, ls), ok
+
+
+def ppo_linear_collect_terms(par, state: torch.Tensor, steps: torch.Tensor, act: torch.Tensor, u01: torch.Tensor, reward_scale: float,
+                              episode_length: int, reset_state=(0.5, 0.5)):
+    """The environment half of one roll-out step on the linear system in torch (what mpcrl_ppo_linear_collect computes after the sample;
+    the policy half is ``ppo_collect_terms``).  par: the 12 doubles of ``qlearning_linear.linear_env_par``; state [E, 2], steps [E] int64
+    (steps since the last reset), act [E] the unclipped sample, u01 [E] the environment's noise.  The environment sees clip(act, -1, 1);
+    the plant never terminates, an episode is truncated after ``episode_length`` steps and restarts at ``reset_state``.  Returns
+        NEXT [E, 2] (the state after the step, before any reset),  REW [E] = reward_scale * cost,  DONE [E] bool = steps + 1 >= episode_length,
+        the state [E, 2] and the step count [E] after the resets."""
+    applied = torch.clamp(act.to(torch.float64).reshape(-1), -1.0, 1.0)
+    nxt, cost = linear_env_step_terms(par, state.to(torch.float64), applied, u01.to(torch.float64))
+    n = steps.to(torch.int64) + 1
+    done = n >= episode_length
+    rs = torch.as_tensor(reset_state, dtype=torch.float64, device=nxt.device).reshape(1, 2)
+    return nxt, reward_scale * cost, done, torch.where(done[:, None], rs.expand_as(nxt), nxt), torch.where(done, torch.zeros_like(n), n)
 
 
 def ppo_gae(rew: torch.Tensor, val: torch.Tensor, vnext: torch.Tensor, term: torch.Tensor, done: torch.Tensor, gamma: float,
@@ -177,7 +195,7 @@ class MPCActorCriticPolicy:
     it); ``observation_space`` / ``action_space`` only need ``.shape``; ``lr_schedule`` is a callable of the remaining progress.
     Every method is ONE batched solve where the reference solves one observation (or raises).  Actions are the scaled ones in [-1, 1]
     (``MPC.scale_action``), float64 [B, 1]; the Gaussian's mean is the MPC's action, ``log_std`` a learnable scalar on the device
-    (``log_std_init`` as in the reference signature), the value function a 4 -> 64 -> 64 -> 1 ``activation_fn`` MLP with the
+    (``log_std_init`` as in the reference signature), the value function an nx -> 64 -> 64 -> 1 ``activation_fn`` MLP with the
     reference's optimiser settings (Adam, eps = 1e-5).  ``value_kernels=True`` (net_arch (64, 64), nn.Tanh, at most 16 observations;
     ValueError otherwise): the network's parameters and gradients are views of the flat float32 buffers ``value_flat`` /
     ``value_grad_flat`` (``td3.flatten_parameters``) and ``predict_values`` is one mpcrl_value_forward launch without an autograd
@@ -285,13 +303,17 @@ class _Box:
 
 # ---------------------------------------------------------------------- the learner
 class BatchedPPO:
-    """PPO (clipped surrogate, GAE) of the cartpole MPC's parameters over E = ``env.num_envs`` parallel environments per rank.
+    """PPO (clipped surrogate, GAE) of the cartpole or the linear-system MPC's parameters over E = ``env.num_envs`` parallel environments
+    per rank: ``cartpole_ocp()`` with a ``BatchedCartPoleSwingUpEnv``, or ``linear_system_ocp()`` with a ``BatchedLinearSystemEnv`` and
+    ``episode_length`` (that plant never terminates and its environment counts no steps: the learner truncates an episode after
+    ``episode_length`` steps and restarts it at the environment's reset state; the roll-out step is mpcrl_ppo_linear_collect, the reward
+    is the step's cost, all 12 parameters A, B, b, V_0, f are learned).  The cartpole's limit is the environment's ``max_episode_steps``.
 
     ``collect()`` rolls out ``n_steps`` = T steps of all environments into [T, E] tables on the device and computes advantages and
     returns; ``train()`` runs ``n_epochs`` passes over the T E samples in minibatches of ``batch_size``; ``learn(n)`` loops the two.
     Neither synchronises with the host; ``last_stats()`` reads the statistics when asked.  The reference environment's ``reward`` is the
     quadratic cost x^2 + theta^2: the default ``reward_scale = -1`` makes PPO maximise its negative (as BatchedTD3).  theta's
-    learnable entries are the OCP's model block (M, m, l); ``lr`` steps them and log_std, ``lr_value`` the value network (loss
+    learnable entries are the OCP's model block (cartpole: M, m, l); ``lr`` steps them and log_std, ``lr_value`` the value network (loss
     ``vf_coef`` x MSE against the returns).  With a process ``group`` every rank owns its environments and handles; per minibatch the
     surrogate's message and the value gradients are all-reduced, so all ranks hold the same theta, log_std and value network.
     ``value_kernels=True`` runs the value function as library kernels (the module docstring; ``MPCActorCriticPolicy``); the default is
@@ -300,11 +322,23 @@ class BatchedPPO:
     def __init__(self, ocp, env, n_steps: int = 32, batch_size: int = 256, n_epochs: int = 4, gamma: float = 0.99, gae_lambda: float = 0.95,
                  clip_range: float = 0.2, ent_coef: float = 0.0, vf_coef: float = 0.5, lr: float = 1e-4, lr_value: float = 3e-4,
                  reward_scale: float = -1.0, normalize_advantage: bool = True, seed: int = 0, device=None, group=None,
-                 log_std_init: float = 0.0, value_kernels: bool = False):
-        if getattr(ocp, "model", None) != _lib.MODEL_CARTPOLE or ocp.nu != 1 or ocp.nx != 4:
-            raise ValueError("BatchedPPO needs the cartpole OCP (cartpole_ocp())")
-        if not isinstance(env, BatchedCartPoleSwingUpEnv):
-            raise TypeError("BatchedPPO needs a BatchedCartPoleSwingUpEnv")
+                 log_std_init: float = 0.0, value_kernels: bool = False, episode_length: Optional[int] = None):
+        model = getattr(ocp, "model", None)
+        self.linear = model == _lib.MODEL_LINEAR
+        if self.linear:
+            if ocp.nu != 1 or ocp.nx != 2:
+                raise ValueError("BatchedPPO needs the cartpole OCP (cartpole_ocp()) or the linear-system OCP (linear_system_ocp())")
+            if isinstance(episode_length, bool) or not isinstance(episode_length, int) or episode_length < 1:
+                raise ValueError("episode_length must be an int >= 1 with the linear system (its environment has no step limit)")
+            if not isinstance(env, BatchedLinearSystemEnv):
+                raise TypeError("BatchedPPO with the linear-system OCP needs a BatchedLinearSystemEnv")
+        else:
+            if model != _lib.MODEL_CARTPOLE or ocp.nu != 1 or ocp.nx != 4:
+                raise ValueError("BatchedPPO needs the cartpole OCP (cartpole_ocp()) or the linear-system OCP (linear_system_ocp())")
+            if not isinstance(env, BatchedCartPoleSwingUpEnv):
+                raise TypeError("BatchedPPO needs a BatchedCartPoleSwingUpEnv")
+            if episode_length is not None:
+                raise ValueError("episode_length is for the linear system; the cartpole's limit is the environment's max_episode_steps")
         for name, v in (("n_steps", n_steps), ("batch_size", batch_size), ("n_epochs", n_epochs)):
             if isinstance(v, bool) or not isinstance(v, int) or v < 1:
                 raise ValueError(f"{name} must be an int >= 1")
@@ -342,12 +376,13 @@ class BatchedPPO:
         self.theta, self.log_std = self.policy.theta, self.policy.log_std          # updated in place
         self.n_p = ocp.n_p
         self.learn_mask = torch.zeros_like(self.theta)
-        self.learn_mask[: ocp.n_model_p] = 1.0                    # (M, m, l)
+        self.learn_mask[: ocp.n_model_p] = 1.0                    # cartpole: (M, m, l); linear system: all of A, B, b, V_0, f
         self.lo, self.hi = self.policy.lo, self.policy.hi
         f64 = dict(dtype=torch.float64, device=dev)
         u8 = dict(dtype=torch.uint8, device=dev)
         # the roll-out tables, [T, E]; every buffer keeps its address
-        self.OBS, self.NEXT = torch.zeros(T, E, 4, **f64), torch.zeros(T, E, 4, **f64)
+        nx = self.nx = ocp.nx
+        self.OBS, self.NEXT = torch.zeros(T, E, nx, **f64), torch.zeros(T, E, nx, **f64)
         self.ACT, self.LOGP, self.VAL, self.REW = (torch.zeros(T, E, **f64) for _ in range(4))
         self.ADV, self.RET, self.VNEXT = (torch.zeros(T, E, **f64) for _ in range(3))
         self.TERM, self.DONE, self.OK = (torch.zeros(T, E, **u8) for _ in range(3))
@@ -356,6 +391,11 @@ class BatchedPPO:
         self.iters = tuple(torch.zeros(T * E, n, **f64) for n in ((N + 1) * ocp.nx, N * ocp.nu, N * ocp.nx, 10 * (N + 1) * nw))
         self._rows = torch.arange(T * E, dtype=torch.int64, device=dev).reshape(T, E)
         self.obs = env.reset().to(dev).to(torch.float64).contiguous()
+        if self.linear:
+            self.episode_length = episode_length
+            self.steps = torch.zeros(E, dtype=torch.int64, device=dev)      # steps since the last reset (the environment keeps no count)
+            self._par_c = (C.c_double * 12)(*linear_env_par(env))           # the environment's parameters, read here
+            self._reset_c = (C.c_double * 2)(*env.state[0].tolist())        # what BatchedLinearSystemEnv.reset writes
         self.ended = torch.ones(E, dtype=torch.int32, device=dev)             # the first solve starts every instance cold
         self.msg = torch.zeros(self.n_p + MSG_EXTRA, **f64)
         self.step_out = torch.zeros(self.n_p, **f64)
@@ -390,13 +430,22 @@ class BatchedPPO:
             value = self.policy.predict_values(self.obs).reshape(self.E).contiguous()
         eps = torch.randn(self.E, dtype=torch.float32, device=dev, generator=self.gen)
         u01 = torch.rand(self.E, generator=env.gen, dtype=torch.float64, device=dev)
+        tables = (_ptr(self.OBS), _ptr(self.ACT), _ptr(self.LOGP), _ptr(self.VAL), _ptr(self.REW), _ptr(self.NEXT), _ptr(self.TERM), _ptr(self.DONE),
+                  _ptr(self.OK), _ptr(self.obs), _ptr(self.ended), self._stream())
         with torch.cuda.device(dev):
-            rc = self._lib.mpcrl_ppo_cartpole_collect(
-                env._par(), self.E, self.T, t, _ptr(env.state), _ptr(env.steps), _ptr(r.u0), _ptr(r.status), _ptr(eps), _ptr(u01), _ptr(value),
-                _ptr(self.log_std), self.lo, self.hi, self.reward_scale, _ptr(self.OBS), _ptr(self.ACT), _ptr(self.LOGP), _ptr(self.VAL),
-                _ptr(self.REW), _ptr(self.NEXT), _ptr(self.TERM), _ptr(self.DONE), _ptr(self.OK), _ptr(self.obs), _ptr(self.ended), self._stream())
+            if self.linear:      # u01: the environment's noise of this step; truncation at episode_length, restart at the reset state
+                name = "mpcrl_ppo_linear_collect"
+                rc = self._lib.mpcrl_ppo_linear_collect(
+                    self._par_c, self.E, self.T, t, _ptr(env.state), _ptr(self.steps), _ptr(r.u0), _ptr(r.status), _ptr(eps), _ptr(u01), _ptr(value),
+                    _ptr(self.log_std), self.lo, self.hi, self.reward_scale, self.episode_length, self._reset_c, *tables)
+            else:
+                name = "mpcrl_ppo_cartpole_collect"
+                rc = self._lib.mpcrl_ppo_cartpole_collect(
+                    env._par(), self.E, self.T, t, _ptr(env.state), _ptr(env.steps), _ptr(r.u0), _ptr(r.status), _ptr(eps), _ptr(u01), _ptr(value),
+                    _ptr(self.log_std), self.lo, self.hi, self.reward_scale, *tables)
         if rc != 0:
-            raise RuntimeError(f"mpcrl_ppo_cartpole_collect failed with {rc}")
+            raise RuntimeError(f"{name} failed with {rc}")
+        self.last_collect = (r, eps, u01, value)                              # the step's solve and draws (what the tests re-state it from)
         self.rollout_mpc.get_iterate_rows(*self.iters, index=self._rows[t])
 
     def collect(self) -> None:
@@ -404,7 +453,7 @@ class BatchedPPO:
         for t in range(self.T):
             self._collect_step(t)
         with torch.no_grad():
-            self.VNEXT.copy_(self.policy.predict_values(self.NEXT.reshape(-1, 4)).reshape(self.T, self.E))
+            self.VNEXT.copy_(self.policy.predict_values(self.NEXT.reshape(-1, self.nx)).reshape(self.T, self.E))
         with torch.cuda.device(self.device):
             rc = self._lib.mpcrl_ppo_gae(_ptr(self.REW), _ptr(self.VAL), _ptr(self.VNEXT), _ptr(self.TERM), _ptr(self.DONE), self.T, self.E,
                                          self.gamma, self.gae_lambda, _ptr(self.ADV), _ptr(self.RET), self._stream())
@@ -418,7 +467,7 @@ class BatchedPPO:
     def _minibatch(self, idx: torch.Tensor) -> None:
         import torch.distributed as dist
         dev, B = self.device, self.B
-        obs = self.OBS.reshape(-1, 4).index_select(0, idx)
+        obs = self.OBS.reshape(-1, self.nx).index_select(0, idx)
         cold = (self.OK.reshape(-1).index_select(0, idx) == 0).to(torch.int32)     # no accepted roll-out solve: no iterate worth starting from
         self.sample_mpc.set_iterate_rows(*self.iters, index=idx)
         r = self.sample_mpc.solve(obs, sens_pi=True, cold_mask=cold)
@@ -444,7 +493,7 @@ class BatchedPPO:
         self._value_step(idx, obs, world)
 
     def _value_step(self, idx: torch.Tensor, obs: torch.Tensor, world: int) -> None:
-        """The value network's step on the returns of the minibatch ``idx`` (``obs``: its observations, float64 [B, 4])."""
+        """The value network's step on the returns of the minibatch ``idx`` (``obs``: its observations, float64 [B, nx])."""
         import torch.distributed as dist
         dev, B = self.device, self.B
         if self.value_kernels:
