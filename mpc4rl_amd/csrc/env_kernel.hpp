@@ -61,13 +61,22 @@ __global__ void __launch_bounds__(256) env_cartpole_step_kernel(const CartpoleEn
     truncated[i] = n >= p.max_episode_steps;
 }
 
+// the state an episode starts from (:178-180), as its (x, xd) and (theta, thetad) pairs; the caller zeroes the step count
+struct CartpoleState {
+    double2 s01, s23;
+};
+__device__ __forceinline__ CartpoleState cartpole_env_reset(double u01) {
+    return {make_double2(0.0, 0.0), make_double2((0.9 + 0.2 * u01) * 3.141592653589793, 0.0)};
+}
+
 template <class OBS>
 __global__ void __launch_bounds__(256) env_cartpole_reset_kernel(int B, double *state, int64_t *steps, const uint8_t *mask, const double *u01, OBS *obs) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= B) return;
     if (!mask || mask[i]) {
-        reinterpret_cast<double2 *>(state)[2 * i] = make_double2(0.0, 0.0);
-        reinterpret_cast<double2 *>(state)[2 * i + 1] = make_double2((0.9 + 0.2 * u01[i]) * 3.141592653589793, 0.0);
+        const CartpoleState s = cartpole_env_reset(u01[i]);
+        reinterpret_cast<double2 *>(state)[2 * i] = s.s01;
+        reinterpret_cast<double2 *>(state)[2 * i + 1] = s.s23;
         steps[i] = 0;
     }
     if (obs) {

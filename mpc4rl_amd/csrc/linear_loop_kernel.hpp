@@ -3,8 +3,8 @@
 // environment.
 //   qlearning_linear_collect_kernel   after the policy's solve: the action (optionally explored), the environment step, row t of the
 //                                     episode table, the observation and the cold mask of the next solve
-//   ppo_linear_collect_kernel         after the policy's solve: the sample and its log probability, the environment step, row t of the
-//                                     roll-out tables, the truncation at episode_length with the reset of those environments
+//   PpoLinearEnv                      the plant of ppo_collect_kernel (ppo_kernel.hpp): the environment step, the truncation at
+//                                     episode_length with the reset of those environments
 // The environment step is linear_env_step of env_kernel.hpp (the same bits as mpcrl_env_linear_step); PPO's mean and log probability are
 // the device functions of ppo_kernel.hpp, shared with the surrogate.  The environment never terminates: there is no liveness in the
 // Q-learning table, and PPO's TERM is all zero (an episode ends by truncation only, so GAE bootstraps through every end).
@@ -60,57 +60,19 @@ __global__ void __launch_bounds__(256) qlearning_linear_collect_kernel(const QlL
     a.cold[i] = 0;
 }
 
-struct PpoLinearCollectArgs {
+// PPO's plant (ppo_collect_kernel<PpoLinearEnv>): the environment never terminates, an episode is truncated after episode_length steps
+// and starts again from a fixed state (BatchedLinearSystemEnv.reset)
+struct PpoLinearEnv {
+    static constexpr int PAIRS = 1;
     LinearEnvPar par;
-    int E, T, t;
-    double *state;            // [E][2] the environments' states
-    int64_t *steps;           // [E] steps since the last reset (the learner's: the environment keeps no count)
-    const double *u0;         // [E] the policy's solve: control
-    const int *status;        // [E]
-    const float *eps;         // [E] standard-normal draws
-    const double *u01;        // [E] uniform draws (the environment's noise)
-    const double *value;      // [E] the critic at the observation just solved
-    const double *log_std;    // [1]
-    double lo, hi, reward_scale;
-    int64_t episode_length;   // an episode is truncated after this many steps
-    double reset0, reset1;    // the state an episode starts from
-    double *OBS, *ACT, *LOGP, *VAL, *REW, *NEXT;      // [T][E] ([..][2] for OBS, NEXT)
-    uint8_t *TERM, *DONE, *OK;                        // [T][E]
-    double *obs;              // [E][2] out: the next solve's x0 (after resets)
-    int32_t *ended;           // [E] out: 1 = the episode ended (the next solve starts that instance cold)
-};
-
-__global__ void __launch_bounds__(256) ppo_linear_collect_kernel(const PpoLinearCollectArgs a) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.E) return;
-    const double ls = a.log_std[0], sigma = exp(ls);
-    const double u = a.u0[i];
-    const bool ok = ppo_solve_ok(a.status[i], u);
-    const double mu = ppo_mean(u, ok, a.lo, a.hi);
-    double act;
-    {
-#pragma clang fp contract(off)      // mu + sigma eps as the torch expression: product, sum
-        act = sigma * (double)a.eps[i];
-        act = mu + act;
+    int64_t episode_length;
+    double reset0, reset1;
+    __device__ __forceinline__ void step(const double2 *s, double action, double u01, double2 *nxt, double &reward, bool &terminated) const {
+        const LinearStepOut o = linear_env_step(par, s[0].x, s[0].y, action, u01);
+        nxt[0] = make_double2(o.s0, o.s1), reward = o.cost, terminated = false;
     }
-    const double logp = ppo_log_prob(act, mu, sigma, ls);
-    const double2 s = reinterpret_cast<const double2 *>(a.state)[i];
-    // the stored sample is unclipped; the environment sees clip(a, -1, 1) (a NaN sample — log_std not finite — steps with NaN, as in torch)
-    const double applied = act < -1.0 ? -1.0 : (act > 1.0 ? 1.0 : act);
-    const LinearStepOut o = linear_env_step(a.par, s.x, s.y, applied, a.u01[i]);
-    const int64_t n = a.steps[i] + 1;
-    const bool done = n >= a.episode_length;
-    const long k = (long)a.t * a.E + i;
-    reinterpret_cast<double2 *>(a.OBS)[k] = s;
-    reinterpret_cast<double2 *>(a.NEXT)[k] = make_double2(o.s0, o.s1);       // before any reset: the bootstrap value is taken here
-    a.ACT[k] = act, a.LOGP[k] = logp, a.VAL[k] = a.value[i], a.REW[k] = a.reward_scale * o.cost;
-    a.TERM[k] = 0, a.DONE[k] = done ? 1 : 0, a.OK[k] = ok ? 1 : 0;
-    // the environment goes on, or starts again (BatchedLinearSystemEnv.reset)
-    const double2 nxt = done ? make_double2(a.reset0, a.reset1) : make_double2(o.s0, o.s1);
-    reinterpret_cast<double2 *>(a.state)[i] = nxt;
-    reinterpret_cast<double2 *>(a.obs)[i] = nxt;
-    a.steps[i] = done ? 0 : n;
-    a.ended[i] = done ? 1 : 0;
-}
+    __device__ __forceinline__ bool ended(bool, int64_t n) const { return n >= episode_length; }
+    __device__ __forceinline__ void reset(double, double2 *s) const { s[0] = make_double2(reset0, reset1); }
+};
 
 }  // namespace mpcrl

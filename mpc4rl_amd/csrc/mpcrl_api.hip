@@ -61,6 +61,51 @@ int device_of(const void *p) {
     if (dev_of_ < 0) return MPCRL_E_ARG;        \
     ON_DEVICE(dev_of_)
 
+// the 9 doubles of mpcrl_env_cartpole_step's `par` (host memory)
+CartpoleEnvPar cartpole_env_par(const double *par) {
+    CartpoleEnvPar p;
+    p.gravity = par[0], p.masscart = par[1], p.masspole = par[2], p.length = par[3], p.force_mag = par[4], p.tau = par[5];
+    p.x_threshold = par[6], p.theta_threshold = par[7], p.max_episode_steps = (long)par[8];
+    return p;
+}
+
+// the 12 doubles of mpcrl_env_linear_step's `par` (host memory)
+LinearEnvPar linear_env_par(const double *par) {
+    LinearEnvPar p;
+    for (int i = 0; i < 4; ++i) p.A[i] = par[i];
+    p.B[0] = par[4], p.B[1] = par[5], p.lb_noise = par[6], p.ub_noise = par[7];
+    p.low[0] = par[8], p.low[1] = par[9], p.high[0] = par[10], p.high[1] = par[11];
+    return p;
+}
+
+// The workspace of a kernel that hands off to its last workgroup (batch_sum.hpp): the ticket, then one row of `cols` doubles per
+// workgroup, a workgroup taking `rows_per_block` of the `rows` terms.
+int64_t ticket_blocks(int64_t rows, int rows_per_block) { return (rows + rows_per_block - 1) / rows_per_block; }
+int64_t ticket_workspace_bytes(int64_t rows, int rows_per_block, int cols) {
+    return 16 + ticket_blocks(rows, rows_per_block) * cols * (int64_t)sizeof(double);
+}
+template <class Args>
+void set_ticket_workspace(Args &a, void *workspace) {
+    a.ticket = (unsigned int *)workspace, a.partial = (double *)((char *)workspace + 16);
+}
+
+// the launch of mpcrl_ppo_cartpole_collect / mpcrl_ppo_linear_collect, after their argument checks
+template <class Env>
+int launch_ppo_collect(const Env &env, int E, int T, int t, double *state, int64_t *steps, const double *u0, const int32_t *status, const float *eps,
+                       const double *u01, const double *value, const double *log_std, double lo, double hi, double reward_scale, double *OBS,
+                       double *ACT, double *LOGP, double *VAL, double *REW, double *NEXT, uint8_t *TERM, uint8_t *DONE, uint8_t *OK, double *obs,
+                       int32_t *ended, void *stream) {
+    ON_DEVICE_OF(OBS);
+    PpoCollectArgs<Env> a;
+    a.env = env;
+    a.E = E, a.T = T, a.t = t, a.state = state, a.steps = steps, a.u0 = u0, a.status = (const int *)status, a.eps = eps, a.u01 = u01, a.value = value;
+    a.log_std = log_std, a.lo = lo, a.hi = hi, a.reward_scale = reward_scale, a.OBS = OBS, a.ACT = ACT, a.LOGP = LOGP, a.VAL = VAL, a.REW = REW;
+    a.NEXT = NEXT, a.TERM = TERM, a.DONE = DONE, a.OK = OK, a.obs = obs, a.ended = ended;
+    hipLaunchKernelGGL(ppo_collect_kernel<Env>, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 template <class T>
 int dev_alloc(T **p, size_t n, int64_t &bytes) {
     hipError_t e = hipMalloc((void **)p, n * sizeof(T));
@@ -619,9 +664,7 @@ int mpcrl_env_cartpole_step(const double *par, int B, double *state, int64_t *st
     if (!par || B < 0 || !state || !steps || !action || !reward || !terminated || !truncated) return MPCRL_E_ARG;
     if (B == 0) return 0;
     ON_DEVICE_OF(state);
-    CartpoleEnvPar p;
-    p.gravity = par[0], p.masscart = par[1], p.masspole = par[2], p.length = par[3], p.force_mag = par[4], p.tau = par[5];
-    p.x_threshold = par[6], p.theta_threshold = par[7], p.max_episode_steps = (long)par[8];
+    const CartpoleEnvPar p = cartpole_env_par(par);
     if (obs_f32)
         hipLaunchKernelGGL(env_cartpole_step_kernel<float>, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, p, B, state, steps, action,
                            (float *)obs, reward, terminated, truncated);
@@ -665,11 +708,11 @@ int mpcrl_td3_cartpole_collect(const double *par, int E, double *state, int64_t 
         return MPCRL_E_ARG;
     ON_DEVICE_OF(state);
     Td3CollectArgs a;
-    a.par.gravity = par[0], a.par.masscart = par[1], a.par.masspole = par[2], a.par.length = par[3], a.par.force_mag = par[4], a.par.tau = par[5];
-    a.par.x_threshold = par[6], a.par.theta_threshold = par[7], a.par.max_episode_steps = (long)par[8];
+    a.par = cartpole_env_par(par);
     a.E = E, a.state = state, a.steps = steps, a.u0 = u0, a.status = (const int *)status, a.eps = eps, a.u01 = u01, a.lo = lo, a.hi = hi, a.scale = scale;
     a.sigma = (float)sigma, a.obs = obs, a.ended = ended, a.table = table, a.cap = cap, a.reward_scale = reward_scale, a.pos = pos, a.iter_ok = iter_ok;
-    a.iter_rows = iter_rows, a.stats = stats, a.ticket = (unsigned int *)workspace, a.partial = (double *)((char *)workspace + 16);
+    a.iter_rows = iter_rows, a.stats = stats;
+    set_ticket_workspace(a, workspace);
     hipLaunchKernelGGL(td3_cartpole_collect_kernel, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
     HIP_OK(hipGetLastError());
     return 0;
@@ -693,8 +736,7 @@ int mpcrl_qlearning_cartpole_collect(const double *par, int E, int T, double *st
         return MPCRL_E_ARG;
     ON_DEVICE_OF(state);
     QlCollectArgs a;
-    a.par.gravity = par[0], a.par.masscart = par[1], a.par.masspole = par[2], a.par.length = par[3], a.par.force_mag = par[4], a.par.tau = par[5];
-    a.par.x_threshold = par[6], a.par.theta_threshold = par[7], a.par.max_episode_steps = (long)par[8];
+    a.par = cartpole_env_par(par);
     a.E = E, a.T = T, a.state = state, a.steps = steps, a.u0 = u0, a.status = (const int *)status, a.eps = eps, a.lo = lo, a.hi = hi;
     a.sigma = (float)sigma, a.obs = obs, a.alive = alive, a.row = row, a.cold = cold, a.S = S, a.A = A, a.C = C, a.live = live;
     hipLaunchKernelGGL(qlearning_cartpole_collect_kernel, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
@@ -704,8 +746,7 @@ int mpcrl_qlearning_cartpole_collect(const double *par, int E, int T, double *st
 
 int64_t mpcrl_qlearning_td_workspace_bytes(int T, int E, int n_p) {
     if (T < 2 || E < 1 || n_p < 1) return MPCRL_E_ARG;
-    const int64_t M = (int64_t)(T - 2) * E;
-    return 16 + ((M + TD_ROWS - 1) / TD_ROWS) * (n_p + 2) * (int64_t)sizeof(double);
+    return ticket_workspace_bytes((int64_t)(T - 2) * E, TD_ROWS, n_p + 2);
 }
 
 int mpcrl_qlearning_td_grad(const double *Q, const double *V, const double *dQ_dp, const int32_t *status_q, const int32_t *status_v, const double *cost,
@@ -719,12 +760,13 @@ int mpcrl_qlearning_td_grad(const double *Q, const double *V, const double *dQ_d
         HIP_OK(hipMemsetAsync(msg, 0, (size_t)(n_p + 2) * sizeof(double), (hipStream_t)stream));
         return 0;
     }
-    if ((M + TD_ROWS - 1) / TD_ROWS > 0x7fffffff) return MPCRL_E_ARG;
+    if (ticket_blocks(M, TD_ROWS) > 0x7fffffff) return MPCRL_E_ARG;
     QlTdArgs a;
     a.Q = Q, a.V = V, a.dQ = dQ_dp, a.sq = (const int *)status_q, a.sv = (const int *)status_v, a.cost = cost, a.live = live;
     a.T = T, a.E = E, a.n_p = n_p, a.gamma = gamma, a.lr = lr, a.td = td, a.valid = valid;
-    a.ticket = (unsigned int *)workspace, a.partial = (double *)((char *)workspace + 16), a.msg = msg;
-    hipLaunchKernelGGL(qlearning_td_grad_kernel, dim3((unsigned)((M + TD_ROWS - 1) / TD_ROWS)), dim3(TD_ROWS), 0, (hipStream_t)stream, a);
+    a.msg = msg;
+    set_ticket_workspace(a, workspace);
+    hipLaunchKernelGGL(qlearning_td_grad_kernel, dim3((unsigned)ticket_blocks(M, TD_ROWS)), dim3(TD_ROWS), 0, (hipStream_t)stream, a);
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -744,16 +786,10 @@ int mpcrl_ppo_cartpole_collect(const double *par, int E, int T, int t, double *s
     if (!par || E < 1 || T < 1 || t < 0 || t >= T || !state || !steps || !u0 || !status || !eps || !u01 || !value || !log_std || !(hi > lo) || !OBS ||
         !ACT || !LOGP || !VAL || !REW || !NEXT || !TERM || !DONE || !OK || !obs || !ended)
         return MPCRL_E_ARG;
-    ON_DEVICE_OF(OBS);
-    PpoCollectArgs a;
-    a.par.gravity = par[0], a.par.masscart = par[1], a.par.masspole = par[2], a.par.length = par[3], a.par.force_mag = par[4], a.par.tau = par[5];
-    a.par.x_threshold = par[6], a.par.theta_threshold = par[7], a.par.max_episode_steps = (long)par[8];
-    a.E = E, a.T = T, a.t = t, a.state = state, a.steps = steps, a.u0 = u0, a.status = (const int *)status, a.eps = eps, a.u01 = u01, a.value = value;
-    a.log_std = log_std, a.lo = lo, a.hi = hi, a.reward_scale = reward_scale, a.OBS = OBS, a.ACT = ACT, a.LOGP = LOGP, a.VAL = VAL, a.REW = REW;
-    a.NEXT = NEXT, a.TERM = TERM, a.DONE = DONE, a.OK = OK, a.obs = obs, a.ended = ended;
-    hipLaunchKernelGGL(ppo_cartpole_collect_kernel, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
-    HIP_OK(hipGetLastError());
-    return 0;
+    PpoCartpoleEnv env;
+    env.par = cartpole_env_par(par);
+    return launch_ppo_collect(env, E, T, t, state, steps, u0, status, eps, u01, value, log_std, lo, hi, reward_scale, OBS, ACT, LOGP, VAL, REW, NEXT,
+                              TERM, DONE, OK, obs, ended, stream);
 }
 
 int mpcrl_ppo_gae(const double *REW, const double *VAL, const double *VNEXT, const uint8_t *TERM, const uint8_t *DONE, int T, int E, double gamma,
@@ -768,7 +804,7 @@ int mpcrl_ppo_gae(const double *REW, const double *VAL, const double *VNEXT, con
 
 int64_t mpcrl_ppo_surrogate_workspace_bytes(int M, int n_p) {
     if (M < 1 || n_p < 1) return MPCRL_E_ARG;
-    return 16 + (int64_t)((M + PPO_ROWS - 1) / PPO_ROWS) * (n_p + PPO_NS) * (int64_t)sizeof(double);
+    return ticket_workspace_bytes(M, PPO_ROWS, n_p + PPO_NS);
 }
 
 int mpcrl_ppo_surrogate_grad(const int64_t *idx, int M, int64_t n_rows, const double *ACT, const double *LOGP, const double *ADV, const uint8_t *OK,
@@ -781,9 +817,10 @@ int mpcrl_ppo_surrogate_grad(const int64_t *idx, int M, int64_t n_rows, const do
     PpoSurrogateArgs a;
     a.idx = idx, a.M = M, a.n_p = n_p, a.n_rows = n_rows, a.ACT = ACT, a.LOGP = LOGP, a.ADV = ADV, a.OK = OK, a.u0_new = u0_new;
     a.status_new = (const int *)status_new, a.dpi = dpi_dp, a.log_std = log_std, a.lo = lo, a.hi = hi, a.clip = clip_range, a.ent_coef = ent_coef, a.lr = lr;
-    a.normalize = normalize_adv, a.ticket = (unsigned int *)workspace, a.partial = (double *)((char *)workspace + 16), a.msg = msg;
+    a.normalize = normalize_adv, a.msg = msg;
+    set_ticket_workspace(a, workspace);
     hipLaunchKernelGGL(ppo_adv_stats_kernel, dim3(1), dim3(PPO_STAT_THREADS), 0, (hipStream_t)stream, a);
-    hipLaunchKernelGGL(ppo_surrogate_kernel, dim3((M + PPO_ROWS - 1) / PPO_ROWS), dim3(PPO_ROWS), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(ppo_surrogate_kernel, dim3((unsigned)ticket_blocks(M, PPO_ROWS)), dim3(PPO_ROWS), 0, (hipStream_t)stream, a);
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -827,7 +864,7 @@ int mpcrl_value_mse_grad(const double *OBS, const double *RET, const int64_t *id
 
 int64_t mpcrl_dpg_workspace_bytes(int B, int n_p) {
     if (B < 1 || n_p < 1) return MPCRL_E_ARG;
-    return 16 + (int64_t)((B + DPG_ROWS - 1) / DPG_ROWS) * (n_p + 1) * (int64_t)sizeof(double);
+    return ticket_workspace_bytes(B, DPG_ROWS, n_p + 1);
 }
 
 int mpcrl_dpg_grad(const float *dq_da, const uint8_t *ok, const double *dpi_dp, int B, int nu, int n_p, const double *lo, const double *hi, int scale,
@@ -836,8 +873,9 @@ int mpcrl_dpg_grad(const float *dq_da, const uint8_t *ok, const double *dpi_dp, 
     ON_DEVICE_OF(out);
     DpgArgs a;
     a.dq_da = dq_da, a.ok = ok, a.dpi_dp = dpi_dp, a.B = B, a.nu = nu, a.n_p = n_p, a.scale = scale, a.lo = lo, a.hi = hi;
-    a.ticket = (unsigned int *)workspace, a.partial = (double *)((char *)workspace + 16), a.out = out;
-    hipLaunchKernelGGL(dpg_grad_kernel, dim3((B + DPG_ROWS - 1) / DPG_ROWS), dim3(128), 0, (hipStream_t)stream, a);
+    a.out = out;
+    set_ticket_workspace(a, workspace);
+    hipLaunchKernelGGL(dpg_grad_kernel, dim3((unsigned)ticket_blocks(B, DPG_ROWS)), dim3(128), 0, (hipStream_t)stream, a);
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -881,15 +919,6 @@ int mpcrl_critic_dq_da(const float *obs, int obs_stride, int B, int nx, int nu, 
     return 0;
 }
 
-// the 12 doubles of mpcrl_env_linear_step's `par` (host memory)
-static LinearEnvPar linear_env_par(const double *par) {
-    LinearEnvPar p;
-    for (int i = 0; i < 4; ++i) p.A[i] = par[i];
-    p.B[0] = par[4], p.B[1] = par[5], p.lb_noise = par[6], p.ub_noise = par[7];
-    p.low[0] = par[8], p.low[1] = par[9], p.high[0] = par[10], p.high[1] = par[11];
-    return p;
-}
-
 int mpcrl_env_linear_step(const double *par, int B, double *state, const double *action, const double *u01, void *obs, int obs_f32,
                           double *cost, void *stream) {
     if (!par || B < 0 || !state || !action || !u01 || !cost) return MPCRL_E_ARG;
@@ -928,16 +957,10 @@ int mpcrl_ppo_linear_collect(const double *par, int E, int T, int t, double *sta
         !value || !log_std || !(hi > lo) || !OBS || !ACT || !LOGP || !VAL || !REW || !NEXT || !TERM || !DONE || !OK || !obs || !ended)
         return MPCRL_E_ARG;
     if (E == 0) return 0;
-    ON_DEVICE_OF(OBS);
-    PpoLinearCollectArgs a;
-    a.par = linear_env_par(par);
-    a.E = E, a.T = T, a.t = t, a.state = state, a.steps = steps, a.u0 = u0, a.status = (const int *)status, a.eps = eps, a.u01 = u01, a.value = value;
-    a.log_std = log_std, a.lo = lo, a.hi = hi, a.reward_scale = reward_scale, a.episode_length = episode_length;
-    a.reset0 = reset_state[0], a.reset1 = reset_state[1];
-    a.OBS = OBS, a.ACT = ACT, a.LOGP = LOGP, a.VAL = VAL, a.REW = REW, a.NEXT = NEXT, a.TERM = TERM, a.DONE = DONE, a.OK = OK, a.obs = obs, a.ended = ended;
-    hipLaunchKernelGGL(ppo_linear_collect_kernel, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
-    HIP_OK(hipGetLastError());
-    return 0;
+    PpoLinearEnv env;
+    env.par = linear_env_par(par), env.episode_length = episode_length, env.reset0 = reset_state[0], env.reset1 = reset_state[1];
+    return launch_ppo_collect(env, E, T, t, state, steps, u0, status, eps, u01, value, log_std, lo, hi, reward_scale, OBS, ACT, LOGP, VAL, REW, NEXT,
+                              TERM, DONE, OK, obs, ended, stream);
 }
 
 int mpcrl_env_cartpole_reset(int B, double *state, int64_t *steps, const uint8_t *mask, const double *u01, void *obs, int obs_f32,

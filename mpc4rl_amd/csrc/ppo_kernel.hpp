@@ -1,7 +1,7 @@
 // Batched PPO with the MPC as Gaussian actor, cartpole environment, nu = 1 (mpc4rl_amd/ppo.py): what the reference's
 // MPCActorCriticPolicy (rlmpc/ppo/policies.py:26-134) leaves as NotImplementedError, around the solves, on the device.  The policy is
 // a ~ N(mu, sigma^2), mu = scale_action(u0*) of the solve, sigma = exp(log_std) with one learnable, state-independent log_std.
-//   ppo_cartpole_collect_kernel   one roll-out step after the policy's solve, one lane per environment: the sample and its log
+//   ppo_collect_kernel<Env>       one roll-out step after the policy's solve, one lane per environment: the sample and its log
 //                                 probability, the environment step, row t of the roll-out tables, the reset of the environments that
 //                                 ended, the observation and the cold mask of the next solve
 //   ppo_gae_kernel                generalised advantage estimates, one lane per environment, serial over t = T-1 ... 0
@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "env_kernel.hpp"
-#include "replay_kernel.hpp"   // nan_to_num_d
+#include "batch_sum.hpp"
 
 namespace mpcrl {
 
@@ -36,25 +36,44 @@ __device__ __forceinline__ double ppo_log_prob(double a, double mu, double sigma
     return -(d * d) / (2.0 * (sigma * sigma)) - log_std - 0.9189385332046727;
 }
 
-struct PpoCollectArgs {
+// What the roll-out step needs of a plant: PAIRS (the state as double2 pairs), the step from state s under the applied action (u01: the
+// step's uniform draw), whether the episode ended after n steps, and the state the next episode starts from.
+struct PpoCartpoleEnv {
+    static constexpr int PAIRS = 2;
     CartpoleEnvPar par;
+    __device__ __forceinline__ void step(const double2 *s, double action, double, double2 *nxt, double &reward, bool &terminated) const {
+        const CartpoleStepOut o = cartpole_env_step(par, s[0].x, s[0].y, s[1].x, s[1].y, action);
+        nxt[0] = make_double2(o.nx, o.nxd), nxt[1] = make_double2(o.nth, o.nthd), reward = o.reward, terminated = o.terminated;
+    }
+    __device__ __forceinline__ bool ended(bool terminated, int64_t n) const { return terminated || n >= par.max_episode_steps; }
+    __device__ __forceinline__ void reset(double u01, double2 *s) const {      // (mpcrl_env_cartpole_reset)
+        const CartpoleState r = cartpole_env_reset(u01);
+        s[0] = r.s01, s[1] = r.s23;
+    }
+};
+
+template <class Env>
+struct PpoCollectArgs {
+    Env env;
     int E, T, t;
-    double *state;            // [E][4] the environments' states
-    int64_t *steps;           // [E]
+    double *state;            // [E][nx] the environments' states
+    int64_t *steps;           // [E] steps since the last reset
     const double *u0;         // [E] the policy's solve: control
     const int *status;        // [E]
     const float *eps;         // [E] standard-normal draws
-    const double *u01;        // [E] uniform draws (resets)
+    const double *u01;        // [E] uniform draws (the step's noise, the reset)
     const double *value;      // [E] the critic at the observation just solved
     const double *log_std;    // [1]
     double lo, hi, reward_scale;
-    double *OBS, *ACT, *LOGP, *VAL, *REW, *NEXT;      // [T][E] ([..][4] for OBS, NEXT)
+    double *OBS, *ACT, *LOGP, *VAL, *REW, *NEXT;      // [T][E] ([..][nx] for OBS, NEXT)
     uint8_t *TERM, *DONE, *OK;                        // [T][E]
-    double *obs;              // [E][4] out: the next solve's x0 (after resets)
+    double *obs;              // [E][nx] out: the next solve's x0 (after resets)
     int32_t *ended;           // [E] out: 1 = the episode ended (the next solve starts that instance cold)
 };
 
-__global__ void __launch_bounds__(256) ppo_cartpole_collect_kernel(const PpoCollectArgs a) {
+template <class Env>
+__global__ void __launch_bounds__(256) ppo_collect_kernel(const PpoCollectArgs<Env> a) {
+    constexpr int W = Env::PAIRS;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.E) return;
     const double ls = a.log_std[0], sigma = exp(ls);
@@ -68,28 +87,33 @@ __global__ void __launch_bounds__(256) ppo_cartpole_collect_kernel(const PpoColl
         act = mu + act;
     }
     const double logp = ppo_log_prob(act, mu, sigma, ls);
-    const double2 s01 = reinterpret_cast<const double2 *>(a.state)[2 * i], s23 = reinterpret_cast<const double2 *>(a.state)[2 * i + 1];
+    double2 s[W], nxt[W];
+#pragma unroll
+    for (int q = 0; q < W; ++q) s[q] = reinterpret_cast<const double2 *>(a.state)[W * i + q];
     // the stored sample is unclipped; the environment sees clip(a, -1, 1) (a NaN sample — log_std not finite — steps with NaN, as in torch)
     const double applied = act < -1.0 ? -1.0 : (act > 1.0 ? 1.0 : act);
-    const CartpoleStepOut o = cartpole_env_step(a.par, s01.x, s01.y, s23.x, s23.y, applied);
+    const double u01 = a.u01[i];
+    double reward;
+    bool terminated;
+    a.env.step(s, applied, u01, nxt, reward, terminated);
     const int64_t n = a.steps[i] + 1;
-    const bool done = o.terminated || n >= a.par.max_episode_steps;
+    const bool done = a.env.ended(terminated, n);
     const long k = (long)a.t * a.E + i;
-    reinterpret_cast<double2 *>(a.OBS)[2 * k] = s01;
-    reinterpret_cast<double2 *>(a.OBS)[2 * k + 1] = s23;
-    reinterpret_cast<double2 *>(a.NEXT)[2 * k] = make_double2(o.nx, o.nxd);       // before any reset: the bootstrap value is taken here
-    reinterpret_cast<double2 *>(a.NEXT)[2 * k + 1] = make_double2(o.nth, o.nthd);
-    a.ACT[k] = act, a.LOGP[k] = logp, a.VAL[k] = a.value[i], a.REW[k] = a.reward_scale * o.reward;
-    a.TERM[k] = o.terminated ? 1 : 0, a.DONE[k] = done ? 1 : 0, a.OK[k] = ok ? 1 : 0;
-    // the environment goes on, or starts again (mpcrl_env_cartpole_reset)
-    double x = o.nx, xd = o.nxd, th = o.nth, thd = o.nthd;
-    int64_t cnt = n;
-    if (done) x = 0.0, xd = 0.0, th = (0.9 + 0.2 * a.u01[i]) * 3.141592653589793, thd = 0.0, cnt = 0;
-    reinterpret_cast<double2 *>(a.state)[2 * i] = make_double2(x, xd);
-    reinterpret_cast<double2 *>(a.state)[2 * i + 1] = make_double2(th, thd);
-    a.steps[i] = cnt;
-    reinterpret_cast<double2 *>(a.obs)[2 * i] = make_double2(x, xd);
-    reinterpret_cast<double2 *>(a.obs)[2 * i + 1] = make_double2(th, thd);
+#pragma unroll
+    for (int q = 0; q < W; ++q) {
+        reinterpret_cast<double2 *>(a.OBS)[W * k + q] = s[q];
+        reinterpret_cast<double2 *>(a.NEXT)[W * k + q] = nxt[q];       // before any reset: the bootstrap value is taken here
+    }
+    a.ACT[k] = act, a.LOGP[k] = logp, a.VAL[k] = a.value[i], a.REW[k] = a.reward_scale * reward;
+    a.TERM[k] = terminated ? 1 : 0, a.DONE[k] = done ? 1 : 0, a.OK[k] = ok ? 1 : 0;
+    // the environment goes on, or starts again
+    if (done) a.env.reset(u01, nxt);
+#pragma unroll
+    for (int q = 0; q < W; ++q) {
+        reinterpret_cast<double2 *>(a.state)[W * i + q] = nxt[q];
+        reinterpret_cast<double2 *>(a.obs)[W * i + q] = nxt[q];
+    }
+    a.steps[i] = done ? 0 : n;
     a.ended[i] = done ? 1 : 0;
 }
 
@@ -182,13 +206,10 @@ __global__ void __launch_bounds__(PPO_STAT_THREADS) ppo_adv_stats_kernel(const P
     if (threadIdx.x == 0) a.msg[a.n_p + 1] = n, a.msg[a.n_p + 6] = s, a.msg[a.n_p + 7] = q;
 }
 
-// Every workgroup sums PPO_ROWS rows into its partial; the last one to finish (a ticket) adds the partials in four slices of the
-// blocks, added in order (the scheme of qlearning_td_grad_kernel): the same inputs give the same bits.
-__global__ void __launch_bounds__(128) ppo_surrogate_kernel(const PpoSurrogateArgs a) {
+// The sum is the fixed-order batch sum of batch_sum.hpp over blocks of PPO_ROWS rows: the same inputs give the same bits.
+__global__ void __launch_bounds__(PPO_ROWS) ppo_surrogate_kernel(const PpoSurrogateArgs a) {
     __shared__ double w[PPO_ROWS];
     __shared__ double sc[PPO_NS][PPO_ROWS];
-    __shared__ bool last;
-    __shared__ double fin[4][PPO_PMAX];
     const long b0 = (long)blockIdx.x * PPO_ROWS;
     const int P2 = a.n_p + PPO_NS;
     const double n_valid = a.msg[a.n_p + 1];
@@ -228,50 +249,17 @@ __global__ void __launch_bounds__(128) ppo_surrogate_kernel(const PpoSurrogateAr
         a.partial[(long)blockIdx.x * P2 + a.n_p + threadIdx.x] = s;
     }
     const int nr = (int)(a.M - b0 < PPO_ROWS ? a.M - b0 : PPO_ROWS);
-    const double *base = a.dpi + b0 * a.n_p;
-    for (int p = threadIdx.x; p < a.n_p; p += 128) {
-        double acc = 0.0;
-        int k = 0;
-        for (; k + 8 <= nr; k += 8) {
-            double v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = base[(long)(k + q) * a.n_p + p];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) acc = fma(w[k + q], nan_to_num_d(v[q]), acc);
-        }
-        for (; k < nr; ++k) acc = fma(w[k], nan_to_num_d(base[(long)k * a.n_p + p]), acc);
-        a.partial[(long)blockIdx.x * P2 + p] = acc;
-    }
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(a.ticket, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
-    const int nb = gridDim.x, per = (nb + 3) / 4;
-    for (int p0 = 0; p0 < P2; p0 += PPO_PMAX) {
-        const int np = P2 - p0 < PPO_PMAX ? P2 - p0 : PPO_PMAX;
-        for (int e = threadIdx.x; e < 4 * np; e += 128) {
-            const int sl = e / np, p = p0 + e - sl * np;
-            const int lo = sl * per, hi = lo + per < nb ? lo + per : nb;
-            double acc = 0.0;
-            for (int k = lo; k < hi; ++k) acc += a.partial[(long)k * P2 + p];
-            fin[sl][e - sl * np] = acc;
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < np; e += 128) {
-            const int p = p0 + e;
-            double s = ((fin[0][e] + fin[1][e]) + fin[2][e]) + fin[3][e];
-            // the step of theta and of log_std: -lr x the sums (the entropy bonus adds -ent_coef to every valid row's g_ls)
-            if (p < a.n_p) s = -a.lr * s;
-            if (p == a.n_p) s = -a.lr * (s - a.ent_coef * n_valid);
-            a.msg[p] = s;
-        }
-        __syncthreads();
-    }
+    block_weighted_colsum<PPO_ROWS>(w, a.dpi + b0 * a.n_p, nr, a.n_p, a.partial + (long)blockIdx.x * P2);
+    if (!last_workgroup(a.ticket)) return;
+    const int nb = gridDim.x;
+    sliced_final_sum<PPO_PMAX, PPO_ROWS>(a.partial, nb, P2, [&](int p, double s) {
+        // the step of theta and of log_std: -lr x the sums (the entropy bonus adds -ent_coef to every valid row's g_ls)
+        if (p < a.n_p) s = -a.lr * s;
+        if (p == a.n_p) s = -a.lr * (s - a.ent_coef * n_valid);
+        a.msg[p] = s;
+    });
     // the workspace is left all zero
-    for (long e = threadIdx.x; e < (long)nb * P2; e += 128) a.partial[e] = 0.0;
-    if (threadIdx.x == 0) *a.ticket = 0u;
+    for (long e = threadIdx.x; e < (long)nb * P2; e += PPO_ROWS) a.partial[e] = 0.0;
 }
 
 // After the collective: log_std += msg[n_p] / max(1, msg[n_p + 1]) — the masked mean mpcrl_qlearning_apply takes for theta

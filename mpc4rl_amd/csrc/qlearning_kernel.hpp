@@ -12,7 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "env_kernel.hpp"
-#include "replay_kernel.hpp"   // nan_to_num_d
+#include "batch_sum.hpp"
 
 namespace mpcrl {
 
@@ -84,8 +84,7 @@ __global__ void __launch_bounds__(256) qlearning_cartpole_collect_kernel(const Q
 // and td[:-1] per environment);
 //     td_j = (cost_j + gamma V_{j+E}) - Q_j;  w_j = valid_j ? lr td_j : 0  (selected: Q / V of a failed solve may be NaN)
 //     msg = [sum_j w_j dQ/dp_j (n_p), sum_j w_j, sum_j valid_j]   (dQ/dp read as nan_to_num does; 0 x finite = 0)
-// Every workgroup sums TD_ROWS terms into its partial; the last one to finish (a ticket) adds the partials in four slices of the blocks,
-// added in order: the same inputs give the same bits.
+// The sum is the fixed-order batch sum of batch_sum.hpp over blocks of TD_ROWS terms: the same inputs give the same bits.
 constexpr int TD_ROWS = 128, TD_PMAX = 256;     // (TD_ROWS = the block size: one term per lane in the first phase)
 
 struct QlTdArgs {
@@ -106,8 +105,6 @@ struct QlTdArgs {
 __global__ void __launch_bounds__(128) qlearning_td_grad_kernel(const QlTdArgs a) {
     __shared__ double w[TD_ROWS], okr[TD_ROWS];
     __shared__ double wsum, cnt;
-    __shared__ bool last;
-    __shared__ double fin[4][TD_PMAX];
     const long M = (long)(a.T - 2) * a.E;
     const long b0 = (long)blockIdx.x * TD_ROWS;
     const int P2 = a.n_p + 2;
@@ -139,50 +136,11 @@ __global__ void __launch_bounds__(128) qlearning_td_grad_kernel(const QlTdArgs a
     }
     __syncthreads();
     const int nr = (int)(M - b0 < TD_ROWS ? M - b0 : TD_ROWS);
-    const double *base = a.dQ + b0 * a.n_p;
-    for (int p = threadIdx.x; p < a.n_p; p += 128) {
-        double acc = 0.0;
-        int k = 0;
-        for (; k + 8 <= nr; k += 8) {
-            double v[8];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = base[(long)(k + q) * a.n_p + p];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) acc = fma(w[k + q], nan_to_num_d(v[q]), acc);
-        }
-        for (; k < nr; ++k) acc = fma(w[k], nan_to_num_d(base[(long)k * a.n_p + p]), acc);
-        a.partial[(long)blockIdx.x * P2 + p] = acc;
-    }
-    if (threadIdx.x == 0) a.partial[(long)blockIdx.x * P2 + a.n_p] = wsum, a.partial[(long)blockIdx.x * P2 + a.n_p + 1] = cnt;
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(a.ticket, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
-    const int nb = gridDim.x, per = (nb + 3) / 4;
-    for (int p0 = 0; p0 < P2; p0 += TD_PMAX) {
-        const int np = P2 - p0 < TD_PMAX ? P2 - p0 : TD_PMAX;
-        for (int e = threadIdx.x; e < 4 * np; e += 128) {
-            const int sl = e / np, p = p0 + e - sl * np;
-            const int lo = sl * per, hi = lo + per < nb ? lo + per : nb;
-            double acc = 0.0;
-            int k = lo;
-            for (; k + 8 <= hi; k += 8) {
-                double v[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) v[q] = a.partial[(long)(k + q) * P2 + p];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) acc += v[q];
-            }
-            for (; k < hi; ++k) acc += a.partial[(long)k * P2 + p];
-            fin[sl][e - sl * np] = acc;
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < np; e += 128) a.msg[p0 + e] = ((fin[0][e] + fin[1][e]) + fin[2][e]) + fin[3][e];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *a.ticket = 0u;
+    double *row = a.partial + (long)blockIdx.x * P2;
+    block_weighted_colsum<TD_ROWS>(w, a.dQ + b0 * a.n_p, nr, a.n_p, row);
+    if (threadIdx.x == 0) row[a.n_p] = wsum, row[a.n_p + 1] = cnt;
+    if (!last_workgroup(a.ticket)) return;
+    sliced_final_sum<TD_PMAX, TD_ROWS>(a.partial, gridDim.x, P2, [&](int p, double s) { a.msg[p] = s; });
 }
 
 // After the collective: step = mask != 0 ? msg / max(1, count) : 0 (the mean of mean_update; a masked entry is selected out, never

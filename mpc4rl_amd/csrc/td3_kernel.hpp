@@ -4,11 +4,12 @@
 // environment step (env_cartpole_step_kernel), the replay row, the flag of the stored iterate, the statistics, the reset of the
 // environments that ended (env_cartpole_reset_kernel), the observation and the cold mask of the next solve, the replay position.
 // One lane per environment; the arithmetic is that of the kernels it stands for (shared device functions: the same bits).  The write
-// position lives on the device: every workgroup reads it when it starts, the LAST one to finish (a ticket) advances it and adds the
-// workgroups' statistics in block order (no floating-point atomics).
+// position lives on the device: every workgroup reads it when it starts, the LAST one to finish (last_workgroup of batch_sum.hpp) advances
+// it and adds the workgroups' statistics in block order (no floating-point atomics).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "batch_sum.hpp"
 #include "env_kernel.hpp"
 
 namespace mpcrl {
@@ -40,7 +41,6 @@ struct Td3CollectArgs {
 
 __global__ void __launch_bounds__(256) td3_cartpole_collect_kernel(const Td3CollectArgs a) {
     __shared__ double red[3][256];
-    __shared__ bool last;
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int64_t pos = a.pos[0], npos = (pos + 1) % a.cap;
     double s_rew = 0.0, s_conv = 0.0, s_done = 0.0;
@@ -63,14 +63,12 @@ __global__ void __launch_bounds__(256) td3_cartpole_collect_kernel(const Td3Coll
         if (a.iter_rows) a.iter_rows[i] = pos * a.E + i;
         s_rew = o.reward, s_conv = st == 0 ? 1.0 : 0.0, s_done = done ? 1.0 : 0.0;
         // the environment goes on, or starts again
-        double x = o.nx, xd = o.nxd, th = o.nth, thd = o.nthd;
-        int64_t cnt = n;
-        if (done) x = 0.0, xd = 0.0, th = (0.9 + 0.2 * a.u01[i]) * 3.141592653589793, thd = 0.0, cnt = 0;
-        reinterpret_cast<double2 *>(a.state)[2 * i] = make_double2(x, xd);
-        reinterpret_cast<double2 *>(a.state)[2 * i + 1] = make_double2(th, thd);
-        a.steps[i] = cnt;
-        reinterpret_cast<double2 *>(a.obs)[2 * i] = make_double2(x, xd);
-        reinterpret_cast<double2 *>(a.obs)[2 * i + 1] = make_double2(th, thd);
+        const CartpoleState nxt = done ? cartpole_env_reset(a.u01[i]) : CartpoleState{make_double2(o.nx, o.nxd), make_double2(o.nth, o.nthd)};
+        reinterpret_cast<double2 *>(a.state)[2 * i] = nxt.s01;
+        reinterpret_cast<double2 *>(a.state)[2 * i + 1] = nxt.s23;
+        a.steps[i] = done ? 0 : n;
+        reinterpret_cast<double2 *>(a.obs)[2 * i] = nxt.s01;
+        reinterpret_cast<double2 *>(a.obs)[2 * i + 1] = nxt.s23;
         a.ended[i] = done ? 1 : 0;
     }
     red[0][threadIdx.x] = s_rew, red[1][threadIdx.x] = s_conv, red[2][threadIdx.x] = s_done;
@@ -81,18 +79,13 @@ __global__ void __launch_bounds__(256) td3_cartpole_collect_kernel(const Td3Coll
         __syncthreads();
     }
     if (threadIdx.x < 3) a.partial[blockIdx.x * 3 + threadIdx.x] = red[threadIdx.x][0];
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) last = atomicAdd(a.ticket, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
+    if (!last_workgroup(a.ticket)) return;
     if (threadIdx.x < 3) {
         double acc = 0.0;
         for (int k = 0; k < (int)gridDim.x; ++k) acc += __builtin_nontemporal_load(&a.partial[k * 3 + threadIdx.x]);
         a.stats[threadIdx.x] += acc;
     }
-    if (threadIdx.x == 0) a.pos[0] = npos, *a.ticket = 0u;
+    if (threadIdx.x == 0) a.pos[0] = npos;
 }
 
 // After the collective, every policy_delay-th update (BatchedTD3._update_post): the policy step from the all-reduced message

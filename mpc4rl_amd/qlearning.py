@@ -9,15 +9,20 @@ The samples of an episode are independent given p, and so are parallel environme
 ``MPCBatch.solve`` per time step over E environments and the learning sweep is TWO batched solves over all E*T samples.
 With several ranks every rank learns from its own environments and the parameter step is all-reduced
 (mpc4rl_amd.distributed), so all ranks hold identical parameters.
+
+``BatchedQLearning`` is that loop in torch for any model.  ``DeviceQLearning`` is the core of its device forms (``CartpoleQLearning``,
+``LinearQLearning``): everything of an episode but the plant's own roll-out kernel and tables.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 from typing import Callable, Optional
 
 import torch
 
-from .batch import MPCBatch
+from . import _lib
+from .batch import MPCBatch, _ptr
 from .distributed import mean_update
 
 
@@ -84,3 +89,178 @@ class BatchedQLearning:
         for m in (self.rollout_mpc, self.sample_mpc):
             m.set_theta(self.theta)                                   # mpc.set_parameter (204-205)
         return EpisodeStats(float(C.sum().item()) / self.E, float(torch.where(okb, td, torch.zeros_like(td)).sum().item() / max(1.0, float(valid.sum().item()))), step, float(valid.mean().item()))
+
+
+class DeviceQLearning:
+    """The plant-independent part of the device Q-learners.  Per time step the roll-out is ONE batched solve over the E environments
+    (warm, an episode's first solve cold per instance through the cold mask) and ONE launch of the plant's collect kernel; the learning
+    sweep is ONE batched Q solve over all E (T - 1) samples (u0 fixed to the recorded actions, dQ/dp, cold), ONE V solve started from
+    the Q solve's primal iterate and ONE launch of mpcrl_qlearning_td_grad (TD errors, validity, and the message [sum lr td dQ/dp,
+    sum lr td, count] of distributed.mean_update).  With several ranks only that message is all-reduced; then mpcrl_qlearning_apply
+    takes the mean and steps theta.
+
+    A plant's class sets ``NX`` and ``_COLLECT``, checks its OCP and environment, allocates ``live`` [T, E] (and what else its collect
+    kernel needs) after this constructor, and defines ``_collect(r)`` (the collect launch after the roll-out solve r; returns its
+    status), ``_stats()`` and, where the environment carries more than its state from step to step, ``_env_carried()``."""
+
+    NX: int = 0             # the state's width
+    _COLLECT: str = ""      # the library's collect entry point (for error messages)
+
+    def __init__(self, ocp, env, episode_length: int, lr: float, gamma: float, noise_scale: float, seed: int, device, group,
+                 mpc_gamma: Optional[float] = None):
+        name = type(self).__name__
+        if isinstance(episode_length, bool) or not isinstance(episode_length, int) or episode_length < 2:
+            raise ValueError("episode_length must be an int >= 2 (a TD term needs two samples)")
+        if not math.isfinite(lr):
+            raise ValueError("lr must be finite")
+        if not (0.0 < gamma <= 1.0):
+            raise ValueError("gamma must lie in (0, 1]")
+        if not (math.isfinite(noise_scale) and noise_scale >= 0.0):
+            raise ValueError("noise_scale must be finite and >= 0")
+        dev = env.device if device is None else torch.device(device)
+        if dev.type != "cuda" or env.device.type != "cuda":
+            raise RuntimeError(f"{name} runs on a HIP device (the environment's state too); there is no CPU fallback")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if env.device.index is not None and env.device != dev:
+            raise ValueError("the environment must live on the learner's device (its state is updated in place by the library)")
+        self.ocp, self.env, self.T, self.lr, self.gamma, self.noise_scale = ocp, env, episode_length, float(lr), float(gamma), float(noise_scale)
+        self.E, self.device, self.group = env.num_envs, dev, group
+        T, E, NX = self.T, self.E, self.NX
+        self.rollout_mpc = MPCBatch(ocp, E, dev)
+        self.sample_mpc = MPCBatch(ocp, E * (T - 1), dev)
+        if mpc_gamma is not None:           # the handles' own discount factor (else the OCP's)
+            for m in (self.rollout_mpc, self.sample_mpc):
+                m.set_discount_factor(mpc_gamma)
+        self.n_p = ocp.n_p
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.theta = torch.as_tensor(ocp.p0, **f64).clone()            # updated in place (the handles copy it after every step)
+        self.learn_mask = torch.zeros_like(self.theta)
+        self.learn_mask[: ocp.n_model_p] = 1.0                          # the model's parameters
+        self.lo, self.hi = float(ocp.lbu[0]), float(ocp.ubu[0])
+        self.gen = torch.Generator(device=dev).manual_seed(seed)
+        # the episode's device state: every buffer keeps its address (captured graphs hold them)
+        self.obs = torch.zeros(E, NX, **f64)
+        self.row = torch.zeros(E, dtype=torch.int32, device=dev)
+        self.cold = torch.ones(E, dtype=torch.int32, device=dev)
+        self.eps = torch.zeros(T, E, dtype=torch.float32, device=dev)
+        self.S = torch.zeros(T, E, NX, **f64)
+        self.A = torch.zeros(T, E, **f64)
+        self.C = torch.zeros(T, E, **f64)
+        self.td = torch.zeros(T - 2, E, **f64)
+        self.valid = torch.zeros(T - 2, E, dtype=torch.uint8, device=dev)
+        self.msg = torch.zeros(self.n_p + 2, **f64)
+        self.step_out = torch.zeros(self.n_p, **f64)
+        self._lib = _lib.load()
+        nb = int(self._lib.mpcrl_qlearning_td_workspace_bytes(T, E, self.n_p))
+        if nb < 0:
+            raise RuntimeError(f"mpcrl_qlearning_td_workspace_bytes failed with {nb}")
+        self._td_ws = torch.zeros(nb, dtype=torch.uint8, device=dev)
+        # the roll-out handle holds an iterate from here on, so that the first solve of every episode (eager or replayed) is the
+        # per-instance cold start of the cold mask, never the handle-wide one of a fresh handle
+        self.rollout_mpc.solve(self.obs, cold=True)
+        self._graphs = None
+        self.last = None                # the roll-out solves of the last eager episode, one SolveResult per step
+        self.last_sweep = None          # (Q solve, V solve) of the last episode's learning sweep
+        self.episodes = 0
+
+    # ------------------------------------------------------------------ pieces (the same launches eager and captured)
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _start_episode(self, x0: Optional[torch.Tensor] = None) -> None:
+        self.env.reset()
+        if x0 is not None:
+            self.env.state.copy_(torch.as_tensor(x0, dtype=torch.float64, device=self.device).reshape(self.E, self.NX))
+        self.obs.copy_(self.env.state)
+        self.row.zero_()
+        self.cold.fill_(1)
+        torch.randn(self.T, self.E, generator=self.gen, dtype=torch.float32, device=self.device, out=self.eps)
+
+    def _rollout_step(self):
+        r = self.rollout_mpc.solve(self.obs, cold_mask=self.cold)           # the policy of every environment (mpc.get_action), one launch
+        with torch.cuda.device(self.device):
+            rc = self._collect(r)
+        if rc != 0:
+            raise RuntimeError(f"{self._COLLECT} failed with {rc}")
+        return r
+
+    def _sweep(self):
+        n = self.T - 1
+        s = self.S[:n].reshape(n * self.E, self.NX)
+        a = self.A[:n].reshape(n * self.E, 1)
+        # q_update: Q(s_i, a_i), dQ/dp_i; its bound multipliers are not kept (store_bounds=False) ...
+        rq = self.sample_mpc.solve(s, u0=a, sens_v=True, cold=True, store_bounds=False)
+        # ... update: V(s_i) from the Q solve's primal iterate, interior point from its default point
+        rv = self.sample_mpc.solve(s)
+        with torch.cuda.device(self.device):
+            rc = self._lib.mpcrl_qlearning_td_grad(
+                _ptr(rq.V), _ptr(rv.V), _ptr(rq.dV_dp), _ptr(rq.status), _ptr(rv.status), _ptr(self.C), _ptr(self.live), self.T, self.E, self.n_p,
+                self.gamma, self.lr, _ptr(self._td_ws), _ptr(self.td), _ptr(self.valid), _ptr(self.msg), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"mpcrl_qlearning_td_grad failed with {rc}")
+        return rq, rv
+
+    def _allreduce(self) -> None:
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and (self.group is not None or dist.get_world_size() > 1):
+            dist.all_reduce(self.msg, op=dist.ReduceOp.SUM, group=self.group)
+
+    def _apply(self) -> None:
+        with torch.cuda.device(self.device):
+            rc = self._lib.mpcrl_qlearning_apply(_ptr(self.msg), self.n_p, _ptr(self.learn_mask), _ptr(self.theta), _ptr(self.step_out),
+                                                 self._stream())
+        if rc != 0:
+            raise RuntimeError(f"mpcrl_qlearning_apply failed with {rc}")
+        for m in (self.rollout_mpc, self.sample_mpc):
+            m.set_theta(self.theta)                                    # mpc.set_parameter
+
+    def _env_carried(self):
+        """The environment's tensors that a roll-out step changes (put back after the warm-up of enable_graphs)."""
+        return [self.env.state]
+
+    # ------------------------------------------------------------------ the episode
+    def run_episode(self, x0: Optional[torch.Tensor] = None) -> EpisodeStats:
+        """One episode of all E environments, its learning sweep and the parameter step.  x0 [E, NX]: the initial states, instead of
+        what the environment's reset gives (which is taken all the same, so the environment's generator advances alike)."""
+        self._start_episode(x0)
+        if self._graphs is not None:
+            for _ in range(self.T):
+                self._graphs["rollout"].replay()
+            self._graphs["sweep"].replay()
+            self.last, self.last_sweep = None, self._graphs["sweep_out"]
+        else:
+            self.last = [self._rollout_step() for _ in range(self.T)]
+            self.last_sweep = self._sweep()
+        self._allreduce()                                               # the one collective of an episode (world > 1)
+        self._apply()
+        self.episodes += 1
+        return self._stats()
+
+    # ------------------------------------------------------------------ HIP graphs
+    def enable_graphs(self) -> None:
+        """Captures one roll-out step (solve + collect; replayed T times per episode) and the learning sweep (Q solve, V solve, TD kernel)
+        as two HIP graphs.  The episode start, the collective and the apply stay eager calls, so episodes are bit-identical to the eager
+        ones.  A warm-up of both pieces runs first on the capture stream (lazy initialisation, the solves' launch shape); the
+        environment's state is put back afterwards, and nothing else the learner carries from one episode to the next is touched by it."""
+        if self._graphs is not None:
+            return
+        dev = self.device
+        snap = [t.clone() for t in self._env_carried()]
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self._rollout_step()
+            self._sweep()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        for t, s in zip(self._env_carried(), snap):
+            t.copy_(s)
+        torch.cuda.synchronize(dev)
+        g_roll, g_sweep = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g_roll, stream=side):
+            self._rollout_step()
+        with torch.cuda.graph(g_sweep, stream=side):
+            out = self._sweep()
+        torch.cuda.synchronize(dev)
+        self._graphs = {"rollout": g_roll, "sweep": g_sweep, "sweep_out": out}

@@ -23,15 +23,14 @@ CPU path: the solver has none.  ``linear_collect_terms`` states the roll-out ker
 from __future__ import annotations
 
 import ctypes
-import math
 from typing import Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib
-from .batch import MPCBatch, _ptr
+from .batch import _ptr
 from .envs import BatchedLinearSystemEnv
-from .qlearning import EpisodeStats
+from .qlearning import DeviceQLearning, EpisodeStats
 
 
 def linear_env_par(env: BatchedLinearSystemEnv) -> list:
@@ -75,10 +74,14 @@ def linear_collect_terms(par: Sequence[float], state: torch.Tensor, u0: torch.Te
     return act, new_state, cost
 
 
-class LinearQLearning:
+class LinearQLearning(DeviceQLearning):
     """Q-learning of the linear-system MPC's parameters with E parallel environments (``env.num_envs``) and episodes of
     ``episode_length`` = T steps.  ``rollout_mpc`` solves the E policies, ``sample_mpc`` the E (T - 1) samples of the learning sweep.
-    ``gamma=None`` takes the OCP's discount factor (as ``BatchedQLearning``); both handles are set to it."""
+    ``gamma=None`` takes the OCP's discount factor (as ``BatchedQLearning``); both handles are set to it.  All of theta (A, B, b, V_0,
+    f) is learned."""
+
+    NX = 2
+    _COLLECT = "mpcrl_qlearning_linear_collect"
 
     def __init__(self, ocp, env, episode_length: int, lr: float = 1e-4, gamma: Optional[float] = None, noise_scale: float = 0.0, seed: int = 0,
                  device=None, group=None):
@@ -86,166 +89,24 @@ class LinearQLearning:
             raise ValueError("LinearQLearning needs the linear-system OCP (linear_system_ocp())")
         if not isinstance(env, BatchedLinearSystemEnv):
             raise TypeError("LinearQLearning needs a BatchedLinearSystemEnv")
-        if isinstance(episode_length, bool) or not isinstance(episode_length, int) or episode_length < 2:
-            raise ValueError("episode_length must be an int >= 2 (a TD term needs two samples)")
-        if not math.isfinite(lr):
-            raise ValueError("lr must be finite")
         gamma = ocp.gamma if gamma is None else gamma
-        if not (0.0 < gamma <= 1.0):
-            raise ValueError("gamma must lie in (0, 1]")
-        if not (math.isfinite(noise_scale) and noise_scale >= 0.0):
-            raise ValueError("noise_scale must be finite and >= 0")
-        dev = env.device if device is None else torch.device(device)
-        if dev.type != "cuda" or env.device.type != "cuda":
-            raise RuntimeError("LinearQLearning runs on a HIP device (the environment's state too); there is no CPU fallback")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if env.device.index is not None and env.device != dev:
-            raise ValueError("the environment must live on the learner's device (its state is updated in place by the library)")
-        self.ocp, self.env, self.T, self.lr, self.gamma, self.noise_scale = ocp, env, episode_length, float(lr), float(gamma), float(noise_scale)
-        self.E, self.device, self.group = env.num_envs, dev, group
-        T, E = self.T, self.E
-        self.rollout_mpc = MPCBatch(ocp, E, dev)
-        self.sample_mpc = MPCBatch(ocp, E * (T - 1), dev)
-        for m in (self.rollout_mpc, self.sample_mpc):
-            m.set_discount_factor(self.gamma)
-        self.n_p = ocp.n_p
-        f64 = dict(dtype=torch.float64, device=dev)
-        self.theta = torch.as_tensor(ocp.p0, **f64).clone()            # updated in place (the handles copy it after every step)
-        self.learn_mask = torch.zeros_like(self.theta)
-        self.learn_mask[: ocp.n_model_p] = 1.0                          # all of A, B, b, V_0, f
-        self.lo, self.hi = float(ocp.lbu[0]), float(ocp.ubu[0])
+        super().__init__(ocp, env, episode_length, lr, gamma, noise_scale, seed, device, group, mpc_gamma=gamma)
         self.par = linear_env_par(env)
         self._par_c = (ctypes.c_double * 12)(*self.par)
-        self.gen = torch.Generator(device=dev).manual_seed(seed)
-        # the episode's device state: every buffer keeps its address (captured graphs hold them)
-        self.obs = torch.zeros(E, 2, **f64)
-        self.row = torch.zeros(E, dtype=torch.int32, device=dev)
-        self.cold = torch.ones(E, dtype=torch.int32, device=dev)
-        self.eps = torch.zeros(T, E, dtype=torch.float32, device=dev)
-        self.u01 = torch.zeros(T, E, **f64)
-        self.S = torch.zeros(T, E, 2, **f64)
-        self.A = torch.zeros(T, E, **f64)
-        self.C = torch.zeros(T, E, **f64)
-        self.live = torch.ones(T, E, dtype=torch.uint8, device=dev)    # the environment never terminates: every row is a sample
-        self.td = torch.zeros(T - 2, E, **f64)
-        self.valid = torch.zeros(T - 2, E, dtype=torch.uint8, device=dev)
-        self.msg = torch.zeros(self.n_p + 2, **f64)
-        self.step_out = torch.zeros(self.n_p, **f64)
-        self._lib = _lib.load()
-        nb = int(self._lib.mpcrl_qlearning_td_workspace_bytes(T, E, self.n_p))
-        if nb < 0:
-            raise RuntimeError(f"mpcrl_qlearning_td_workspace_bytes failed with {nb}")
-        self._td_ws = torch.zeros(nb, dtype=torch.uint8, device=dev)
-        # the roll-out handle holds an iterate from here on, so that the first solve of every episode (eager or replayed) is the
-        # per-instance cold start of the cold mask, never the handle-wide one of a fresh handle
-        self.rollout_mpc.solve(self.obs, cold=True)
-        self._graphs = None
-        self.last = None                # the roll-out solves of the last eager episode, one SolveResult per step
-        self.last_sweep = None          # (Q solve, V solve) of the last episode's learning sweep
-        self.episodes = 0
-
-    # ------------------------------------------------------------------ pieces (the same launches eager and captured)
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
+        self.u01 = torch.zeros(self.T, self.E, dtype=torch.float64, device=self.device)
+        self.live = torch.ones(self.T, self.E, dtype=torch.uint8, device=self.device)    # the environment never terminates: every row is a sample
 
     def _start_episode(self, x0: Optional[torch.Tensor] = None) -> None:
-        self.env.reset()
-        if x0 is not None:
-            self.env.state.copy_(torch.as_tensor(x0, dtype=torch.float64, device=self.device).reshape(self.E, 2))
-        self.obs.copy_(self.env.state)
-        self.row.zero_()
-        self.cold.fill_(1)
-        torch.randn(self.T, self.E, generator=self.gen, dtype=torch.float32, device=self.device, out=self.eps)
+        super()._start_episode(x0)
         torch.rand(self.T, self.E, generator=self.env.gen, dtype=torch.float64, device=self.device, out=self.u01)
 
-    def _rollout_step(self):
-        r = self.rollout_mpc.solve(self.obs, cold_mask=self.cold)           # the policy of every environment (mpc.get_action), one launch
-        with torch.cuda.device(self.device):
-            rc = self._lib.mpcrl_qlearning_linear_collect(
-                self._par_c, self.E, self.T, _ptr(self.env.state), _ptr(r.u0), _ptr(r.status), _ptr(self.eps), _ptr(self.u01), self.lo, self.hi,
-                self.noise_scale, _ptr(self.obs), _ptr(self.row), _ptr(self.cold), _ptr(self.S), _ptr(self.A), _ptr(self.C), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"mpcrl_qlearning_linear_collect failed with {rc}")
-        return r
-
-    def _sweep(self):
-        n = self.T - 1
-        s = self.S[:n].reshape(n * self.E, 2)
-        a = self.A[:n].reshape(n * self.E, 1)
-        # q_update: Q(s_i, a_i), dQ/dp_i (181-187); its bound multipliers are not kept (the module docstring) ...
-        rq = self.sample_mpc.solve(s, u0=a, sens_v=True, cold=True, store_bounds=False)
-        # ... update: V(s_i) from the Q solve's primal iterate, interior point from its default point (189-190)
-        rv = self.sample_mpc.solve(s)
-        with torch.cuda.device(self.device):
-            rc = self._lib.mpcrl_qlearning_td_grad(
-                _ptr(rq.V), _ptr(rv.V), _ptr(rq.dV_dp), _ptr(rq.status), _ptr(rv.status), _ptr(self.C), _ptr(self.live), self.T, self.E, self.n_p,
-                self.gamma, self.lr, _ptr(self._td_ws), _ptr(self.td), _ptr(self.valid), _ptr(self.msg), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"mpcrl_qlearning_td_grad failed with {rc}")
-        return rq, rv
-
-    def _allreduce(self) -> None:
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and (self.group is not None or dist.get_world_size() > 1):
-            dist.all_reduce(self.msg, op=dist.ReduceOp.SUM, group=self.group)
-
-    def _apply(self) -> None:
-        with torch.cuda.device(self.device):
-            rc = self._lib.mpcrl_qlearning_apply(_ptr(self.msg), self.n_p, _ptr(self.learn_mask), _ptr(self.theta), _ptr(self.step_out),
-                                                 self._stream())
-        if rc != 0:
-            raise RuntimeError(f"mpcrl_qlearning_apply failed with {rc}")
-        for m in (self.rollout_mpc, self.sample_mpc):
-            m.set_theta(self.theta)                                    # mpc.set_parameter (204-205)
-
-    # ------------------------------------------------------------------ the episode
-    def run_episode(self, x0: Optional[torch.Tensor] = None) -> EpisodeStats:
-        """One episode of all E environments, its learning sweep and the parameter step.  x0 [E, 2]: the initial states, instead of the
-        environment's reset state."""
-        self._start_episode(x0)
-        if self._graphs is not None:
-            for _ in range(self.T):
-                self._graphs["rollout"].replay()
-            self._graphs["sweep"].replay()
-            self.last, self.last_sweep = None, self._graphs["sweep_out"]
-        else:
-            self.last = [self._rollout_step() for _ in range(self.T)]
-            self.last_sweep = self._sweep()
-        self._allreduce()                                               # the one collective of an episode (world > 1)
-        self._apply()
-        self.episodes += 1
-        return self._stats()
+    def _collect(self, r) -> int:
+        return self._lib.mpcrl_qlearning_linear_collect(
+            self._par_c, self.E, self.T, _ptr(self.env.state), _ptr(r.u0), _ptr(r.status), _ptr(self.eps), _ptr(self.u01), self.lo, self.hi,
+            self.noise_scale, _ptr(self.obs), _ptr(self.row), _ptr(self.cold), _ptr(self.S), _ptr(self.A), _ptr(self.C), self._stream())
 
     def _stats(self) -> EpisodeStats:
         nv = float(self.valid.sum().item())
         cand = float((self.T - 2) * self.E)
         return EpisodeStats(total_cost=float(self.C.sum().item()) / self.E, td_error_mean=float(self.td.sum().item()) / max(1.0, nv),
                             step=self.step_out.clone(), converged_fraction=nv / cand if cand > 0 else 1.0)
-
-    # ------------------------------------------------------------------ HIP graphs
-    def enable_graphs(self) -> None:
-        """Captures one roll-out step (solve + collect; replayed T times per episode) and the learning sweep (Q solve, V solve, TD kernel)
-        as two HIP graphs.  The episode start, the collective and the apply stay eager calls, so episodes are bit-identical to the eager
-        ones.  A warm-up of both pieces runs first on the capture stream (lazy initialisation, the solves' launch shape); the
-        environment's state is put back afterwards, and nothing else the learner carries from one episode to the next is touched by it."""
-        if self._graphs is not None:
-            return
-        dev = self.device
-        snap = self.env.state.clone()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            self._rollout_step()
-            self._sweep()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.env.state.copy_(snap)
-        torch.cuda.synchronize(dev)
-        g_roll, g_sweep = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g_roll, stream=side):
-            self._rollout_step()
-        with torch.cuda.graph(g_sweep, stream=side):
-            out = self._sweep()
-        torch.cuda.synchronize(dev)
-        self._graphs = {"rollout": g_roll, "sweep": g_sweep, "sweep_out": out}

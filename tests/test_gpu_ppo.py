@@ -161,11 +161,11 @@ def _surrogate_call(lib, c, ws, clip, ent, lr, norm, msg):
                                         _p(msg), _stream())
 
 
-@pytest.mark.parametrize("n_p", [3, 83])
-@pytest.mark.parametrize("M", [1, 127, 129, 300])
+@pytest.mark.parametrize("M,n_p", [(M, n_p) for n_p in (3, 83) for M in (1, 127, 129, 300)] + [(520, 251)])
 def test_surrogate_kernel_matches_torch_statement(M, n_p):
     """msg of mpcrl_ppo_surrogate_grad against ppo_surrogate_terms at 1e-12 relative on every entry, with and without advantage
-    normalisation; the call repeated gives equal bits; the workspace is all zero afterwards."""
+    normalisation; the call repeated gives equal bits; the workspace is all zero afterwards.  (520, 251): five workgroups, the last one
+    ragged, and n_p + 6 = 257 entries — a second chunk, of one entry, in the final sum."""
     from mpc4rl_amd import _lib, ppo_surrogate_terms
     lib = _lib.load()
     clip, ent, lr = 0.2, 0.01, 3e-3
