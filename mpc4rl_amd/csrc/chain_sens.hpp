@@ -282,13 +282,16 @@ __global__ void __launch_bounds__(64, 1) chain_sens_riccati_kernel(const LargeSp
     const WsArr Hex{(char *)w, (unsigned)lay.Hex};
     if (!((a.flags & 2) && a.dpi) || S.qmode) return;
     for (int e = lane; e < NW * NW; e += NT) Hex[N * NW * NW + e] = S.ck(N) * M::hess(true, e / NW, e % NW, th);
-    // barrier diagonal from the final (lam, t) of the bound rows (slacks are constants of the mirror, quirk q1)
+    // barrier diagonal from the final (lam, t) of the bound rows (slacks are constants of the mirror, quirk q1), capped as in the small
+    // models' pass and in the port (SENS_W_MAX): uncapped, lam / t ~ 1e15 .. 1e18 of an active STATE row (mpcrl_set_bounds) on the diagonal of
+    // P_k costs the recursion the digits of the entries next to it — du0*/dp off by O(1) at n_mass 3, a factorisation that is not
+    // positive definite (NaN rows) at n_mass 5, N = 40
     for (int e = lane; e < ne; e += NT) {
         const int k = e / NW, i = e - k * NW;
         double d = 0.0;
         if (!S.skipc(k, i))
             for (int sd = 0; sd < 2; ++sd)
-                if (S.has(sd, k, i)) d += S.LAM(sd, e) / S.TT(sd, e);
+                if (S.has(sd, k, i)) d += fmin(S.LAM(sd, e) / S.TT(sd, e), SENS_W_MAX);
         S.Dg[e] = d;
     }
     wave_sync();

@@ -263,6 +263,33 @@ def test_mirror_certifies_an_iterate_it_did_not_produce(oracle_port):
                 assert np.abs(mr.dpi_dp - r.dpi[i]).max() <= 1e-6 * max(1.0, np.abs(r.dpi[i]).max())
 
 
+def test_mirror_certifies_the_port_chain_q_mode(oracle_port):
+    """The port's chain Q mode (u_0 pinned) is what tests/test_gpu_chain_modes.py holds the chain kernels to; nothing else pins it.
+    The mirror of the reference's NLP at the port's own iterate of two pinned instances (n_mass 3, N = 10, tol 1e-8): the reference's
+    update_nlp thresholds hold and dQ/dp is the mirror's dL/dp (measured: 3e-15)."""
+    import test_gpu_chain_modes as T
+    c = T.case(oracle_port, *[T.MIRROR[k] for k in ("n_mass", "N", "B", "seed", "tol")])
+    r, rows = c.ref_q, [2, 3]
+    assert np.all(r.status == 0) and np.all(r.dpi == 0.0)
+    dL, L = T.mirror_q_mode(c.P, (r.X, r.U, r.PI, r.BND), c.x0, c.u0, r.V, rows)
+    assert T.largest_error({"dV": r.dV[rows]}, {"dV": dL}, fields=("dV",)) < 1e-6
+    assert np.abs(L - r.V[rows]).max() < 1e-5          # lam'h + pi'g vanish at a KKT point up to the barrier parameter
+
+
+def test_mirror_certifies_the_port_chain_state_bound(oracle_port):
+    """... and a chain with a state row among its bounds (the reference chain bounds controls only): a lower bound on the end
+    point's x position at stages 1 .. N, halfway to the smallest value the unconstrained solutions reach.  At the first two instances
+    where it is active the mirror's dL/dp and dz/dp[:nu] equal the port's dV/dp, du0*/dp (measured: 4e-15, 8.5e-8; strict-complementarity
+    margin 6.4e-4, the bar of the cartpole active-bound test is 1e-4)."""
+    import test_gpu_chain_modes as T
+    c = T.case(oracle_port, *[T.MIRROR[k] for k in ("n_mass", "N", "B", "seed", "tol")])
+    ix, lo, P_sb, r, rows = T.mirror_state_bound_problem(oracle_port, c)
+    assert r.X[:, 1:, ix].min() > lo - 1e-9 and np.all(r.BND[rows, 0, :, c.ocp.nu + ix].max(1) > 1e-3)
+    dL, dpi, L, sc = T.mirror_state_bound(P_sb, (r.X, r.U, r.PI, r.BND), c.x0, r.V, rows)
+    assert sc.min() >= 1e-4
+    assert T.largest_error({"dV": r.dV[rows], "dpi": r.dpi[rows]}, {"dV": dL, "dpi": dpi}, fields=("dV", "dpi")) < 1e-6
+
+
 def test_certification_worker_runs_in_a_process_pool(oracle_port):
     """The GPU certification tests farm oracle.from_iterate.certify_job out to fresh interpreters (spawn): the worker must be
     importable there and return what the in-process call returns."""
