@@ -444,12 +444,9 @@ __global__ void __launch_bounds__(64, 1) chain_sqp_kernel(const LargeSpec sp, co
         const bool tight = tol_res <= IPM_TOL_RES && tol_mu <= IPM_TOL_MU;
         const double warm_mu = (stepn < 0.0 || exact_qp) ? 0.0 : fmin(IPM_WARM_MAX, fmax(IPM_WARM_MIN, IPM_WARM_C * stepn * stepn));
         S.frac_fixed = exact_qp;
-        // the SQP Hessian: this lane's tiles of (R, Q) without c_k, in registers
-        HessConst<M> hs;
-        hs.th = S.th, hs.sck = S.sCK();
         // (MPCRL_COLD_DUAL keeps the stored multipliers of the dynamics while the QP starts from zero ones: not the same residual)
         const bool rg_ready = stepn >= 0.0 || !(a.flags & 16);
-        if (!S.qp_solve(hs, x0, u0f, n_ipm, warm_mu, tol_res, tol_mu, rg_ready)) {
+        if (!S.qp_solve(x0, u0f, n_ipm, warm_mu, tol_res, tol_mu, rg_ready)) {
             status = 4;
             break;
         }

@@ -32,7 +32,6 @@ struct HessConst {
     MPCRL_DI void init(const S_ &S, unsigned) { th = S.th, sck = S.sCK(), tab = S.lds + ChainCfg<M>::oBig; }
     MPCRL_DI void prefetch(int) {}
     MPCRL_DI void advance(int) {}
-    MPCRL_DI unsigned hex_offset() const { return 0u; }
     MPCRL_DI double tile(int k, int rg, int tj) const { return sck[k] * tab[(rg * O::NT + tj) * 64 + lane_]; }
     MPCRL_DI double term(int N, int i, int j) const { return sck[N] * M::Qs(th, i, j); }
 };
@@ -64,7 +63,6 @@ struct HessGlobal {
             for (int tj = 0; tj < O::NT; ++tj) hc[rg][tj] = hn[rg][tj];
         if (k > 0) prefetch(k - 1);
     }
-    MPCRL_DI unsigned hex_offset() const { return Hex.off; }
     MPCRL_DI double tile(int, int rg, int tj) const { return hc[rg][tj]; }
     MPCRL_DI double term(int N, int i, int j) const { return Hex[N * NW * NW + (NU + i) * NW + NU + j]; }
 };
@@ -1283,52 +1281,181 @@ struct ChainSolver {
         wave_sync();
     }
 
-    // ---- the interior-point iteration of qp_solve (below) with the BOUND ROWS IN REGISTERS (round 4; at most 128 rows: two per lane — the chain
-    // problems bound the controls only, 3 x 40 rows).  Every row phase of qp_solve below is a pass over the rows through the
-    // workspace: multipliers, slacks, the row's entry of the iterate and of the direction — a global-memory round trip (~2 us with
-    // the chip streaming) per phase, ~27 of them per iteration, one lane-pass each.  Here a lane keeps its rows' (lam, t, aff, value,
-    // residual entry) for the whole QP; what the sweeps need (barrier diagonal, modified gradient at the rows) is stored, the
-    // direction at the rows is the one load per sweep, and the dense vector updates of an iteration are one fused pass.
-    template <class HS>
-    MPCRL_DI bool qp_solve_rows(HS &hs, const double *x0, const double *u0f, int &n_it, double warm_mu, double tol_res, double tol_mu, bool rg_ready) {
+    // ---- the bound rows of the interior point (qp_solve below).  One SIDE of a row (sd = 0: lower bound, 1: upper) with multiplier
+    // l and slack t, and every row formula of the iteration, once.  Every fused multiply-add is written out: left to the compiler's
+    // contraction, a product that two passes share (l rd, l dt) is kept as a product and the results change in the last bit with the
+    // code around them.  W is a row of one of the two row stores below.
+    struct RowSide {
+        int sd;
+        double l, t, rd;      // rd = t - (distance of the row's value v to the bound)
+        template <class W>
+        MPCRL_DI static double slack(W &w, int sd, double v) { return sd ? w.ub() - v : v - w.lb(); }
+        template <class W>
+        MPCRL_DI RowSide(W &w, int sd_, double v) : sd(sd_), l(w.l(sd_)), t(w.t(sd_)), rd(w.t(sd_) - slack(w, sd_, v)) {}
+        // residual of l t = sigma mu - aff; c = 0 (predictor) or aff - sigma mu (corrector)
+        MPCRL_DI double rm(double c) const { return fma(l, t, c); }
+        // the row's share of the barrier diagonal and of the modified gradient
+        MPCRL_DI void barrier(double rm_, double &dg, double &er) const { dg += l / t, er += (sd ? -1.0 : 1.0) * fma(-l, rd, rm_) / t; }
+        MPCRL_DI double dt(double dv) const { return -rd + (sd ? -dv : dv); }
+        MPCRL_DI double dl(double rm_, double dt1) const { return fma(-l, dt1, -rm_) / t; }
+        MPCRL_DI double dl_aff(double dt1) const { return fma(t, -l, -(l * dt1)) / t; }      // (the predictor's dl where only the products are needed)
+        MPCRL_DI void ratio(double dl1, double dt1, double &amax) const {
+            if (dl1 < 0.0) amax = fmin(amax, -l / dl1);
+            if (dt1 < 0.0) amax = fmin(amax, -t / dt1);
+        }
+    };
+    // REGISTER store (at most 128 rows, two per lane: the chain problems bound the controls only, 3 x 40 rows).  As passes over the
+    // workspace every row phase is a global-memory round trip (~2 us with the chip streaming), ~27 of them per iteration.  Here a lane
+    // keeps its rows' (lam, t, aff, value, residual entry) for the whole QP; what the sweeps need (barrier diagonal, modified gradient
+    // at the rows) is stored, the direction at the rows is the one load per sweep.
+    struct RegRows {
+        ChainSolver &S;
+        bool on[2], hs_[2][2], fr[2];
+        int re_[2];
+        unsigned doff[2], Doff[2];      // where the row's entry of (dx | du) and (Dx | Du) sits, relative to dx / Dx
+        double lb_[2], ub_[2], v0[2], dvq[2], rgr[2], lm[2][2], tt_[2][2], af[2][2], dvr[2];
+        struct Row {
+            RegRows &R;
+            const int j;
+            MPCRL_DI bool on() const { return R.on[j]; }
+            MPCRL_DI bool has(int sd) const { return R.hs_[j][sd]; }
+            MPCRL_DI bool free_rg() const { return R.fr[j]; }
+            MPCRL_DI int e() const { return R.re_[j]; }
+            MPCRL_DI double lb() const { return R.lb_[j]; }
+            MPCRL_DI double ub() const { return R.ub_[j]; }
+            MPCRL_DI double v() const { return R.v0[j] + R.dvq[j]; }
+            MPCRL_DI double dv() const { return R.dvr[j]; }
+            MPCRL_DI double rg() const { return R.rgr[j]; }
+            MPCRL_DI double &l(int sd) { return R.lm[j][sd]; }
+            MPCRL_DI double &t(int sd) { return R.tt_[j][sd]; }
+            MPCRL_DI double &aff(int sd) { return R.af[j][sd]; }
+            MPCRL_DI void add_rg(double d) { R.rgr[j] += d, R.S.rg[R.re_[j]] = R.rgr[j]; }
+            MPCRL_DI void step(double alpha) { R.dvq[j] = fma(alpha, R.dvr[j], R.dvq[j]); }      // (the same fma the dense update applies to the entry)
+        };
+        MPCRL_DI explicit RegRows(ChainSolver &S_) : S(S_) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int r_ = S.lane + 64 * j;
+                on[j] = r_ < S.nrows;
+                int k = 0, i = 0;
+                if (on[j]) S.row_of(r_, k, i);
+                re_[j] = k * NW + i;
+                lb_[j] = S.lbv(k, i), ub_[j] = S.ubv(k, i);
+                hs_[j][0] = on[j] && S.has(0, k, i), hs_[j][1] = on[j] && S.has(1, k, i);
+                fr[j] = on[j] && !S.skipc(k, i) && !S.fixedc(k, i);
+                const bool isu = i < NU;
+                doff[j] = isu ? (S.du.off - S.dx.off) + (unsigned)((k < S.N ? k : 0) * NU + i) : (unsigned)(k * NX + i - NU);
+                Doff[j] = isu ? (S.Du.off - S.Dx.off) + (unsigned)((k < S.N ? k : 0) * NU + i) : (unsigned)(k * NX + i - NU);
+                v0[j] = on[j] ? S.vc(k, i) : 0.0;
+                dvq[j] = on[j] ? S.dx[(int)doff[j]] : 0.0;
+                rgr[j] = on[j] ? S.rg[re_[j]] : 0.0;
+                dvr[j] = 0.0;
+#pragma unroll
+                for (int sd = 0; sd < 2; ++sd) lm[j][sd] = 0.0, tt_[j][sd] = 1.0, af[j][sd] = 0.0;
+            }
+        }
+        template <class F>
+        MPCRL_DI void each(F &&fn) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                Row w{*this, j};
+                fn(w);
+            }
+        }
+        MPCRL_DI void store() {      // multipliers and slacks back to the workspace (qp_residuals, next QP's warm start, the kernel's write-out)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int sd = 0; sd < 2; ++sd)
+                    if (hs_[j][sd]) S.LAM(sd, re_[j]) = lm[j][sd], S.TT(sd, re_[j]) = tt_[j][sd];
+        }
+        MPCRL_DI void reread_rg(bool rg_ready) {      // after the starting residuals
+            if (!rg_ready) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j) rgr[j] = on[j] ? S.rg[re_[j]] : 0.0;
+            } else {      // the stage-0 terms of a warm solve from a new state may have touched this lane's entries
+#pragma unroll
+                for (int j = 0; j < 2; ++j) rgr[j] = (on[j] && re_[j] < NW) ? S.rg[re_[j]] : rgr[j];
+            }
+        }
+        MPCRL_DI void load_dir() {      // the direction at the rows: the one load of the pass
+#pragma unroll
+            for (int j = 0; j < 2; ++j) dvr[j] = on[j] ? S.Dx[(int)Doff[j]] : 0.0;
+        }
+        MPCRL_DI void before_update() {}
+        MPCRL_DI void scale_rg(double om) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) rgr[j] *= om;
+        }
+    };
+    // WORKSPACE store (more rows than two per lane: state bounds set through mpcrl_set_bounds).  A row is its (stage, coordinate); its
+    // state is read from and written to the workspace where the iteration uses it.  Row r belongs to lane r % 64 in every pass, so
+    // lam / t / aff are only ever touched by their own lane and need no wave_sync of their own.
+    struct WsRows {
+        ChainSolver &S;
+        struct Row {
+            ChainSolver &S;
+            int k, i, e_;
+            MPCRL_DI bool on() const { return true; }
+            MPCRL_DI bool has(int sd) const { return S.has(sd, k, i); }
+            MPCRL_DI bool free_rg() const { return !S.skipc(k, i) && !S.fixedc(k, i); }
+            MPCRL_DI int e() const { return e_; }
+            MPCRL_DI double lb() const { return S.lbv(k, i); }
+            MPCRL_DI double ub() const { return S.ubv(k, i); }
+            MPCRL_DI double v() const { return S.vc(k, i) + S.dvc(S.dx, S.du, k, i); }
+            MPCRL_DI double dv() const { return S.dvc(S.Dx, S.Du, k, i); }
+            MPCRL_DI double rg() const { return S.rg[e_]; }
+            MPCRL_DI double &l(int sd) { return S.LAM(sd, e_); }
+            MPCRL_DI double &t(int sd) { return S.TT(sd, e_); }
+            MPCRL_DI double &aff(int sd) { return S.AFF(sd, e_); }
+            MPCRL_DI void add_rg(double d) { S.rg[e_] += d; }
+            MPCRL_DI void step(double) {}
+        };
+        MPCRL_DI explicit WsRows(ChainSolver &S_) : S(S_) {}
+        template <class F>
+        MPCRL_DI void each(F &&fn) {
+            for (int r_ = S.lane; r_ < S.nrows; r_ += NT) {
+                Row w{S, 0, 0, 0};
+                S.row_of(r_, w.k, w.i);
+                w.e_ = w.k * NW + w.i;
+                fn(w);
+            }
+        }
+        MPCRL_DI void store() {}
+        MPCRL_DI void reread_rg(bool) {}
+        MPCRL_DI void load_dir() {}
+        // the rows' update reads (dx | du) at the rows; the dense update that follows rewrites those entries from other lanes
+        MPCRL_DI void before_update() { wave_sync(); }
+        MPCRL_DI void scale_rg(double) {}
+    };
+
+    // ---- Mehrotra predictor-corrector on the QP of the current linearisation (hard bounds) --------------------
+    // rg_ready: rg holds q -+ lam + [B A]' NUv - [0; NUv] of this linearisation (round_start left it there) and the QP starts from
+    // nuq = NUv (warm) or from NUv = 0 (cold): its starting residual needs no pass over the [B A]_k
+    MPCRL_DI bool qp_solve(const double *x0, const double *u0f, int &n_it, double warm_mu, double tol_res, double tol_mu, bool rg_ready = false) {
+        if (nrows <= 128) return qp_solve_on<RegRows>(x0, u0f, n_it, warm_mu, tol_res, tol_mu, rg_ready);
+        return qp_solve_on<WsRows>(x0, u0f, n_it, warm_mu, tol_res, tol_mu, rg_ready);
+    }
+    template <class Rows>
+    MPCRL_DI bool qp_solve_on(const double *x0, const double *u0f, int &n_it, double warm_mu, double tol_res, double tol_mu, bool rg_ready) {
         const bool warm = warm_mu > 0.0;
         const int ne = (N + 1) * NW;
-        constexpr bool MERGED = MPCRL_CHAIN_MERGE_CALLS != 0 && std::is_same<HS, HessConst<M>>::value;
         for (int e = lane; e < (N + 1) * NX; e += NT) dx[e] = e < NX ? x0[e] - X[e] : 0.0, nuq[e] = warm ? NUv[e] : 0.0;
         for (int e = lane; e < N * NU; e += NT) du[e] = (qmode && e < NU) ? u0f[e] - U[e] : 0.0;
         wave_sync();
-        // ---- this lane's rows
-        bool on[2], hs_[2][2];
-        int re_[2];
-        unsigned doff[2], Doff[2];      // where the row's entry of (dx | du) and (Dx | Du) sits, relative to dx / Dx
-        double lb_[2], ub_[2], v0[2], dvq[2], rgr[2], lm[2][2], tt_[2][2], af[2][2];
+        Rows R(*this);
         double cnt = 0.0;
+        R.each([&](auto &w) {      // the starting multipliers and slacks
+            const double v = w.v();
+            double drg = 0.0;      // the multipliers of this row change: so does its entry of the stationarity residual
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int r_ = lane + 64 * j;
-            on[j] = r_ < nrows;
-            int k = 0, i = 0;
-            if (on[j]) row_of(r_, k, i);
-            re_[j] = k * NW + i;
-            lb_[j] = lbv(k, i), ub_[j] = ubv(k, i);
-            hs_[j][0] = on[j] && has(0, k, i), hs_[j][1] = on[j] && has(1, k, i);
-            const bool isu = i < NU;
-            doff[j] = isu ? (du.off - dx.off) + (unsigned)((k < N ? k : 0) * NU + i) : (unsigned)(k * NX + i - NU);
-            Doff[j] = isu ? (Du.off - Dx.off) + (unsigned)((k < N ? k : 0) * NU + i) : (unsigned)(k * NX + i - NU);
-            v0[j] = on[j] ? vc(k, i) : 0.0;
-            dvq[j] = on[j] ? dx[(int)doff[j]] : 0.0;
-            rgr[j] = on[j] ? rg[re_[j]] : 0.0;
-            const double v = v0[j] + dvq[j];
-            double drg = 0.0;
-#pragma unroll
-            for (int sd = 0; sd < 2; ++sd) {
-                lm[j][sd] = 0.0, tt_[j][sd] = 1.0, af[j][sd] = 0.0;
-                if (hs_[j][sd]) {
+            for (int sd = 0; sd < 2; ++sd)
+                if (w.has(sd)) {
                     cnt += 1.0;
-                    const double l_old = LAM(sd, re_[j]), sl = sd ? ub_[j] - v : v - lb_[j];
+                    const double l_old = LAM(sd, w.e()), sl = RowSide::slack(w, sd, v);
                     double l, t1;
                     if (warm) {
-                        l = l_old, t1 = fmax(sl, TT(sd, re_[j]));
+                        l = l_old, t1 = fmax(sl, TT(sd, w.e()));
                         if (l * t1 < warm_mu) {
                             if (l >= t1)
                                 t1 = warm_mu / l;
@@ -1339,50 +1466,37 @@ struct ChainSolver {
                         t1 = fmax(sl, IPM_T_MIN);
                         l = IPM_MU0 / t1;
                     }
-                    lm[j][sd] = l, tt_[j][sd] = t1;
+                    w.l(sd) = l, w.t(sd) = t1;
                     drg += sd ? l - l_old : l_old - l;
                 }
-            }
-            if (rg_ready && on[j] && !skipc(k, i) && !fixedc(k, i)) {
-                rgr[j] += drg;
-                rg[re_[j]] = rgr[j];
-            }
-        }
-        auto store_rows = [&]() {      // multipliers and slacks back to the workspace (next QP's warm start, the kernel's write-out)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int sd = 0; sd < 2; ++sd)
-                    if (hs_[j][sd]) LAM(sd, re_[j]) = lm[j][sd], TT(sd, re_[j]) = tt_[j][sd];
-        };
+            if (rg_ready && w.free_rg()) w.add_rg(drg);
+        });
         const double n_rows = wave_sum(cnt);
-        if (!rg_ready) store_rows();      // (qp_residuals reads lam from the workspace)
+        if (!rg_ready) R.store();      // (qp_residuals reads lam from the workspace)
         wave_sync();
         bool ok = false, stepped = false;
+        // The residuals of the LINEAR equations (dynamics rb, stationarity rg) are evaluated once per QP: a step of length alpha
+        // along a direction that solves the Newton system takes them to (1 - alpha) times their value, exactly — they are
+        // scaled at the end of the iteration instead of being re-evaluated (a sweep over all [B A]_k: 161 KB per instance at
+        // n_mass 5, 10 % of the kernel).  Only the bound rows below depend on the step nonlinearly (complementarity).
         double rlin = wave_max(rg_ready ? qp_start_residuals() : qp_residuals_call(ctx()));
-        if (!rg_ready) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) rgr[j] = on[j] ? rg[re_[j]] : 0.0;
-        } else {      // the stage-0 terms of a warm solve from a new state may have touched this lane's entries
-#pragma unroll
-            for (int j = 0; j < 2; ++j) rgr[j] = (on[j] && re_[j] < NW) ? rg[re_[j]] : rgr[j];
-        }
+        R.reread_rg(rg_ready);
         // rt = rg, Dg = 0 once: the rows rewrite their own entries in every pass, the other entries of rt follow rg in the fused update
         batched_pass<8>(ne, lane, [&](int e) { return rg[e]; }, [&](int e, double v) { rt[e] = v, Dg[e] = 0.0; });
         wave_sync();
         for (int it = 0;; ++it) {
             ph(7);
             double rloc = rlin, muloc = 0.0;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const double v = v0[j] + dvq[j];
+            R.each([&](auto &w) {
+                const double v = w.v();
 #pragma unroll
                 for (int sd = 0; sd < 2; ++sd)
-                    if (hs_[j][sd]) {
-                        rloc = fmax(rloc, fabs(tt_[j][sd] - (sd ? ub_[j] - v : v - lb_[j])));
-                        muloc = fma(lm[j][sd], tt_[j][sd], muloc);
+                    if (w.has(sd)) {
+                        const RowSide s(w, sd, v);
+                        rloc = fmax(rloc, fabs(s.rd));
+                        muloc = fma(s.l, s.t, muloc);
                     }
-            }
+            });
             const double rinf = wave_max(rloc);
             const double mu = n_rows > 0.0 ? wave_sum(muloc) / n_rows : 0.0;
             if (rinf <= tol_res && mu <= tol_mu) {
@@ -1392,37 +1506,33 @@ struct ChainSolver {
             if (it >= IPM_MAX_ITER || !(rinf < 1e300)) break;
             ++n_it;
             ph(0);
-            double sigma_mu = 0.0, alpha = 1.0, dvr[2] = {0.0, 0.0};
+            double sigma_mu = 0.0, alpha = 1.0;
             bool fail = false;
             for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
+                R.each([&](auto &w) {      // barrier diagonal + modified gradient at the rows
                     double dg = 0.0, er = 0.0;
-                    const double v = v0[j] + dvq[j];
+                    const double v = w.v();
 #pragma unroll
                     for (int sd = 0; sd < 2; ++sd)
-                        if (hs_[j][sd]) {
-                            const double l1 = lm[j][sd], t1 = tt_[j][sd];
-                            const double rd1 = t1 - (sd ? ub_[j] - v : v - lb_[j]);
-                            const double rm = fma(l1, t1, pass ? af[j][sd] - sigma_mu : 0.0);
-                            dg += l1 / t1;
-                            er += (sd ? -1.0 : 1.0) * (rm - l1 * rd1) / t1;
+                        if (w.has(sd)) {
+                            const RowSide s(w, sd, v);
+                            s.barrier(s.rm(pass ? w.aff(sd) - sigma_mu : 0.0), dg, er);
                         }
-                    if (on[j]) {
-                        if (pass == 0) Dg[re_[j]] = dg;
-                        rt[re_[j]] = rgr[j] + er;
+                    if (w.on()) {
+                        if (pass == 0) Dg[w.e()] = dg;
+                        rt[w.e()] = w.rg() + er;
                     }
-                }
+                });
                 wave_sync();
                 ph(1);
-                if constexpr (MERGED) {
+                if constexpr (MPCRL_CHAIN_MERGE_CALLS != 0) {
                     if (pass == 0) {
-                        if (!pred_call<HS>(ctx(), hs.hex_offset(), rt.off, rb.off)) fail = true;
+                        if (!pred_call(ctx(), rt.off, rb.off)) fail = true;
                     } else
                         corr_call(ctx(), rt.off, rb.off);
                 } else {
                     if (pass == 0) {
-                        if (!factor_call<HS>(ctx(), hs.hex_offset(), rt.off, rb.off)) fail = true;
+                        if (!factor_call<HessConst<M>>(ctx(), 0u, rt.off, rb.off)) fail = true;
                         ph(2);
                     } else {
                         backward_vec_call(ctx(), rt.off);
@@ -1431,40 +1541,31 @@ struct ChainSolver {
                     forward_call(ctx(), rb.off);
                 }
                 ph(4);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) dvr[j] = on[j] ? Dx[(int)Doff[j]] : 0.0;      // the direction at the rows: the one load of the pass
+                R.load_dir();
                 double amax = 1.0, muaff = 0.0;
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const double v = v0[j] + dvq[j], dv = dvr[j];
+                R.each([&](auto &w) {
+                    const double v = w.v(), dv = w.dv();
 #pragma unroll
                     for (int sd = 0; sd < 2; ++sd)
-                        if (hs_[j][sd]) {
-                            const double l1 = lm[j][sd], t1 = tt_[j][sd];
-                            const double rd1 = t1 - (sd ? ub_[j] - v : v - lb_[j]);
-                            const double rm = fma(l1, t1, pass ? af[j][sd] - sigma_mu : 0.0);
-                            const double dt1 = -rd1 + (sd ? -dv : dv);
-                            const double dl1 = (-rm - l1 * dt1) / t1;
-                            if (dl1 < 0.0) amax = fmin(amax, -l1 / dl1);
-                            if (dt1 < 0.0) amax = fmin(amax, -t1 / dt1);
+                        if (w.has(sd)) {
+                            const RowSide s(w, sd, v);
+                            const double dt1 = s.dt(dv), dl1 = s.dl(s.rm(pass ? w.aff(sd) - sigma_mu : 0.0), dt1);
+                            s.ratio(dl1, dt1, amax);
                         }
-                }
+                });
                 amax = -wave_max(-amax);
                 if (pass == 0) {
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const double v = v0[j] + dvq[j], dv = dvr[j];
+                    R.each([&](auto &w) {
+                        const double v = w.v(), dv = w.dv();
 #pragma unroll
                         for (int sd = 0; sd < 2; ++sd)
-                            if (hs_[j][sd]) {
-                                const double l1 = lm[j][sd], t1 = tt_[j][sd];
-                                const double rd1 = t1 - (sd ? ub_[j] - v : v - lb_[j]);
-                                const double dt1 = -rd1 + (sd ? -dv : dv);
-                                const double dl1 = (-l1 * t1 - l1 * dt1) / t1;
-                                muaff = fma(fma(amax, dl1, l1), fma(amax, dt1, t1), muaff);
-                                af[j][sd] = dl1 * dt1;
+                            if (w.has(sd)) {
+                                const RowSide s(w, sd, v);
+                                const double dt1 = s.dt(dv), dl1 = s.dl_aff(dt1);
+                                muaff = fma(fma(amax, dl1, s.l), fma(amax, dt1, s.t), muaff);
+                                w.aff(sd) = dl1 * dt1;
                             }
-                    }
+                    });
                     const double mu_aff = n_rows > 0.0 ? wave_sum(muaff) / n_rows : 0.0;
                     const double ratio = mu > 0.0 ? mu_aff / mu : 0.0;
                     sigma_mu = ratio * ratio * ratio * mu;
@@ -1473,22 +1574,19 @@ struct ChainSolver {
             }
             ph(5);
             if (fail) break;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const double v = v0[j] + dvq[j], dv = dvr[j];
+            R.each([&](auto &w) {
+                const double v = w.v(), dv = w.dv();
 #pragma unroll
                 for (int sd = 0; sd < 2; ++sd)
-                    if (hs_[j][sd]) {
-                        const double l1 = lm[j][sd], t1 = tt_[j][sd];
-                        const double rd1 = t1 - (sd ? ub_[j] - v : v - lb_[j]);
-                        const double rm = fma(l1, t1, af[j][sd] - sigma_mu);
-                        const double dt1 = -rd1 + (sd ? -dv : dv);
-                        const double dl1 = (-rm - l1 * dt1) / t1;
-                        lm[j][sd] = fma(alpha, dl1, l1);
-                        tt_[j][sd] = fma(alpha, dt1, t1);
+                    if (w.has(sd)) {
+                        const RowSide s(w, sd, v);
+                        const double dt1 = s.dt(dv), dl1 = s.dl(s.rm(w.aff(sd) - sigma_mu), dt1);
+                        w.l(sd) = fma(alpha, dl1, s.l);
+                        w.t(sd) = fma(alpha, dt1, s.t);
                     }
-                dvq[j] = fma(alpha, dvr[j], dvq[j]);      // (the same fma the dense update below applies to the entry)
-            }
+                w.step(alpha);
+            });
+            R.before_update();
             // one fused pass: dx += alpha Dx, du += alpha Du, rg *= (1 - alpha) (and rt = rg), rb *= (1 - alpha)
             const double om = 1.0 - alpha;
             struct Upd {
@@ -1506,205 +1604,13 @@ struct ChainSolver {
                                 if (e < N * NU) du[e] = fma(alpha, v.d, v.e);
                                 if (e < N * NX) rb[e] = om * v.f;
                             });
-#pragma unroll
-            for (int j = 0; j < 2; ++j) rgr[j] *= om;
+            R.scale_rg(om);
             rlin *= om;
             stepped = true;
             wave_sync();
         }
-        store_rows();
+        R.store();
         wave_sync();
-        if (stepped) costate_call(ctx());      // nuq of the point the iteration ended at (no iteration: the warm multipliers stand)
-        return ok;
-    }
-
-    // ---- Mehrotra predictor-corrector on the QP of the current linearisation (hard bounds) --------------------
-    // rg_ready: rg holds q -+ lam + [B A]' NUv - [0; NUv] of this linearisation (round_start left it there) and the QP starts from
-    // nuq = NUv (warm) or from NUv = 0 (cold): its starting residual needs no pass over the [B A]_k
-    template <class HS>
-    MPCRL_DI bool qp_solve(HS &hs, const double *x0, const double *u0f, int &n_it, double warm_mu, double tol_res, double tol_mu, bool rg_ready = false) {
-        if (nrows <= 128) return qp_solve_rows(hs, x0, u0f, n_it, warm_mu, tol_res, tol_mu, rg_ready);
-        // more rows than two per lane (state bounds set through mpcrl_set_bounds): the row phases as passes over the workspace
-        const bool warm = warm_mu > 0.0;
-        const int ne = (N + 1) * NW;
-        for (int e = lane; e < (N + 1) * NX; e += NT) dx[e] = e < NX ? x0[e] - X[e] : 0.0, nuq[e] = warm ? NUv[e] : 0.0;
-        for (int e = lane; e < N * NU; e += NT) du[e] = (qmode && e < NU) ? u0f[e] - U[e] : 0.0;
-        wave_sync();
-        double cnt = 0.0;
-        for (int r_ = lane; r_ < nrows; r_ += NT) {
-            int k, i;
-            row_of(r_, k, i);
-            const int e = k * NW + i;
-            const double v = vc(k, i) + dvc(dx, du, k, i);
-            double drg = 0.0;      // the multipliers of this row change: so does its entry of the stationarity residual
-            for (int sd = 0; sd < 2; ++sd)
-                if (has(sd, k, i)) {
-                    cnt += 1.0;
-                    const double l_old = LAM(sd, e);
-                    double l_new;
-                    if (warm) {
-                        double l = l_old, tt = fmax(bslack(sd, k, i, v), TT(sd, e));
-                        if (l * tt < warm_mu) {
-                            if (l >= tt)
-                                tt = warm_mu / l;
-                            else
-                                l = warm_mu / tt;
-                        }
-                        LAM(sd, e) = l, TT(sd, e) = tt;
-                        l_new = l;
-                    } else {
-                        const double tt = fmax(bslack(sd, k, i, v), IPM_T_MIN);
-                        TT(sd, e) = tt;
-                        l_new = IPM_MU0 / tt;
-                        LAM(sd, e) = l_new;
-                    }
-                    drg += sd ? l_new - l_old : l_old - l_new;
-                }
-            if (rg_ready && !skipc(k, i) && !fixedc(k, i)) rg[e] += drg;
-        }
-        const double n_rows = wave_sum(cnt);
-        wave_sync();
-        bool ok = false, stepped = false;
-        double rlin = 0.0;
-        for (int it = 0;; ++it) {
-            ph(7);
-            // The residuals of the LINEAR equations (dynamics rb, stationarity rg) are evaluated once per QP: a step of length alpha
-            // along a direction that solves the Newton system takes them to (1 - alpha) times their value, exactly — they are
-            // scaled at the end of the iteration instead of being re-evaluated (a sweep over all [B A]_k: 161 KB per instance at
-            // n_mass 5, 10 % of the kernel).  Only the bound rows below depend on the step nonlinearly (complementarity).
-            if (it == 0) rlin = wave_max(rg_ready ? qp_start_residuals() : qp_residuals_call(ctx()));
-            double rloc = rlin, muloc = 0.0;
-            for (int r_ = lane; r_ < nrows; r_ += NT) {
-                int k, i;
-                row_of(r_, k, i);
-                const int e = k * NW + i;
-                const double v = vc(k, i) + dvc(dx, du, k, i);
-                for (int sd = 0; sd < 2; ++sd)
-                    if (has(sd, k, i)) {
-                        rloc = fmax(rloc, fabs(TT(sd, e) - bslack(sd, k, i, v)));
-                        muloc = fma(LAM(sd, e), TT(sd, e), muloc);
-                    }
-            }
-            const double rinf = wave_max(rloc);
-            const double mu = n_rows > 0.0 ? wave_sum(muloc) / n_rows : 0.0;
-            if (rinf <= tol_res && mu <= tol_mu) {
-                ok = true;
-                break;
-            }
-            if (it >= IPM_MAX_ITER || !(rinf < 1e300)) break;
-            ++n_it;
-            ph(0);
-            double sigma_mu = 0.0, alpha = 1.0;
-            bool fail = false;
-            for (int pass = 0; pass < 2; ++pass) {
-                // barrier diagonal + modified gradient: rt = rg everywhere, corrected on the bounded rows
-                batched_pass<8>(ne, lane, [&](int e) { return rg[e]; },
-                                [&](int e, double v) {
-                                    rt[e] = v;
-                                    if (pass == 0) Dg[e] = 0.0;
-                                });
-                wave_sync();
-                for (int r_ = lane; r_ < nrows; r_ += NT) {
-                    int k, i;
-                    row_of(r_, k, i);
-                    const int e = k * NW + i;
-                    double dg = 0.0, er = 0.0;
-                    const double v = vc(k, i) + dvc(dx, du, k, i);
-                    for (int sd = 0; sd < 2; ++sd)
-                        if (has(sd, k, i)) {
-                            const double l1 = LAM(sd, e), t1 = TT(sd, e);
-                            const double rd1 = t1 - bslack(sd, k, i, v);
-                            const double rm = fma(l1, t1, pass ? AFF(sd, e) - sigma_mu : 0.0);
-                            dg += l1 / t1;
-                            er += (sd ? -1.0 : 1.0) * (rm - l1 * rd1) / t1;
-                        }
-                    if (pass == 0) Dg[e] = dg;
-                    rt[e] = rg[e] + er;
-                }
-                wave_sync();
-                ph(1);
-                if (pass == 0) {
-                    if (!factor_call<HS>(ctx(), hs.hex_offset(), rt.off, rb.off)) fail = true;
-                    ph(2);
-                } else {
-                    backward_vec_call(ctx(), rt.off);
-                    ph(3);
-                }
-                forward_call(ctx(), rb.off);
-                ph(4);
-                double amax = 1.0, muaff = 0.0;
-                for (int r_ = lane; r_ < nrows; r_ += NT) {
-                    int k, i;
-                    row_of(r_, k, i);
-                    const int e = k * NW + i;
-                    const double v = vc(k, i) + dvc(dx, du, k, i), dv = dvc(Dx, Du, k, i);
-                    for (int sd = 0; sd < 2; ++sd)
-                        if (has(sd, k, i)) {
-                            const double l1 = LAM(sd, e), t1 = TT(sd, e);
-                            const double rd1 = t1 - bslack(sd, k, i, v);
-                            const double rm = fma(l1, t1, pass ? AFF(sd, e) - sigma_mu : 0.0);
-                            const double dt1 = -rd1 + (sd ? -dv : dv);
-                            const double dl1 = (-rm - l1 * dt1) / t1;
-                            if (dl1 < 0.0) amax = fmin(amax, -l1 / dl1);
-                            if (dt1 < 0.0) amax = fmin(amax, -t1 / dt1);
-                        }
-                }
-                amax = -wave_max(-amax);
-                if (pass == 0) {
-                    for (int r_ = lane; r_ < nrows; r_ += NT) {
-                        int k, i;
-                        row_of(r_, k, i);
-                        const int e = k * NW + i;
-                        const double v = vc(k, i) + dvc(dx, du, k, i), dv = dvc(Dx, Du, k, i);
-                        for (int sd = 0; sd < 2; ++sd)
-                            if (has(sd, k, i)) {
-                                const double l1 = LAM(sd, e), t1 = TT(sd, e);
-                                const double rd1 = t1 - bslack(sd, k, i, v);
-                                const double dt1 = -rd1 + (sd ? -dv : dv);
-                                const double dl1 = (-l1 * t1 - l1 * dt1) / t1;
-                                muaff = fma(fma(amax, dl1, l1), fma(amax, dt1, t1), muaff);
-                                AFF(sd, e) = dl1 * dt1;
-                            }
-                    }
-                    const double mu_aff = n_rows > 0.0 ? wave_sum(muaff) / n_rows : 0.0;
-                    const double ratio = mu > 0.0 ? mu_aff / mu : 0.0;
-                    sigma_mu = ratio * ratio * ratio * mu;
-                    wave_sync();
-                } else
-                    alpha = fmin(1.0, fmax(IPM_FRAC, frac_fixed ? 0.0 : 1.0 - mu) * amax);   // fraction to the boundary -> 1 as mu -> 0
-            }
-            ph(5);
-            if (fail) break;
-            for (int r_ = lane; r_ < nrows; r_ += NT) {
-                int k, i;
-                row_of(r_, k, i);
-                const int e = k * NW + i;
-                const double v = vc(k, i) + dvc(dx, du, k, i), dv = dvc(Dx, Du, k, i);
-                for (int sd = 0; sd < 2; ++sd)
-                    if (has(sd, k, i)) {
-                        const double l1 = LAM(sd, e), t1 = TT(sd, e);
-                        const double rd1 = t1 - bslack(sd, k, i, v);
-                        const double rm = fma(l1, t1, AFF(sd, e) - sigma_mu);
-                        const double dt1 = -rd1 + (sd ? -dv : dv);
-                        const double dl1 = (-rm - l1 * dt1) / t1;
-                        LAM(sd, e) = fma(alpha, dl1, l1);
-                        TT(sd, e) = fma(alpha, dt1, t1);
-                    }
-            }
-            wave_sync();
-            batched_pass<8>((N + 1) * NX, lane, [&](int e) { return Pair2{Dx[e], dx[e]}; },
-                            [&](int e, const Pair2 &v) { dx[e] = fma(alpha, v.a, v.b); });
-            stepped = true;
-            batched_pass<2>(N * NU, lane, [&](int e) { return Pair2{Du[e], du[e]}; },
-                            [&](int e, const Pair2 &v) { du[e] = fma(alpha, v.a, v.b); });
-            {
-                const double om = 1.0 - alpha;
-                batched_pass<8>(ne, lane, [&](int e) { return rg[e]; }, [&](int e, double v) { rg[e] = om * v; });
-                batched_pass<8>(N * NX, lane, [&](int e) { return rb[e]; }, [&](int e, double v) { rb[e] = om * v; });
-                rlin *= om;
-            }
-            wave_sync();
-        }
         if (stepped) costate_call(ctx());      // nuq of the point the iteration ended at (no iteration: the warm multipliers stand)
         return ok;
     }
@@ -1825,12 +1731,11 @@ struct ChainSolver {
     // half of the registers its body uses — 29 KB per wavefront for the factor sweep, ~20 KB for a vector sweep, through scratch, i.e.
     // HBM traffic at 1024 resident wavefronts: ~1.9 GB written and read back per step of 1024 solves at n_mass 5 with four calls per
     // interior-point iteration.  The time is the same either way (measured: 8.68 vs 8.69 ms), the bytes are not.
-    template <class HS>
-    __device__ MPCRL_PHASE_FN static bool pred_call(Ctx c, unsigned hex_off, unsigned g_off, unsigned bb_off) {
+    __device__ MPCRL_PHASE_FN static bool pred_call(Ctx c, unsigned g_off, unsigned bb_off) {
         ChainSolver S = from_ctx(c);
-        HS hs;
-        hs.init(S, hex_off);
-        const bool ok = S.template factor2<HS, false>(hs, S.arr(g_off), S.arr(bb_off));
+        HessConst<M> hs;
+        hs.init(S, 0u);
+        const bool ok = S.template factor2<HessConst<M>, false>(hs, S.arr(g_off), S.arr(bb_off));
         S.forward2(S.arr(bb_off));
         return ok;
     }

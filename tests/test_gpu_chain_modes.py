@@ -1,6 +1,7 @@
 """The chain-of-masses kernels in the modes and at the horizons the rest of the suite runs on the small models only: Q mode (u_0
-pinned), full-SQP warm starts, bounds changed after creation (a state row among them), the status codes, and horizons from N = 1
-over the 16-stage batches of the corrector's matrix-core pass.
+pinned), full-SQP warm starts, bounds changed after creation (a state row among them), the status codes, horizons from N = 1
+over the 16-stage batches of the corrector's matrix-core pass, and the two stores of the interior point's bound rows on both sides
+of their 128-row switch.
 
 Reference: the C++ CPU port (oracle/cpu) on the same inputs; the autograd mirror of the reference's NLP (oracle/from_iterate.certify)
 is the independent leg for the two things the port itself is held to nowhere else, Q mode and a state bound (the same two
@@ -557,3 +558,68 @@ def test_mirror_active_state_bound(oracle_port):
     assert err < RTOL, largest_error.last
     wrong = oracle_port.solve(with_state_bound(c.P, ix, lo + 1e-3), c.x0, tol=c.tol)
     assert largest_error(have, {"dV": wrong.dV[rows], "dpi": wrong.dpi[rows], "L": wrong.V[rows]}, fields=("dV", "dpi", "L")) > RTOL
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 6. the two row stores of the interior point at their switch
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Up to 128 bound rows (two per lane) stay in registers, more go through the workspace.  n_mass 3, N = 11 with bounds on the three
+# controls and all nine states at the interior stages has n0 + 10 * 12 + ne rows: n0 = 3 (V mode) or 0 (Q mode: u_0 is pinned) at
+# stage 0, ne bounded states at the terminal stage.  128 rows: the register store with the second row of lane 63 in use; 129: the
+# workspace store.  The state bounds are loose (+-LOOSE: rows of the interior point that never bind) but for one lower bound on the
+# end point's x position, which is active on part of the batch.
+EDGE = dict(n_mass=3, N=11, B=4, seed=SEED)
+LOOSE = 1e3
+EDGE_CASES = [(False, 5, 128), (False, 6, 129), (True, 8, 128), (True, 9, 129)]
+
+
+def with_loose_state_bounds(P_sb, ne):
+    """P_sb = with_state_bound(...): every other state bounded by +-LOOSE at stages 1 .. N - 1, the first ne states at stage N."""
+    nx = P_sb.nx
+    lbx = np.full(nx, -LOOSE)
+    lbx[int(P_sb.idxbx[0])] = float(P_sb.lbx[0])
+    ubx = np.full(nx, LOOSE)
+    return dataclasses.replace(P_sb, idxbx=np.arange(nx), lbx=lbx, ubx=ubx, idxbx_e=np.arange(ne), lbx_e=lbx[:ne], ubx_e=ubx[:ne])
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(port, qmode, ne):
+    """(the bounded problem, the pinned u_0 or None, the port's solution, the port's solution with the active bound moved by 1e-3)"""
+    c = case(port, *[EDGE[k] for k in ("n_mass", "N", "B", "seed")])
+    ix = 3 * (EDGE["n_mass"] - 2)
+    u0, free = None, c.ref_v
+    if qmode:      # x_1[ix] = x_0[ix] + dT u_0[0] is pinned with u_0: on the feasible side of a bound below x_0[ix]
+        u0 = c.u0.copy()
+        u0[:, 0] = np.abs(u0[:, 0])
+        free = port.solve(c.P, c.x0, u0fix=u0)
+        assert np.all(free.status == 0)
+    lo = state_bound_level(c.ocp, free, ix)
+    P = with_loose_state_bounds(with_state_bound(c.P, ix, lo), ne)
+    wrong = with_loose_state_bounds(with_state_bound(c.P, ix, lo + 1e-3), ne)
+    return c, ix, P, u0, port.solve(P, c.x0, u0fix=u0), port.solve(wrong, c.x0, u0fix=u0)
+
+
+@pytest.mark.parametrize("qmode,ne,rows", EDGE_CASES)
+def test_row_store_switch(oracle_port, qmode, ne, rows):
+    from mpc4rl_amd import MPCBatch, _lib
+    c, ix, P, u0, ref, wrong = edge_case(oracle_port, qmode, ne)
+    nx, nu, N, B = c.ocp.nx, c.ocp.nu, EDGE["N"], EDGE["B"]
+    assert (0 if qmode else nu) + (N - 1) * (nu + nx) + ne == rows
+    assert np.abs(ref.X).max() < 1e-2 * LOOSE < 1e-4 * _lib.NO_BOUND
+    mpc = MPCBatch(c.ocp, B)
+    lbe, ube = np.full(nx, -1e30), np.full(nx, 1e30)
+    lbe[:ne], ube[:ne] = P.lbx_e, P.ubx_e
+    mpc.set_bounds(_lib.BOUNDS_STAGE, np.concatenate([-np.ones(nu), P.lbx]), np.concatenate([np.ones(nu), P.ubx]))
+    mpc.set_bounds(_lib.BOUNDS_TERMINAL, lbe, ube)
+    r = mpc.solve(c.x0, u0, sens_v=True, sens_pi=True, cold=True)
+    got = outputs(mpc, r)
+    same_statuses(got, ref)
+    lam, lam_ref = got["BND"][:, 0, :, nu + ix], ref.BND[:, 0, :, nu + ix]
+    assert (lam.max(1) > 1e-3).sum() >= 2 and (lam_ref.max(1) > 1e-3).sum() >= 2, (lam.max(1), lam_ref.max(1))      # the active row
+    others = nu + np.flatnonzero(np.arange(nx) != ix)      # the loose rows: slack ~LOOSE, multiplier = (barrier parameter) / slack
+    assert max(np.abs(got["BND"][:, :2][..., others]).max(), np.abs(ref.BND[:, :2][..., others]).max()) < 1e-6
+    assert got["X"][:, 1:, ix].min() > float(P.lbx[ix]) - 1e-7
+    err = largest_error(got, ref)
+    report(f"{rows} bound rows, {'Q' if qmode else 'V'} mode", err)
+    assert err < RTOL, largest_error.last
+    assert largest_error(got, wrong) > RTOL      # negative control: the active bound moved by 1e-3
