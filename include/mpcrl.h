@@ -40,6 +40,9 @@
  *   mpc.get_action + env.step + replay_buffer.add of the       mpcrl_qlearning_linear_collect  (PPO on the same plant:
  *   linear system's Q-learning roll-out                          mpcrl_ppo_linear_collect)
  *     rlmpc/examples/linear_system_mpc_qlearning.py:160-172
+ *   the chain of masses as a plant (f_expl + RK4, the model's     mpcrl_env_chain_step, and the roll-out step of its Q-learning
+ *   own map at the plant's parameters, with a disturbance)       loop around it: mpcrl_qlearning_chain_collect
+ *     rlmpc/mpc/chain_mass/ocp_utils.py:76-130
  *
  * Conventions
  *   - plain C, no torch types.  Every array argument of mpcrl_solve / *_iterate / mpcrl_reset /
@@ -96,7 +99,8 @@ extern "C" {
  *        mpcrl_ppo_surrogate_grad / mpcrl_ppo_surrogate_workspace_bytes; mpcrl_ppo_log_std_apply (batched PPO with the MPC as
  *        Gaussian actor, cartpole); round 8: mpcrl_value_forward; mpcrl_value_mse_grad / mpcrl_value_workspace_bytes (PPO's value
  *        function as library kernels); mpcrl_qlearning_linear_collect; mpcrl_ppo_linear_collect (the linear system's Q-learning and
- *        PPO roll-out steps) */
+ *        PPO roll-out steps); mpcrl_env_chain_step; mpcrl_qlearning_chain_collect (the chain of masses as a plant and its Q-learning
+ *        roll-out step) */
 #define MPCRL_ABI_VERSION 132
 
 enum { MPCRL_MODEL_CARTPOLE = 0, MPCRL_MODEL_LINEAR = 1, MPCRL_MODEL_CHAIN = 2 };
@@ -500,6 +504,40 @@ int mpcrl_ppo_linear_collect(const double *par, int E, int T, int t, double *sta
                              double reward_scale, int64_t episode_length, const double *reset_state, double *OBS, double *ACT, double *LOGP,
                              double *VAL, double *REW, double *NEXT, uint8_t *TERM, uint8_t *DONE, uint8_t *OK, double *obs, int32_t *ended,
                              void *stream);
+
+/* Added under ABI 132.  The chain of masses as a plant (chain_env_kernel.hpp; mpc4rl_amd/envs.py BatchedChainMassEnv), B environments in
+ * one launch, one lane per environment, all arithmetic fp64: the reference's chain ODE (rlmpc/mpc/chain_mass/ocp_utils.py:76-130)
+ * integrated as the model integrates it, rk_steps RK4 steps of Ts / rk_steps (ocp_utils.py:42-56,132), at the environment's OWN parameters.
+ * n_mass in 3..7, nx = 3 (2 (n_mass - 2) + 1), M = n_mass - 2 free masses.  p: DEVICE pointer in the OCP's layout (m, D, L, C, Q, R, w;
+ * n_p doubles); p_stride = 0: one vector shared by all environments, p_stride = n_p: one row per environment.  x_ss [nx]: DEVICE pointer,
+ * the cost's reference state.  state [B][nx] is updated in place; action [B][3] is used as given (the caller clips); wn [B][3 M]:
+ * standard-normal draws of the caller, w_std * wn is added to the free masses' accelerations in every ODE evaluation of the step (the
+ * ODE is additive in w: this is p's w + noise); wn may be NULL if and only if w_std == 0 (then it is not read).
+ *   cost [B] = 1/2 (s - x_ss)' Q (s - x_ss) + 1/2 a' R a  of the state BEFORE the step with the environment's own Q and R: l(s, a), the
+ *   quantity the MPC's Q(s, a) models (mpcrl_env_cartpole_step and mpcrl_env_linear_step report the cost of the NEW state).
+ * obs [B][nx] (may be NULL) = the new state, float if obs_f32 != 0, else double.  MPCRL_E_ARG: n_mass outside 3..7, rk_steps < 1,
+ * Ts <= 0, a p_stride other than 0 or n_p, B < 0, a NULL p, x_ss, state, action or cost, a NULL wn with w_std != 0.  B = 0: nothing is
+ * launched.  Handle-less (launched on the device that owns `state`), asynchronous on `stream`, capture-safe. */
+int mpcrl_env_chain_step(int n_mass, double Ts, int rk_steps, const double *p, int64_t p_stride, const double *x_ss, int B, double *state,
+                         const double *action, const double *wn, double w_std, void *obs, int obs_f32, double *cost, void *stream);
+
+/* Added under ABI 132.  One roll-out step of the chain's Q-learning loop after the policy's solve, one launch
+ * (mpc4rl_amd/qlearning_chain.py): mpcrl_qlearning_linear_collect's shape with three controls.  n_mass ... x_ss, w_std: the plant as in
+ * mpcrl_env_chain_step (the environment step is that call's device function: the same bits).  u0 [E][3], status [E]: the solve;
+ * eps [T][E][3] float standard-normal draws and wn [T][E][3 M] (NULL iff w_std == 0), row r = row[env] of both read; lo, hi: 3 HOST
+ * doubles each (lbu, ubu), lo_j < hi_j.
+ *   good = status in {0, 2} and all three u0 finite;   a_j = good ? u0_j : 0;
+ *   sigma > 0: a_j = clip(a_j + (double)(float(sigma) eps_j), lo_j, hi_j)   (the float product is rounded first, then the fp64 sum and the
+ *   clip; sigma = 0: a is u0 itself, beyond the bounds too; sigma is held as a float, so a positive double that rounds to 0.0f is 0);
+ *   the environment is stepped with a and row r of wn.
+ * Row r of the episode table: S [T][E][nx] = s_r (the state BEFORE the step), A [T][E][3] = a, C [T][E] = l(s_r, a).  state is updated in
+ * place, obs [E][nx] = the new state (the next solve's x0), cold [E] int32 = 0, row [E] int32 advances by one; an environment whose row is
+ * outside [0, T) is left alone: nothing is written, nothing is stepped.  The plant never terminates: there is no liveness.
+ * MPCRL_E_ARG: the plant's cases, E < 0, T < 1, a NULL pointer, lo_j >= hi_j, a negative or non-finite sigma.  E = 0: nothing is launched. */
+int mpcrl_qlearning_chain_collect(int n_mass, double Ts, int rk_steps, const double *p, int64_t p_stride, const double *x_ss, double w_std, int E,
+                                  int T, double *state, const double *u0, const int32_t *status, const float *eps, const double *wn,
+                                  const double *lo, const double *hi, double sigma, double *obs, int32_t *row, int32_t *cold, double *S, double *A,
+                                  double *C, void *stream);
 
 /* Bytes of device memory held by the handle; library version (MPCRL_ABI_VERSION of the header it was built from). */
 int64_t mpcrl_workspace_bytes(mpcrl_handle h);

@@ -34,7 +34,8 @@ EXPORTS = ["mpcrl_create", "mpcrl_destroy", "mpcrl_set_theta", "mpcrl_set_gamma"
            "mpcrl_solve", "mpcrl_get_iterate", "mpcrl_set_iterate", "mpcrl_get_iterate_rows", "mpcrl_set_iterate_rows", "mpcrl_get_lagrangian", "mpcrl_weighted_grad_sum", "mpcrl_env_cartpole_step", "mpcrl_env_cartpole_reset", "mpcrl_env_linear_step", "mpcrl_policy_action", "mpcrl_critic_workspace_bytes", "mpcrl_critic_td_grad", "mpcrl_critic_dq_da", "mpcrl_replay_sample", "mpcrl_dpg_workspace_bytes", "mpcrl_dpg_grad", "mpcrl_td3_cartpole_collect", "mpcrl_td3_policy_post", "mpcrl_qlearning_cartpole_collect", "mpcrl_qlearning_td_workspace_bytes", "mpcrl_qlearning_td_grad", "mpcrl_qlearning_apply", "mpcrl_auto_order", "mpcrl_query_time_sliced", "mpcrl_set_launch_mode", "mpcrl_get_launch_times", "mpcrl_workspace_bytes", "mpcrl_version",
            "mpcrl_ppo_cartpole_collect", "mpcrl_ppo_gae", "mpcrl_ppo_surrogate_workspace_bytes", "mpcrl_ppo_surrogate_grad", "mpcrl_ppo_log_std_apply",
            "mpcrl_value_forward", "mpcrl_value_workspace_bytes", "mpcrl_value_mse_grad",
-           "mpcrl_qlearning_linear_collect", "mpcrl_ppo_linear_collect"]
+           "mpcrl_qlearning_linear_collect", "mpcrl_ppo_linear_collect",
+           "mpcrl_env_chain_step", "mpcrl_qlearning_chain_collect"]
 
 _lib = None
 
@@ -112,6 +113,9 @@ def load():
                                                    vp, vp]
     lib.mpcrl_ppo_linear_collect.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double,
                                              C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mpcrl_env_chain_step.argtypes = [C.c_int, C.c_double, C.c_int, vp, C.c_int64, vp, C.c_int, vp, vp, vp, C.c_double, vp, C.c_int, vp, vp]
+    lib.mpcrl_qlearning_chain_collect.argtypes = [C.c_int, C.c_double, C.c_int, vp, C.c_int64, vp, C.c_double, C.c_int, C.c_int, vp, vp, vp, vp, vp,
+                                                  _dp, _dp, C.c_double, vp, vp, vp, vp, vp, vp, vp]
     lib.mpcrl_workspace_bytes.argtypes = [vp]
     lib.mpcrl_workspace_bytes.restype = C.c_int64
     for name in EXPORTS:

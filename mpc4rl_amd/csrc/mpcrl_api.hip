@@ -23,6 +23,7 @@
 #include "ppo_kernel.hpp"
 #include "value_kernel.hpp"
 #include "linear_loop_kernel.hpp"
+#include "chain_env_kernel.hpp"
 
 using namespace mpcrl;
 
@@ -77,6 +78,26 @@ LinearEnvPar linear_env_par(const double *par) {
     p.low[0] = par[8], p.low[1] = par[9], p.high[0] = par[10], p.high[1] = par[11];
     return p;
 }
+
+// The plant arguments of mpcrl_env_chain_step / mpcrl_qlearning_chain_collect, checked: false = MPCRL_E_ARG.  wn may be NULL only without
+// a disturbance.
+bool chain_env_par(int n_mass, double Ts, int rk_steps, const double *p, int64_t p_stride, const double *x_ss, const double *wn, double w_std,
+                   ChainEnvPar &e) {
+    if (n_mass < 3 || n_mass > 7 || rk_steps < 1 || !(Ts > 0.0) || !p || !x_ss || !(w_std == w_std) || (w_std != 0.0 && !wn)) return false;
+    const int64_t nl = n_mass - 1, m = n_mass - 2, nx = (2 * m + 1) * 3, n_p = 10 * nl + nx * nx + 9 + 3 * m;      // ChainDev<n_mass>::NP
+    if (p_stride != 0 && p_stride != n_p) return false;
+    e.p = p, e.p_stride = p_stride, e.x_ss = x_ss, e.wn = w_std != 0.0 ? wn : nullptr, e.h = Ts / rk_steps, e.w_std = w_std, e.rk_steps = rk_steps;
+    return true;
+}
+// one instantiation per chain size (the host switches on n_mass)
+#define CHAIN_ENV_SWITCH(n_mass, LAUNCH) \
+    switch (n_mass) {                    \
+        case 3: LAUNCH(3); break;        \
+        case 4: LAUNCH(4); break;        \
+        case 5: LAUNCH(5); break;        \
+        case 6: LAUNCH(6); break;        \
+        default: LAUNCH(7); break;       \
+    }
 
 // The workspace of a kernel that hands off to its last workgroup (batch_sum.hpp): the ticket, then one row of `cols` doubles per
 // workgroup, a workgroup taking `rows_per_block` of the `rows` terms.
@@ -961,6 +982,43 @@ int mpcrl_ppo_linear_collect(const double *par, int E, int T, int t, double *sta
     env.par = linear_env_par(par), env.episode_length = episode_length, env.reset0 = reset_state[0], env.reset1 = reset_state[1];
     return launch_ppo_collect(env, E, T, t, state, steps, u0, status, eps, u01, value, log_std, lo, hi, reward_scale, OBS, ACT, LOGP, VAL, REW, NEXT,
                               TERM, DONE, OK, obs, ended, stream);
+}
+
+int mpcrl_env_chain_step(int n_mass, double Ts, int rk_steps, const double *p, int64_t p_stride, const double *x_ss, int B, double *state,
+                         const double *action, const double *wn, double w_std, void *obs, int obs_f32, double *cost, void *stream) {
+    ChainEnvPar e;
+    if (!chain_env_par(n_mass, Ts, rk_steps, p, p_stride, x_ss, wn, w_std, e) || B < 0 || !state || !action || !cost) return MPCRL_E_ARG;
+    if (B == 0) return 0;
+    ON_DEVICE_OF(state);
+#define LAUNCH(NM) \
+    hipLaunchKernelGGL(env_chain_step_kernel<NM>, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, e, B, state, action, obs, obs_f32, cost)
+    CHAIN_ENV_SWITCH(n_mass, LAUNCH)
+#undef LAUNCH
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int mpcrl_qlearning_chain_collect(int n_mass, double Ts, int rk_steps, const double *p, int64_t p_stride, const double *x_ss, double w_std, int E,
+                                  int T, double *state, const double *u0, const int32_t *status, const float *eps, const double *wn,
+                                  const double *lo, const double *hi, double sigma, double *obs, int32_t *row, int32_t *cold, double *S, double *A,
+                                  double *C, void *stream) {
+    QlChainCollectArgs a;
+    if (!chain_env_par(n_mass, Ts, rk_steps, p, p_stride, x_ss, wn, w_std, a.env) || E < 0 || T < 1 || !state || !u0 || !status || !eps || !lo ||
+        !hi || !obs || !row || !cold || !S || !A || !C || !(sigma >= 0.0) || !std::isfinite(sigma))
+        return MPCRL_E_ARG;
+    for (int j = 0; j < 3; ++j) {
+        if (!(hi[j] > lo[j])) return MPCRL_E_ARG;
+        a.lo[j] = lo[j], a.hi[j] = hi[j];
+    }
+    if (E == 0) return 0;
+    ON_DEVICE_OF(state);
+    a.E = E, a.T = T, a.state = state, a.u0 = u0, a.status = (const int *)status, a.eps = eps, a.sigma = (float)sigma;
+    a.obs = obs, a.row = row, a.cold = cold, a.S = S, a.A = A, a.C = C;
+#define LAUNCH(NM) hipLaunchKernelGGL(qlearning_chain_collect_kernel<NM>, dim3((E + 63) / 64), dim3(64), 0, (hipStream_t)stream, a)
+    CHAIN_ENV_SWITCH(n_mass, LAUNCH)
+#undef LAUNCH
+    HIP_OK(hipGetLastError());
+    return 0;
 }
 
 int mpcrl_env_cartpole_reset(int B, double *state, int64_t *steps, const uint8_t *mask, const double *u01, void *obs, int obs_f32,

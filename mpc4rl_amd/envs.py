@@ -7,6 +7,9 @@ Restates (no gymnasium dependency, tensors in / tensors out, B environments per 
       terminated when |x| < 0.1, |x_dot| < 0.1, |theta| < 2 deg, |theta_dot| < 0.1 all hold (84-103)
   * LinearSystemEnv                rlmpc/gym/linear_system/environment.py:6-66
       s+ = A s + B a + [U(lb_noise, ub_noise), 0]; reset to [0.5, 0.5]; cost = 1/2 s's + 1/2 a'a + 100 per violated side
+  * the chain of masses                rlmpc/mpc/chain_mass/ocp_utils.py:76-130 (the reference has no gym environment for it)
+      the model's own map (RK4 on the chain ODE) at the PLANT's parameter vector, plus a Gaussian disturbance on the free masses'
+      accelerations; reset to the OCP's x0 with perturbed velocities; cost = l(s, a) of the state BEFORE the step; never terminates
 The STATE is always float64 (the reference's numpy state); observations are returned in ``dtype`` — float64 by default (they feed the
 fp64 solve directly), ``dtype=torch.float32`` for what the reference's gymnasium envs return (``np.array(self.state, dtype=np.float32)``,
 continuous_cartpole/environment.py:166,186).  On a GPU every call is ONE launch of the library's environment kernels
@@ -182,3 +185,85 @@ class BatchedLinearSystemEnv:
         reward = self.cost(self.state, a)
         done = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)
         return self.state.to(self.dtype, copy=True), reward, done, done.clone()
+
+
+def _chain_dims(ocp):
+    """(n_mass, Ts, rk_steps) of a chain_mass_ocp(...)."""
+    from . import _lib
+    if getattr(ocp, "model", None) != _lib.MODEL_CHAIN or ocp.nu != 3 or ocp.nx % 3 != 0 or (ocp.nx // 3) % 2 != 1:
+        raise ValueError("the chain-of-masses OCP is needed (chain_mass_ocp())")
+    return (ocp.nx // 3 - 1) // 2 + 2, float(ocp.dT), int(ocp.rk_steps)
+
+
+class BatchedChainMassEnv:
+    """The chain of masses as a plant: E chains stepped by the model's own map, ``rk_steps`` RK4 steps of ``Ts / rk_steps`` on the
+    reference's chain ODE (rlmpc/mpc/chain_mass/ocp_utils.py:76-130), at the environment's OWN parameters ``p`` — a device float64 tensor
+    in the OCP's layout (``chain_param_layout``), [n_p] shared or [E, n_p] one row per environment, default ``ocp.p0``; an in-place edit of
+    ``env.p`` is honoured on the next step — with ``w_std * N(0, 1)`` added to the free masses' accelerations over the step (drawn from
+    ``env.gen``; nothing is drawn when ``w_std`` is 0).  ``ocp`` (a ``chain_mass_ocp(...)``) supplies n_mass, Ts, rk_steps, the cost's
+    reference ``x_ss = ocp.consts`` and ``x0``.
+
+    ``reset()`` / ``reset_where(mask)``: ``ocp.x0`` plus ``vel_std * N(0, 1)`` on the 3 M velocity entries, in torch (the plant never ends
+    an episode, so there is no reset kernel).  ``step(action [E, 3])`` uses the action as given (the caller clips) and returns
+    (obs, cost, terminated, truncated), the last two all False.  UNLIKE the cartpole and the linear system, whose reward / cost is that of
+    the NEW state, the cost here is l(s, a) = 1/2 (s - x_ss)' Q (s - x_ss) + 1/2 a' R a of the state BEFORE the step with the
+    environment's own Q and R: the quantity the MPC's Q(s, a) models.  On a GPU a step is ONE launch of mpcrl_env_chain_step
+    (csrc/chain_env_kernel.hpp); on the CPU it is ``chain_env_step_terms`` (qlearning_chain.py), the same map in torch."""
+
+    def __init__(self, num_envs: int, ocp, device="cpu", p=None, w_std: float = 0.0, vel_std: float = 1e-2, seed: int = 0,
+                 dtype=torch.float64):
+        self.num_envs, self.device, self.dtype = num_envs, torch.device(device), dtype
+        if dtype not in (torch.float64, torch.float32):
+            raise ValueError("observations are float64 or float32")
+        self.n_mass, self.Ts, self.rk_steps = _chain_dims(ocp)
+        self.M, self.nx, self.n_p = self.n_mass - 2, ocp.nx, ocp.n_p
+        if not (math.isfinite(w_std) and math.isfinite(vel_std)):
+            raise ValueError("w_std and vel_std must be finite")
+        self.w_std, self.vel_std = float(w_std), float(vel_std)
+        kw = dict(dtype=torch.float64, device=self.device)
+        self.p = torch.as_tensor(ocp.p0 if p is None else p, **kw).clone().contiguous()
+        if self.p.shape not in ((self.n_p,), (num_envs, self.n_p)):
+            raise ValueError(f"p must be [{self.n_p}] or [{num_envs}, {self.n_p}]")
+        self.x_ss = torch.as_tensor(ocp.consts, **kw).clone().contiguous()
+        self.x0 = torch.as_tensor(ocp.x0, **kw).clone()
+        self.gen = torch.Generator(device=self.device).manual_seed(seed)
+        self.state = self.x0.repeat(num_envs, 1)                                        # never rebound: graphs hold its address
+
+    def _fresh(self) -> torch.Tensor:
+        s = self.x0.repeat(self.num_envs, 1)
+        s[:, self.nx - 3 * self.M:] += self.vel_std * torch.randn(self.num_envs, 3 * self.M, generator=self.gen, dtype=torch.float64, device=self.device)
+        return s
+
+    def reset(self) -> torch.Tensor:
+        self.state.copy_(self._fresh())
+        return self.state.to(self.dtype, copy=True)
+
+    def reset_where(self, mask: torch.Tensor) -> torch.Tensor:
+        """reset for the masked environments without a host synchronisation: E x 3 M normals are drawn and the masked environments take
+        theirs.  Returns the observation of every environment after the reset."""
+        self.state.copy_(torch.where(mask.to(self.device).bool()[:, None], self._fresh(), self.state))
+        return self.state.to(self.dtype, copy=True)
+
+    def step(self, action: torch.Tensor):
+        from .qlearning_chain import chain_env_step_terms
+        E = self.num_envs
+        a = action.to(dtype=torch.float64, device=self.device).reshape(E, 3).contiguous()
+        wn = torch.randn(E, 3 * self.M, generator=self.gen, dtype=torch.float64, device=self.device) if self.w_std != 0.0 else None
+        done = torch.zeros(E, dtype=torch.bool, device=self.device)
+        if self.device.type == "cuda":   # one launch through the C ABI (csrc/chain_env_kernel.hpp)
+            from . import _lib
+            from .batch import _ptr
+            if not (self.p.is_contiguous() and self.p.dtype == torch.float64 and self.p.device.type == "cuda"):
+                raise ValueError("env.p must stay a contiguous float64 tensor on the environment's device")
+            obs = torch.empty(E, self.nx, dtype=self.dtype, device=self.device)
+            cost = torch.empty(E, dtype=torch.float64, device=self.device)
+            rc = _lib.load().mpcrl_env_chain_step(self.n_mass, self.Ts, self.rk_steps, _ptr(self.p), 0 if self.p.dim() == 1 else self.n_p,
+                                                  _ptr(self.x_ss), E, _ptr(self.state), _ptr(a), _ptr(wn), self.w_std, _ptr(obs),
+                                                  1 if self.dtype == torch.float32 else 0, _ptr(cost),
+                                                  torch.cuda.current_stream(self.device).cuda_stream)
+            if rc != 0:
+                raise RuntimeError(f"mpcrl_env_chain_step failed with code {rc}")
+            return obs, cost, done, done.clone()
+        new, cost = chain_env_step_terms((self.n_mass, self.Ts, self.rk_steps), self.p, self.x_ss, self.state, a, wn, self.w_std)
+        self.state.copy_(new)
+        return self.state.to(self.dtype, copy=True), cost, done, done.clone()

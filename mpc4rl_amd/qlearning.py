@@ -11,7 +11,7 @@ With several ranks every rank learns from its own environments and the parameter
 (mpc4rl_amd.distributed), so all ranks hold identical parameters.
 
 ``BatchedQLearning`` is that loop in torch for any model.  ``DeviceQLearning`` is the core of its device forms (``CartpoleQLearning``,
-``LinearQLearning``): everything of an episode but the plant's own roll-out kernel and tables.
+``LinearQLearning``, ``ChainQLearning``): everything of an episode but the plant's own roll-out kernel and tables.
 """
 from __future__ import annotations
 
@@ -99,11 +99,16 @@ class DeviceQLearning:
     sum lr td, count] of distributed.mean_update).  With several ranks only that message is all-reduced; then mpcrl_qlearning_apply
     takes the mean and steps theta.
 
-    A plant's class sets ``NX`` and ``_COLLECT``, checks its OCP and environment, allocates ``live`` [T, E] (and what else its collect
-    kernel needs) after this constructor, and defines ``_collect(r)`` (the collect launch after the roll-out solve r; returns its
-    status), ``_stats()`` and, where the environment carries more than its state from step to step, ``_env_carried()``."""
+    A plant's class sets ``NX``, ``_COLLECT`` and, with more than one control, ``NU``, checks its OCP and environment, allocates
+    ``live`` [T, E] (and what else its collect kernel needs) after this constructor, and defines ``_collect(r)`` (the collect launch
+    after the roll-out solve r; returns its status), ``_stats()``, where the environment carries more than its state from step to step
+    ``_env_carried()``, and, where the zero state is no state of the plant, ``_initial_obs()``.
+
+    ``NU`` = 1: ``A`` and ``eps`` are [T, E] and the control bounds the floats ``lo``, ``hi``.  ``NU`` > 1: ``A`` and ``eps`` are
+    [T, E, NU] and the bounds the host arrays ``lo_v``, ``hi_v`` (ctypes doubles, what a collect export takes)."""
 
     NX: int = 0             # the state's width
+    NU: int = 1             # the number of controls
     _COLLECT: str = ""      # the library's collect entry point (for error messages)
 
     def __init__(self, ocp, env, episode_length: int, lr: float, gamma: float, noise_scale: float, seed: int, device, group,
@@ -126,7 +131,10 @@ class DeviceQLearning:
             raise ValueError("the environment must live on the learner's device (its state is updated in place by the library)")
         self.ocp, self.env, self.T, self.lr, self.gamma, self.noise_scale = ocp, env, episode_length, float(lr), float(gamma), float(noise_scale)
         self.E, self.device, self.group = env.num_envs, dev, group
-        T, E, NX = self.T, self.E, self.NX
+        T, E, NX, NU = self.T, self.E, self.NX, self.NU
+        if ocp.nu != NU:
+            raise ValueError(f"{name} is written for {NU} control(s), the OCP has {ocp.nu}")
+        wide = () if NU == 1 else (NU,)      # one control: the tables keep no control axis
         self.rollout_mpc = MPCBatch(ocp, E, dev)
         self.sample_mpc = MPCBatch(ocp, E * (T - 1), dev)
         if mpc_gamma is not None:           # the handles' own discount factor (else the OCP's)
@@ -137,15 +145,19 @@ class DeviceQLearning:
         self.theta = torch.as_tensor(ocp.p0, **f64).clone()            # updated in place (the handles copy it after every step)
         self.learn_mask = torch.zeros_like(self.theta)
         self.learn_mask[: ocp.n_model_p] = 1.0                          # the model's parameters
-        self.lo, self.hi = float(ocp.lbu[0]), float(ocp.ubu[0])
+        if NU == 1:
+            self.lo, self.hi = float(ocp.lbu[0]), float(ocp.ubu[0])
+        else:
+            import ctypes
+            self.lo_v, self.hi_v = (ctypes.c_double * NU)(*map(float, ocp.lbu)), (ctypes.c_double * NU)(*map(float, ocp.ubu))
         self.gen = torch.Generator(device=dev).manual_seed(seed)
         # the episode's device state: every buffer keeps its address (captured graphs hold them)
         self.obs = torch.zeros(E, NX, **f64)
         self.row = torch.zeros(E, dtype=torch.int32, device=dev)
         self.cold = torch.ones(E, dtype=torch.int32, device=dev)
-        self.eps = torch.zeros(T, E, dtype=torch.float32, device=dev)
+        self.eps = torch.zeros(T, E, *wide, dtype=torch.float32, device=dev)
         self.S = torch.zeros(T, E, NX, **f64)
-        self.A = torch.zeros(T, E, **f64)
+        self.A = torch.zeros(T, E, *wide, **f64)
         self.C = torch.zeros(T, E, **f64)
         self.td = torch.zeros(T - 2, E, **f64)
         self.valid = torch.zeros(T - 2, E, dtype=torch.uint8, device=dev)
@@ -158,6 +170,11 @@ class DeviceQLearning:
         self._td_ws = torch.zeros(nb, dtype=torch.uint8, device=dev)
         # the roll-out handle holds an iterate from here on, so that the first solve of every episode (eager or replayed) is the
         # per-instance cold start of the cold mask, never the handle-wide one of a fresh handle
+        x_init = self._initial_obs()
+        if x_init is not None:              # else the zero state, as the buffers are allocated
+            x_init = torch.as_tensor(x_init, **f64)
+            self.obs.copy_(x_init.expand_as(self.obs))
+            self.S.copy_(x_init.expand_as(self.S))
         self.rollout_mpc.solve(self.obs, cold=True)
         self._graphs = None
         self.last = None                # the roll-out solves of the last eager episode, one SolveResult per step
@@ -175,7 +192,7 @@ class DeviceQLearning:
         self.obs.copy_(self.env.state)
         self.row.zero_()
         self.cold.fill_(1)
-        torch.randn(self.T, self.E, generator=self.gen, dtype=torch.float32, device=self.device, out=self.eps)
+        torch.randn(*self.eps.shape, generator=self.gen, dtype=torch.float32, device=self.device, out=self.eps)
 
     def _rollout_step(self):
         r = self.rollout_mpc.solve(self.obs, cold_mask=self.cold)           # the policy of every environment (mpc.get_action), one launch
@@ -188,7 +205,7 @@ class DeviceQLearning:
     def _sweep(self):
         n = self.T - 1
         s = self.S[:n].reshape(n * self.E, self.NX)
-        a = self.A[:n].reshape(n * self.E, 1)
+        a = self.A[:n].reshape(n * self.E, self.NU)
         # q_update: Q(s_i, a_i), dQ/dp_i; its bound multipliers are not kept (store_bounds=False) ...
         rq = self.sample_mpc.solve(s, u0=a, sens_v=True, cold=True, store_bounds=False)
         # ... update: V(s_i) from the Q solve's primal iterate, interior point from its default point
@@ -214,6 +231,11 @@ class DeviceQLearning:
             raise RuntimeError(f"mpcrl_qlearning_apply failed with {rc}")
         for m in (self.rollout_mpc, self.sample_mpc):
             m.set_theta(self.theta)                                    # mpc.set_parameter
+
+    def _initial_obs(self):
+        """The state [NX] that ``obs`` and the rows of ``S`` hold before the first episode: what the constructor's priming solve and the
+        warm-up of enable_graphs solve on.  None: zeros."""
+        return None
 
     def _env_carried(self):
         """The environment's tensors that a roll-out step changes (put back after the warm-up of enable_graphs)."""
