@@ -100,7 +100,8 @@ extern "C" {
  *        Gaussian actor, cartpole); round 8: mpcrl_value_forward; mpcrl_value_mse_grad / mpcrl_value_workspace_bytes (PPO's value
  *        function as library kernels); mpcrl_qlearning_linear_collect; mpcrl_ppo_linear_collect (the linear system's Q-learning and
  *        PPO roll-out steps); mpcrl_env_chain_step; mpcrl_qlearning_chain_collect (the chain of masses as a plant and its Q-learning
- *        roll-out step) */
+ *        roll-out step); mpcrl_ppo_chain_collect; mpcrl_ppo_surrogate_grad_nu / mpcrl_ppo_surrogate_workspace_bytes_nu;
+ *        mpcrl_ppo_log_std_apply_nu (PPO on the chain of masses: a diagonal Gaussian over its three controls) */
 #define MPCRL_ABI_VERSION 132
 
 enum { MPCRL_MODEL_CARTPOLE = 0, MPCRL_MODEL_LINEAR = 1, MPCRL_MODEL_CHAIN = 2 };
@@ -538,6 +539,51 @@ int mpcrl_qlearning_chain_collect(int n_mass, double Ts, int rk_steps, const dou
                                   int T, double *state, const double *u0, const int32_t *status, const float *eps, const double *wn,
                                   const double *lo, const double *hi, double sigma, double *obs, int32_t *row, int32_t *cold, double *S, double *A,
                                   double *C, void *stream);
+
+/* Added under ABI 132.  One roll-out step of PPO on the chain of masses after the policy's solve, one launch (ppo_chain_kernel.hpp;
+ * mpc4rl_amd/ppo.py): mpcrl_ppo_linear_collect's shape with the chain as the plant and a diagonal Gaussian over its three controls, one
+ * lane per environment, all arithmetic fp64.  n_mass ... x_ss, w_std: the plant as in mpcrl_env_chain_step (the environment step is that
+ * call's device function: the same bits); wn [E][3 M]: this step's disturbance draws (NULL iff w_std == 0).  u0 [E][3], status [E]: the
+ * solve; eps [E][3] float standard-normal draws; value [E]; log_std [3]: DEVICE doubles, one per control; lo, hi: 3 HOST doubles each
+ * (lbu, ubu), lo_j < hi_j; 0 <= t < T the row written.
+ *   ok   = status in {0, 2} and all three u0 finite (mpcrl_qlearning_chain_collect's `good`);   mu_j = ok ? 2 (u0_j - lo_j) / (hi_j - lo_j) - 1 : 0;
+ *   a_j  = mu_j + exp(log_std_j) eps_j (unclipped: this is what is stored);
+ *   logp = sum_j [-(a_j - mu_j)^2 / (2 sigma_j^2) - log_std_j - 1/2 log 2 pi], j = 0, 1, 2 in that order;
+ *   the plant is stepped with the PHYSICAL controls lo_j + 0.5 (clip(a_j, -1, 1) + 1) (hi_j - lo_j) (unscale_action) and wn.
+ * Row t of the tables [T][E]: OBS ([..][nx], the state before the step), ACT ([..][3]), LOGP, VAL = value, REW = reward_scale * l(s, applied)
+ * (mpcrl_env_chain_step's cost: of the state BEFORE the step), NEXT ([..][nx], the state after the step BEFORE any reset), TERM = 0 (the
+ * plant never terminates), DONE = steps + 1 >= episode_length (>= 1; steps [E] int64 is the CALLER's count of steps since the last reset),
+ * OK.  A done environment restarts at x_reset (nx DEVICE doubles: the OCP's x0) plus vel_std * rn on its 3 M velocity entries (the last
+ * 3 M of the state) with steps = 0 — rn [E][3 M]: this step's standard-normal draws, NULL iff vel_std == 0 — which is what
+ * BatchedChainMassEnv.reset draws.  obs [E][nx] = the state after that (the next solve's x0), ended [E] int32 = DONE.
+ * MPCRL_E_ARG: the plant's cases, E < 0, T < 1, t outside [0, T), episode_length < 1, a NULL pointer, lo_j >= hi_j, a NaN vel_std.  E = 0:
+ * nothing is launched.  Handle-less (launched on the device that owns `state`), asynchronous on `stream`, capture-safe. */
+int mpcrl_ppo_chain_collect(int n_mass, double Ts, int rk_steps, const double *p, int64_t p_stride, const double *x_ss, double w_std, int E, int T,
+                            int t, double *state, int64_t *steps, const double *u0, const int32_t *status, const float *eps, const double *wn,
+                            const double *value, const double *log_std, const double *lo, const double *hi, double reward_scale,
+                            int64_t episode_length, const double *x_reset, double vel_std, const double *rn, double *OBS, double *ACT, double *LOGP,
+                            double *VAL, double *REW, double *NEXT, uint8_t *TERM, uint8_t *DONE, uint8_t *OK, double *obs, int32_t *ended,
+                            void *stream);
+
+/* Added under ABI 132.  mpcrl_ppo_surrogate_grad for a diagonal Gaussian over nu controls, 1 <= nu <= 3: ACT [n_rows][nu], u0_new [M][nu],
+ * dpi_dp [M][nu][n_p], log_std [nu] DEVICE doubles, lo, hi: nu HOST doubles each, lo_c < hi_c.  A row is valid when all nu entries of
+ * u0_new and of ACT are finite (and the rest as there); logp_b is the sum over c = 0 .. nu-1, in that order, of the one-control term;
+ *   g_mu,c = -A r (a_c - mu_c) / sigma_c^2,  g_ls,c = -A r ((a_c - mu_c)^2 / sigma_c^2 - 1), all 0 where the clipped branch is the minimum.
+ * msg [n_p + 8 + (nu - 1)]: [0, n_p) = -lr sum_b sum_c g_mu,bc 2 / (hi_c - lo_c) nan_to_num(dpi_dp[b][c][.]) — the rows b in order, the
+ *   controls c in order inside a row; [n_p, n_p + 8) as in mpcrl_ppo_surrogate_grad with g_ls,0 at [n_p], so mpcrl_qlearning_apply and
+ *   the all-reduce read the same layout;  [n_p + 8 + c - 1] = -lr (sum_b g_ls,bc - ent_coef count) for c = 1 .. nu-1.
+ * nu = 1 runs the kernel mpcrl_ppo_surrogate_grad runs: the same bits.  workspace: mpcrl_ppo_surrogate_workspace_bytes_nu(M, n_p, nu) bytes,
+ * ZERO before the first call (the call leaves it zero).  MPCRL_E_ARG: nu outside 1..3, M < 0 and the cases there.  M = 0: nothing is
+ * launched (and the workspace is the 16 bytes of the ticket). */
+int64_t mpcrl_ppo_surrogate_workspace_bytes_nu(int M, int n_p, int nu);
+int mpcrl_ppo_surrogate_grad_nu(const int64_t *idx, int M, int64_t n_rows, const double *ACT, const double *LOGP, const double *ADV, const uint8_t *OK,
+                                const double *u0_new, const int32_t *status_new, const double *dpi_dp, int n_p, int nu, const double *log_std,
+                                const double *lo, const double *hi, double clip_range, double ent_coef, double lr, int normalize_adv, void *workspace,
+                                double *msg, void *stream);
+
+/* Added under ABI 132.  mpcrl_ppo_log_std_apply for nu entries (1 <= nu <= 3), c = max(1, msg[n_p + 1]):
+ * log_std[0] += msg[n_p] / c;  log_std[j] += msg[n_p + 7 + j] / c for j = 1 .. nu-1 (the layout of mpcrl_ppo_surrogate_grad_nu). */
+int mpcrl_ppo_log_std_apply_nu(const double *msg, int n_p, int nu, double *log_std, void *stream);
 
 /* Bytes of device memory held by the handle; library version (MPCRL_ABI_VERSION of the header it was built from). */
 int64_t mpcrl_workspace_bytes(mpcrl_handle h);

@@ -16,6 +16,7 @@ from .qlearning_linear import LinearQLearning, linear_collect_terms, linear_env_
 from .qlearning_chain import ChainQLearning, chain_collect_terms, chain_env_step_terms  # noqa: F401
 from .td3 import BatchedTD3, ContinuousCritic, DeviceReplayBuffer, MPCActor, MPCTD3Policy  # noqa: F401
 from .ppo import BatchedPPO, MPCActorCriticPolicy, ppo_collect_terms, ppo_gae, ppo_linear_collect_terms, ppo_surrogate_terms, ppo_value_terms  # noqa: F401
+from .ppo import ppo_chain_collect_terms, ppo_surrogate_terms_nu  # noqa: F401
 from .config import cartpole_ocp_from_config, read_config, store_iterate, load_iterate  # noqa: F401
 from .mpc import MPC, CartpoleMPC, ChainMassMPC, LinearSystemMPC  # noqa: F401
 

@@ -16,7 +16,8 @@ __device__ inline double nan_to_num_d(double v) {
 
 // partial_row[p] = sum_{k < nr} w[k] nan_to_num(base[k n_p + p]) for p < n_p: one lane per column (stride NT, the block size), the rows in
 // order, eight loads in flight per lane.  (A row that is left out has weight 0 and is read all the same — nan_to_num makes every entry
-// finite, 0 x finite = 0: no branch.)
+// finite, 0 x finite = 0: no branch.)  Sensitivities of nu components per batch row, base [.][nu][n_p] with w [.][nu], are nr x nu rows
+// here: the batch rows in order, the components 0 .. nu-1 in order inside a row.
 template <int NT>
 __device__ __forceinline__ void block_weighted_colsum(const double *w, const double *base, int nr, int n_p, double *partial_row) {
     for (int p = threadIdx.x; p < n_p; p += NT) {

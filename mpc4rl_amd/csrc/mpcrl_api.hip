@@ -21,6 +21,7 @@
 #include "td3_kernel.hpp"
 #include "qlearning_kernel.hpp"
 #include "ppo_kernel.hpp"
+#include "ppo_chain_kernel.hpp"
 #include "value_kernel.hpp"
 #include "linear_loop_kernel.hpp"
 #include "chain_env_kernel.hpp"
@@ -828,28 +829,69 @@ int64_t mpcrl_ppo_surrogate_workspace_bytes(int M, int n_p) {
     return ticket_workspace_bytes(M, PPO_ROWS, n_p + PPO_NS);
 }
 
+int64_t mpcrl_ppo_surrogate_workspace_bytes_nu(int M, int n_p, int nu) {
+    if (M < 0 || n_p < 1 || nu < 1 || nu > PPO_NU_MAX) return MPCRL_E_ARG;
+    return ticket_workspace_bytes(M, PPO_ROWS, n_p + PPO_NS + nu - 1);
+}
+
+// the two launches of mpcrl_ppo_surrogate_grad / mpcrl_ppo_surrogate_grad_nu, after their argument checks (lo, hi: nu host doubles)
+static int launch_ppo_surrogate(const int64_t *idx, int M, int64_t n_rows, const double *ACT, const double *LOGP, const double *ADV, const uint8_t *OK,
+                                const double *u0_new, const int32_t *status_new, const double *dpi_dp, int n_p, int nu, const double *log_std,
+                                const double *lo, const double *hi, double clip_range, double ent_coef, double lr, int normalize_adv, void *workspace,
+                                double *msg, void *stream) {
+    ON_DEVICE_OF(msg);
+    PpoSurrogateArgs a;
+    a.idx = idx, a.M = M, a.n_p = n_p, a.n_rows = n_rows, a.ACT = ACT, a.LOGP = LOGP, a.ADV = ADV, a.OK = OK, a.u0_new = u0_new;
+    a.status_new = (const int *)status_new, a.dpi = dpi_dp, a.log_std = log_std, a.clip = clip_range, a.ent_coef = ent_coef, a.lr = lr;
+    for (int c = 0; c < PPO_NU_MAX; ++c) a.lo[c] = c < nu ? lo[c] : 0.0, a.hi[c] = c < nu ? hi[c] : 1.0;
+    a.normalize = normalize_adv, a.msg = msg;
+    set_ticket_workspace(a, workspace);
+    const dim3 grid((unsigned)ticket_blocks(M, PPO_ROWS));
+#define LAUNCH(NU)                                                                                                   \
+    hipLaunchKernelGGL(ppo_adv_stats_kernel<NU>, dim3(1), dim3(PPO_STAT_THREADS), 0, (hipStream_t)stream, a); \
+    hipLaunchKernelGGL(ppo_surrogate_kernel<NU>, grid, dim3(PPO_ROWS), 0, (hipStream_t)stream, a)
+    switch (nu) {
+        case 1: LAUNCH(1); break;
+        case 2: LAUNCH(2); break;
+        default: LAUNCH(3); break;
+    }
+#undef LAUNCH
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 int mpcrl_ppo_surrogate_grad(const int64_t *idx, int M, int64_t n_rows, const double *ACT, const double *LOGP, const double *ADV, const uint8_t *OK,
                              const double *u0_new, const int32_t *status_new, const double *dpi_dp, int n_p, const double *log_std, double lo, double hi,
                              double clip_range, double ent_coef, double lr, int normalize_adv, void *workspace, double *msg, void *stream) {
     if (!idx || M < 1 || n_rows < 1 || !ACT || !LOGP || !ADV || !OK || !u0_new || !status_new || !dpi_dp || n_p < 1 || !log_std || !(hi > lo) ||
         !(clip_range > 0.0) || !workspace || !msg)
         return MPCRL_E_ARG;
-    ON_DEVICE_OF(msg);
-    PpoSurrogateArgs a;
-    a.idx = idx, a.M = M, a.n_p = n_p, a.n_rows = n_rows, a.ACT = ACT, a.LOGP = LOGP, a.ADV = ADV, a.OK = OK, a.u0_new = u0_new;
-    a.status_new = (const int *)status_new, a.dpi = dpi_dp, a.log_std = log_std, a.lo = lo, a.hi = hi, a.clip = clip_range, a.ent_coef = ent_coef, a.lr = lr;
-    a.normalize = normalize_adv, a.msg = msg;
-    set_ticket_workspace(a, workspace);
-    hipLaunchKernelGGL(ppo_adv_stats_kernel, dim3(1), dim3(PPO_STAT_THREADS), 0, (hipStream_t)stream, a);
-    hipLaunchKernelGGL(ppo_surrogate_kernel, dim3((unsigned)ticket_blocks(M, PPO_ROWS)), dim3(PPO_ROWS), 0, (hipStream_t)stream, a);
-    HIP_OK(hipGetLastError());
-    return 0;
+    return launch_ppo_surrogate(idx, M, n_rows, ACT, LOGP, ADV, OK, u0_new, status_new, dpi_dp, n_p, 1, log_std, &lo, &hi, clip_range, ent_coef, lr,
+                                normalize_adv, workspace, msg, stream);
+}
+
+int mpcrl_ppo_surrogate_grad_nu(const int64_t *idx, int M, int64_t n_rows, const double *ACT, const double *LOGP, const double *ADV, const uint8_t *OK,
+                                const double *u0_new, const int32_t *status_new, const double *dpi_dp, int n_p, int nu, const double *log_std,
+                                const double *lo, const double *hi, double clip_range, double ent_coef, double lr, int normalize_adv, void *workspace,
+                                double *msg, void *stream) {
+    if (!idx || M < 0 || n_rows < 1 || !ACT || !LOGP || !ADV || !OK || !u0_new || !status_new || !dpi_dp || n_p < 1 || nu < 1 || nu > PPO_NU_MAX ||
+        !log_std || !lo || !hi || !(clip_range > 0.0) || !workspace || !msg)
+        return MPCRL_E_ARG;
+    for (int c = 0; c < nu; ++c)
+        if (!(hi[c] > lo[c])) return MPCRL_E_ARG;
+    if (M == 0) return 0;
+    return launch_ppo_surrogate(idx, M, n_rows, ACT, LOGP, ADV, OK, u0_new, status_new, dpi_dp, n_p, nu, log_std, lo, hi, clip_range, ent_coef, lr,
+                                normalize_adv, workspace, msg, stream);
 }
 
 int mpcrl_ppo_log_std_apply(const double *msg, int n_p, double *log_std, void *stream) {
-    if (!msg || n_p < 1 || !log_std) return MPCRL_E_ARG;
+    return mpcrl_ppo_log_std_apply_nu(msg, n_p, 1, log_std, stream);
+}
+
+int mpcrl_ppo_log_std_apply_nu(const double *msg, int n_p, int nu, double *log_std, void *stream) {
+    if (!msg || n_p < 1 || nu < 1 || nu > PPO_NU_MAX || !log_std) return MPCRL_E_ARG;
     ON_DEVICE_OF(log_std);
-    hipLaunchKernelGGL(ppo_log_std_apply_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, msg, n_p, log_std);
+    hipLaunchKernelGGL(ppo_log_std_apply_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, msg, n_p, nu, log_std);
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -1015,6 +1057,34 @@ int mpcrl_qlearning_chain_collect(int n_mass, double Ts, int rk_steps, const dou
     a.E = E, a.T = T, a.state = state, a.u0 = u0, a.status = (const int *)status, a.eps = eps, a.sigma = (float)sigma;
     a.obs = obs, a.row = row, a.cold = cold, a.S = S, a.A = A, a.C = C;
 #define LAUNCH(NM) hipLaunchKernelGGL(qlearning_chain_collect_kernel<NM>, dim3((E + 63) / 64), dim3(64), 0, (hipStream_t)stream, a)
+    CHAIN_ENV_SWITCH(n_mass, LAUNCH)
+#undef LAUNCH
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int mpcrl_ppo_chain_collect(int n_mass, double Ts, int rk_steps, const double *p, int64_t p_stride, const double *x_ss, double w_std, int E, int T,
+                            int t, double *state, int64_t *steps, const double *u0, const int32_t *status, const float *eps, const double *wn,
+                            const double *value, const double *log_std, const double *lo, const double *hi, double reward_scale,
+                            int64_t episode_length, const double *x_reset, double vel_std, const double *rn, double *OBS, double *ACT, double *LOGP,
+                            double *VAL, double *REW, double *NEXT, uint8_t *TERM, uint8_t *DONE, uint8_t *OK, double *obs, int32_t *ended,
+                            void *stream) {
+    PpoChainCollectArgs a;
+    if (!chain_env_par(n_mass, Ts, rk_steps, p, p_stride, x_ss, wn, w_std, a.env) || E < 0 || T < 1 || t < 0 || t >= T || episode_length < 1 ||
+        !state || !steps || !u0 || !status || !eps || !value || !log_std || !lo || !hi || !x_reset || !(vel_std == vel_std) ||
+        (vel_std != 0.0 && !rn) || !OBS || !ACT || !LOGP || !VAL || !REW || !NEXT || !TERM || !DONE || !OK || !obs || !ended)
+        return MPCRL_E_ARG;
+    for (int j = 0; j < 3; ++j) {
+        if (!(hi[j] > lo[j])) return MPCRL_E_ARG;
+        a.lo[j] = lo[j], a.hi[j] = hi[j];
+    }
+    if (E == 0) return 0;
+    ON_DEVICE_OF(state);
+    a.E = E, a.T = T, a.t = t, a.state = state, a.steps = steps, a.u0 = u0, a.status = (const int *)status, a.eps = eps, a.value = value;
+    a.log_std = log_std, a.reward_scale = reward_scale, a.episode_length = episode_length, a.x_reset = x_reset, a.vel_std = vel_std;
+    a.rn = vel_std != 0.0 ? rn : nullptr, a.OBS = OBS, a.ACT = ACT, a.LOGP = LOGP, a.VAL = VAL, a.REW = REW, a.NEXT = NEXT, a.TERM = TERM, a.DONE = DONE;
+    a.OK = OK, a.obs = obs, a.ended = ended;
+#define LAUNCH(NM) hipLaunchKernelGGL(ppo_chain_collect_kernel<NM>, dim3((E + 63) / 64), dim3(64), 0, (hipStream_t)stream, a)
     CHAIN_ENV_SWITCH(n_mass, LAUNCH)
 #undef LAUNCH
     HIP_OK(hipGetLastError());

@@ -1,4 +1,5 @@
-// Batched PPO with the MPC as Gaussian actor, cartpole environment, nu = 1 (mpc4rl_amd/ppo.py): what the reference's
+// Batched PPO with the MPC as Gaussian actor (mpc4rl_amd/ppo.py; the roll-out step here is the one-control one, the chain's is in
+// ppo_chain_kernel.hpp; the surrogate is written for 1 to 3 controls): what the reference's
 // MPCActorCriticPolicy (rlmpc/ppo/policies.py:26-134) leaves as NotImplementedError, around the solves, on the device.  The policy is
 // a ~ N(mu, sigma^2), mu = scale_action(u0*) of the solve, sigma = exp(log_std) with one learnable, state-independent log_std.
 //   ppo_collect_kernel<Env>       one roll-out step after the policy's solve, one lane per environment: the sample and its log
@@ -137,38 +138,48 @@ __global__ void __launch_bounds__(256) ppo_gae_kernel(const double *REW, const d
     }
 }
 
-// The policy half of one minibatch update.  Rows b < M of the minibatch, j = idx[b] its row of the flattened [T E] tables:
-//     valid_b = 0 <= j < n_rows, OK[j], the re-solve accepted (status 0 or 2, u0_new finite), ACT, LOGP, ADV[j] finite
+// The policy half of one minibatch update, for NU controls (1: the cartpole and the linear system; 3: the chain of masses, whose policy
+// is the diagonal Gaussian of ppo_chain_kernel.hpp).  Rows b < M of the minibatch, j = idx[b] its row of the flattened [T E] tables:
+//     valid_b = 0 <= j < n_rows, OK[j], the re-solve accepted (status 0 or 2, all NU u0_new finite), ACT (all NU), LOGP, ADV[j] finite
 //     A_b     = normalize_adv and more than one valid row ? (ADV[j] - mean) / (std + 1e-8) : ADV[j]      (unbiased std, as torch.std)
-//     r_b     = exp(logp_b - LOGP[j]);   loss_b = -min(r_b A_b, clip(r_b, 1 - eps, 1 + eps) A_b)
-//     g_mu = -A r (a - mu) / sigma^2,  g_ls = -A r ((a - mu)^2 / sigma^2 - 1);  both 0 where the clipped branch is the minimum
-// An invalid row is selected out (its u0_new / dpi_dp may be NaN); dpi_dp is read as nan_to_num does.
-constexpr int PPO_ROWS = 128, PPO_PMAX = 256, PPO_NS = 6, PPO_STAT_THREADS = 1024;
-// message / partial columns after the n_p gradient entries: sum g_ls, count, sum loss, sum (r - 1) - log r, clipped rows, sum r;
-// the message then carries the two advantage statistics: sum ADV and sum (ADV - mean)^2 over the valid rows
+//     logp_b  = sum_c log N(a_c; mu_c, sigma_c^2), c = 0 .. NU-1 in that order;   r_b = exp(logp_b - LOGP[j])
+//     loss_b  = -min(r_b A_b, clip(r_b, 1 - eps, 1 + eps) A_b)
+//     g_mu_c = -A r (a_c - mu_c) / sigma_c^2,  g_ls_c = -A r ((a_c - mu_c)^2 / sigma_c^2 - 1);  all 0 where the clipped branch is the minimum
+// An invalid row is selected out (its u0_new / dpi_dp may be NaN); dpi_dp is read as nan_to_num does.  With NU = 1 these are the
+// operations of the one-control kernel in its order.
+constexpr int PPO_ROWS = 128, PPO_PMAX = 256, PPO_NS = 6, PPO_STAT_THREADS = 1024, PPO_NU_MAX = 3;
+// message / partial columns after the n_p gradient entries: sum g_ls_0, count, sum loss, sum (r - 1) - log r, clipped rows, sum r;
+// the message then carries the two advantage statistics: sum ADV and sum (ADV - mean)^2 over the valid rows.  With NU > 1 the sums of
+// g_ls_c, c >= 1, follow: partial columns [n_p + PPO_NS + c - 1], message entries [n_p + PPO_MSG_EXTRA + c - 1] — the first
+// n_p + PPO_MSG_EXTRA entries are the one-control layout, which mpcrl_qlearning_apply and the all-reduce read.
 constexpr int PPO_MSG_EXTRA = 8;
 
 struct PpoSurrogateArgs {
     const int64_t *idx;           // [M]
     int M, n_p;
     int64_t n_rows;               // rows of the flattened tables
-    const double *ACT, *LOGP, *ADV;
+    const double *ACT, *LOGP, *ADV;      // ACT [n_rows][NU]
     const uint8_t *OK;
-    const double *u0_new;         // [M]
+    const double *u0_new;         // [M][NU]
     const int *status_new;        // [M]
-    const double *dpi;            // [M][1][n_p]
-    const double *log_std;        // [1]
-    double lo, hi, clip, ent_coef, lr;
+    const double *dpi;            // [M][NU][n_p]
+    const double *log_std;        // [NU]
+    double lo[PPO_NU_MAX], hi[PPO_NU_MAX];
+    double clip, ent_coef, lr;
     int normalize;
-    double *partial;              // [n_blocks][n_p + PPO_NS]
+    double *partial;              // [n_blocks][n_p + PPO_NS + NU - 1]
     unsigned int *ticket;         // [1], zero before the first launch (the kernel leaves it zero)
-    double *msg;                  // [n_p + PPO_MSG_EXTRA]
+    double *msg;                  // [n_p + PPO_MSG_EXTRA + NU - 1]
 };
 
+template <int NU>
 __device__ __forceinline__ bool ppo_row_valid(const PpoSurrogateArgs &a, int b, long &j) {
     j = (long)a.idx[b];
     if (j < 0 || j >= a.n_rows) return false;
-    return a.OK[j] != 0 && ppo_solve_ok(a.status_new[b], a.u0_new[b]) && isfinite(a.ACT[j]) && isfinite(a.LOGP[j]) && isfinite(a.ADV[j]);
+    bool ok = a.OK[j] != 0;
+#pragma unroll
+    for (int c = 0; c < NU; ++c) ok = ok && ppo_solve_ok(a.status_new[b], a.u0_new[(long)NU * b + c]) && isfinite(a.ACT[NU * j + c]);
+    return ok && isfinite(a.LOGP[j]) && isfinite(a.ADV[j]);
 }
 
 // sum of v over the workgroup in a fixed order (a tree over the lanes' slots); every lane returns the total
@@ -185,19 +196,20 @@ __device__ __forceinline__ double ppo_block_sum(double v, double *red) {
 }
 
 // one workgroup: msg[n_p + 1] = valid rows, msg[n_p + 6] = sum ADV, msg[n_p + 7] = sum (ADV - mean)^2 over them (two passes)
+template <int NU>
 __global__ void __launch_bounds__(PPO_STAT_THREADS) ppo_adv_stats_kernel(const PpoSurrogateArgs a) {
     __shared__ double red[PPO_STAT_THREADS];
     double n = 0.0, s = 0.0;
     for (int b = threadIdx.x; b < a.M; b += PPO_STAT_THREADS) {
         long j;
-        if (ppo_row_valid(a, b, j)) n += 1.0, s += a.ADV[j];
+        if (ppo_row_valid<NU>(a, b, j)) n += 1.0, s += a.ADV[j];
     }
     n = ppo_block_sum(n, red), s = ppo_block_sum(s, red);
     const double mean = s / (n > 1.0 ? n : 1.0);
     double q = 0.0;
     for (int b = threadIdx.x; b < a.M; b += PPO_STAT_THREADS) {
         long j;
-        if (ppo_row_valid(a, b, j)) {
+        if (ppo_row_valid<NU>(a, b, j)) {
             const double d = a.ADV[j] - mean;
             q += d * d;
         }
@@ -206,12 +218,15 @@ __global__ void __launch_bounds__(PPO_STAT_THREADS) ppo_adv_stats_kernel(const P
     if (threadIdx.x == 0) a.msg[a.n_p + 1] = n, a.msg[a.n_p + 6] = s, a.msg[a.n_p + 7] = q;
 }
 
-// The sum is the fixed-order batch sum of batch_sum.hpp over blocks of PPO_ROWS rows: the same inputs give the same bits.
+// The sum is the fixed-order batch sum of batch_sum.hpp over blocks of PPO_ROWS rows — a row's NU sensitivity rows in the order of its
+// controls: the same inputs give the same bits.
+template <int NU>
 __global__ void __launch_bounds__(PPO_ROWS) ppo_surrogate_kernel(const PpoSurrogateArgs a) {
-    __shared__ double w[PPO_ROWS];
-    __shared__ double sc[PPO_NS][PPO_ROWS];
+    constexpr int NS = PPO_NS + NU - 1;
+    __shared__ double w[PPO_ROWS * NU];          // [row][control]: block_weighted_colsum's weights of the block's PPO_ROWS x NU rows of dpi
+    __shared__ double sc[NS][PPO_ROWS];
     const long b0 = (long)blockIdx.x * PPO_ROWS;
-    const int P2 = a.n_p + PPO_NS;
+    const int P2 = a.n_p + NS;
     const double n_valid = a.msg[a.n_p + 1];
     double mean = 0.0, den = 1.0;
     if (a.normalize && n_valid > 1.0) {
@@ -220,53 +235,71 @@ __global__ void __launch_bounds__(PPO_ROWS) ppo_surrogate_kernel(const PpoSurrog
     }
     {
         const long b = b0 + threadIdx.x;
-        double wj = 0.0, v[PPO_NS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        double wj[NU], v[NS];
+#pragma unroll
+        for (int c = 0; c < NU; ++c) wj[c] = 0.0;
+#pragma unroll
+        for (int q = 0; q < NS; ++q) v[q] = 0.0;
         long j;
-        if (b < a.M && ppo_row_valid(a, (int)b, j)) {
-            const double ls = a.log_std[0], sigma = exp(ls), var = sigma * sigma;
+        if (b < a.M && ppo_row_valid<NU>(a, (int)b, j)) {
             const double A = (a.ADV[j] - mean) / den;
-            const double act = a.ACT[j];
-            const double mu = ppo_mean(a.u0_new[b], true, a.lo, a.hi);
-            const double logr = ppo_log_prob(act, mu, sigma, ls) - a.LOGP[j];
+            double d[NU], var[NU], logp = 0.0;
+#pragma unroll
+            for (int c = 0; c < NU; ++c) {
+                const double ls = a.log_std[c], sigma = exp(ls);
+                var[c] = sigma * sigma;
+                const double act = a.ACT[NU * j + c];
+                const double mu = ppo_mean(a.u0_new[(long)NU * b + c], true, a.lo[c], a.hi[c]);
+                const double lp = ppo_log_prob(act, mu, sigma, ls);
+                logp = c == 0 ? lp : logp + lp;
+                d[c] = act - mu;
+            }
+            const double logr = logp - a.LOGP[j];
             const double r = exp(logr);
             const double rc = r < 1.0 - a.clip ? 1.0 - a.clip : (r > 1.0 + a.clip ? 1.0 + a.clip : r);
             const double l1 = r * A, l2 = rc * A;
             const bool flat = (A > 0.0 && r > 1.0 + a.clip) || (A < 0.0 && r < 1.0 - a.clip);      // the clipped branch is the minimum
-            const double d = act - mu;
-            const double g_mu = flat ? 0.0 : -(A * r) * (d / var);
-            const double g_ls = flat ? 0.0 : -(A * r) * (d * d / var - 1.0);
-            wj = g_mu * (2.0 / (a.hi - a.lo));
-            v[0] = g_ls, v[1] = 1.0, v[2] = -(l1 < l2 ? l1 : l2), v[3] = (r - 1.0) - logr, v[4] = fabs(r - 1.0) > a.clip ? 1.0 : 0.0, v[5] = r;
-        }
-        w[threadIdx.x] = wj;
 #pragma unroll
-        for (int q = 0; q < PPO_NS; ++q) sc[q][threadIdx.x] = v[q];
+            for (int c = 0; c < NU; ++c) {
+                const double g_mu = flat ? 0.0 : -(A * r) * (d[c] / var[c]);
+                const double g_ls = flat ? 0.0 : -(A * r) * (d[c] * d[c] / var[c] - 1.0);
+                wj[c] = g_mu * (2.0 / (a.hi[c] - a.lo[c]));
+                v[c == 0 ? 0 : PPO_NS + c - 1] = g_ls;
+            }
+            v[1] = 1.0, v[2] = -(l1 < l2 ? l1 : l2), v[3] = (r - 1.0) - logr, v[4] = fabs(r - 1.0) > a.clip ? 1.0 : 0.0, v[5] = r;
+        }
+#pragma unroll
+        for (int c = 0; c < NU; ++c) w[NU * threadIdx.x + c] = wj[c];
+#pragma unroll
+        for (int q = 0; q < NS; ++q) sc[q][threadIdx.x] = v[q];
     }
     __syncthreads();
-    if (threadIdx.x < PPO_NS) {
+    if (threadIdx.x < NS) {
         double s = 0.0;
         for (int r = 0; r < PPO_ROWS; ++r) s += sc[threadIdx.x][r];
         a.partial[(long)blockIdx.x * P2 + a.n_p + threadIdx.x] = s;
     }
     const int nr = (int)(a.M - b0 < PPO_ROWS ? a.M - b0 : PPO_ROWS);
-    block_weighted_colsum<PPO_ROWS>(w, a.dpi + b0 * a.n_p, nr, a.n_p, a.partial + (long)blockIdx.x * P2);
+    block_weighted_colsum<PPO_ROWS>(w, a.dpi + b0 * NU * a.n_p, nr * NU, a.n_p, a.partial + (long)blockIdx.x * P2);
     if (!last_workgroup(a.ticket)) return;
     const int nb = gridDim.x;
     sliced_final_sum<PPO_PMAX, PPO_ROWS>(a.partial, nb, P2, [&](int p, double s) {
         // the step of theta and of log_std: -lr x the sums (the entropy bonus adds -ent_coef to every valid row's g_ls)
         if (p < a.n_p) s = -a.lr * s;
-        if (p == a.n_p) s = -a.lr * (s - a.ent_coef * n_valid);
-        a.msg[p] = s;
+        if (p == a.n_p || p >= a.n_p + PPO_NS) s = -a.lr * (s - a.ent_coef * n_valid);
+        a.msg[p < a.n_p + PPO_NS ? p : p + (PPO_MSG_EXTRA - PPO_NS)] = s;
     });
     // the workspace is left all zero
     for (long e = threadIdx.x; e < (long)nb * P2; e += PPO_ROWS) a.partial[e] = 0.0;
 }
 
-// After the collective: log_std += msg[n_p] / max(1, msg[n_p + 1]) — the masked mean mpcrl_qlearning_apply takes for theta
-__global__ void ppo_log_std_apply_kernel(const double *msg, int n_p, double *log_std) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const double c = msg[n_p + 1] > 1.0 ? msg[n_p + 1] : 1.0;
-        log_std[0] = log_std[0] + msg[n_p] / c;
+// After the collective: log_std[0] += msg[n_p] / max(1, msg[n_p + 1]) — the masked mean mpcrl_qlearning_apply takes for theta — and
+// log_std[c] += msg[n_p + PPO_MSG_EXTRA + c - 1] / max(1, msg[n_p + 1]) for the controls c >= 1
+__global__ void ppo_log_std_apply_kernel(const double *msg, int n_p, int nu, double *log_std) {
+    const int c = threadIdx.x;
+    if (blockIdx.x == 0 && c < nu) {
+        const double cnt = msg[n_p + 1] > 1.0 ? msg[n_p + 1] : 1.0;
+        log_std[c] = log_std[c] + msg[c == 0 ? n_p : n_p + PPO_MSG_EXTRA + c - 1] / cnt;
     }
 }
 
