@@ -33,6 +33,8 @@
  *   td_error, dp = LR td dQ_dp, np.mean(dp) of the learning   mpcrl_qlearning_td_grad / mpcrl_qlearning_td_workspace_bytes,
  *   sweep; mpc.set_p(p + mean)                                  mpcrl_qlearning_apply
  *     scripts/cartpole_mpc_qlearning.py:255-269
+ *   (none: the reference steps p by LR td dQ_dp only)          mpcrl_qlearning_td_gn / mpcrl_qlearning_gn_workspace_bytes,
+ *   the same sweep's Gauss-Newton (least-squares TD) step        mpcrl_qlearning_gn_apply
  *   MPCActorCriticPolicy.forward / evaluate_actions /          mpcrl_ppo_cartpole_collect, mpcrl_ppo_gae,
  *   predict_values (NotImplementedError in the reference)       mpcrl_ppo_surrogate_grad / mpcrl_ppo_surrogate_workspace_bytes,
  *   and the PPO roll-out / update around them                   mpcrl_ppo_log_std_apply,
@@ -101,7 +103,8 @@ extern "C" {
  *        function as library kernels); mpcrl_qlearning_linear_collect; mpcrl_ppo_linear_collect (the linear system's Q-learning and
  *        PPO roll-out steps); mpcrl_env_chain_step; mpcrl_qlearning_chain_collect (the chain of masses as a plant and its Q-learning
  *        roll-out step); mpcrl_ppo_chain_collect; mpcrl_ppo_surrogate_grad_nu / mpcrl_ppo_surrogate_workspace_bytes_nu;
- *        mpcrl_ppo_log_std_apply_nu (PPO on the chain of masses: a diagonal Gaussian over its three controls) */
+ *        mpcrl_ppo_log_std_apply_nu (PPO on the chain of masses: a diagonal Gaussian over its three controls);
+ *        mpcrl_qlearning_td_gn / mpcrl_qlearning_gn_workspace_bytes; mpcrl_qlearning_gn_apply (the Q-learners' Gauss-Newton step) */
 #define MPCRL_ABI_VERSION 132
 
 enum { MPCRL_MODEL_CARTPOLE = 0, MPCRL_MODEL_LINEAR = 1, MPCRL_MODEL_CHAIN = 2 };
@@ -399,6 +402,35 @@ int mpcrl_qlearning_td_grad(const double *Q, const double *V, const double *dQ_d
 /* ABI 131.  After the collective: step_i = mask_i != 0 ? msg_i / max(1, msg[n_theta + 1]) : 0 (mask [n_theta] double, NULL = all), the mean of
  * distributed.mean_update; theta += step; step_out [n_theta] = step (mpc.set_p(mpc.get_p() + np.mean(dp)), script lines 263-269). */
 int mpcrl_qlearning_apply(const double *msg, int n_theta, const double *mask, double *theta, double *step_out, void *stream);
+
+/* Added under ABI 132.  The Gauss-Newton (least-squares TD) form of the same step (qlearning_gn_kernel.hpp): over the K learned entries
+ * idx of theta, Delta = lr (G/n + damping diag(G/n))^-1 (b/n) with G = sum_j g_j g_j', b = sum_j td_j g_j over the n valid terms and
+ * g_j = dQ_dp_j[idx] — covariant under a rescaling of the parameters, so one lr in (0, 1] means the same on every model.
+ *
+ * mpcrl_qlearning_td_gn, one launch: the inputs, the terms j, valid_j and td_j of mpcrl_qlearning_td_grad (td and valid come out with the
+ * same bits), without lr, plus idx [K] int32 on the DEVICE: strictly increasing columns of dQ_dp, 1 <= K <= 64 and K <= n_p (else
+ * MPCRL_E_ARG; the entries cannot be checked on the host: one outside [0, n_p) reads as a zero column).  With g_j = nan_to_num(dQ_dp_j[idx])
+ *   msg [K (K + 1) / 2 + K + 2] = [ G | b | sum_j valid_j td_j | sum_j valid_j ]
+ *     G: the upper triangle packed row-major, G_ac (a <= c) at a K - a (a - 1) / 2 + (c - a):  G_ac = sum_j valid_j g_ja g_jc
+ *     b: b_a = sum_j valid_j td_j g_ja at K (K + 1) / 2 + a
+ * an invalid term selected out, never multiplied in.  The message is additive over environments and ranks: one all-reduce (sum).
+ * workspace: mpcrl_qlearning_gn_workspace_bytes(T, E, K) bytes of device memory, ZERO before the first call (the call leaves it zero).
+ * Fixed summation order (blocks of 128 terms in term order on the matrix cores, then the blocks in four slices; no floating-point
+ * atomics): the same inputs give the same bits.  T >= 2 (T = 2: no term, msg = 0). */
+int64_t mpcrl_qlearning_gn_workspace_bytes(int T, int E, int K);
+int mpcrl_qlearning_td_gn(const double *Q, const double *V, const double *dQ_dp, const int32_t *status_q, const int32_t *status_v, const double *cost,
+                          const uint8_t *live, int T, int E, int n_p, double gamma, const int32_t *idx, int K, void *workspace, double *td,
+                          uint8_t *valid, double *msg, void *stream);
+
+/* Added under ABI 132.  After the collective, one launch of one workgroup: n = max(1, count), Gb = G / n, bb = b / n, d_max = max_a Gb_aa.
+ *   count == 0, d_max not finite or d_max == 0:  info = -1, theta untouched, step_out = 0;
+ *   H = Gb + damping diag(Gb_aa > 0 ? Gb_aa : 1e-12 d_max)  (Marquardt's scaling: covariant under a diagonal rescaling of the parameters
+ *   for any damping; the floor is for an entry no term is sensitive to, whose step is 0), fp64 Cholesky; pivot a not a finite number > 0:
+ *   info = a + 1 (1-based), theta untouched, step_out = 0;
+ *   else Delta = lr H^-1 bb, theta[idx[a]] += Delta_a, step_out [n_theta] = Delta at idx and 0 elsewhere, info = 0.
+ * idx as above (device, [K], an entry outside [0, n_theta) is skipped); info [1] int32 on the device; damping >= 0; K <= n_theta. */
+int mpcrl_qlearning_gn_apply(const double *msg, int K, const int32_t *idx, int n_theta, double lr, double damping, double *theta, double *step_out,
+                             int32_t *info, void *stream);
 
 /* Added under ABI 132.  Batched PPO with the MPC as Gaussian actor (ppo_kernel.hpp; mpc4rl_amd/ppo.py), cartpole environment, nu = 1, all
  * arithmetic fp64: a ~ N(mu, sigma^2) with mu = scale_action(u0*) of the solve and sigma = exp(log_std[0]), log_std a DEVICE double the

@@ -20,6 +20,7 @@
 #include "replay_kernel.hpp"
 #include "td3_kernel.hpp"
 #include "qlearning_kernel.hpp"
+#include "qlearning_gn_kernel.hpp"
 #include "ppo_kernel.hpp"
 #include "ppo_chain_kernel.hpp"
 #include "value_kernel.hpp"
@@ -797,6 +798,52 @@ int mpcrl_qlearning_apply(const double *msg, int n_theta, const double *mask, do
     if (!msg || n_theta < 1 || !theta || !step_out) return MPCRL_E_ARG;
     ON_DEVICE_OF(theta);
     hipLaunchKernelGGL(qlearning_apply_kernel, dim3((n_theta + 255) / 256), dim3(256), 0, (hipStream_t)stream, msg, n_theta, mask, theta, step_out);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int64_t mpcrl_qlearning_gn_workspace_bytes(int T, int E, int K) {
+    if (T < 2 || E < 1 || K < 1 || K > GN_KMAX) return MPCRL_E_ARG;
+    return ticket_workspace_bytes((int64_t)(T - 2) * E, TD_ROWS, gn_msg_len(K));
+}
+
+int mpcrl_qlearning_td_gn(const double *Q, const double *V, const double *dQ_dp, const int32_t *status_q, const int32_t *status_v, const double *cost,
+                          const uint8_t *live, int T, int E, int n_p, double gamma, const int32_t *idx, int K, void *workspace, double *td,
+                          uint8_t *valid, double *msg, void *stream) {
+    if (!msg || T < 2 || E < 1 || n_p < 1 || K < 1 || K > GN_KMAX || K > n_p || !idx) return MPCRL_E_ARG;
+    const int64_t M = (int64_t)(T - 2) * E;
+    if (M > 0 && (!Q || !V || !dQ_dp || !status_q || !status_v || !cost || !live || !workspace || !td)) return MPCRL_E_ARG;
+    ON_DEVICE_OF(msg);
+    if (M == 0) {   // no term: an empty message
+        HIP_OK(hipMemsetAsync(msg, 0, (size_t)gn_msg_len(K) * sizeof(double), (hipStream_t)stream));
+        return 0;
+    }
+    if (ticket_blocks(M, TD_ROWS) > 0x7fffffff) return MPCRL_E_ARG;
+    QlGnArgs a;
+    a.Q = Q, a.V = V, a.dQ = dQ_dp, a.sq = (const int *)status_q, a.sv = (const int *)status_v, a.cost = cost, a.live = live;
+    a.idx = (const int *)idx, a.T = T, a.E = E, a.n_p = n_p, a.K = K, a.gamma = gamma, a.td = td, a.valid = valid;
+    a.msg = msg;
+    set_ticket_workspace(a, workspace);
+    const dim3 grid((unsigned)ticket_blocks(M, TD_ROWS)), block(TD_ROWS);
+#define GN_LAUNCH(NC) hipLaunchKernelGGL(qlearning_td_gn_kernel<NC>, grid, block, 0, (hipStream_t)stream, a)
+    switch (K / 16 + 1) {       // the column tiles of [G | b]: ceil((K + 1) / 16)
+        case 1: GN_LAUNCH(1); break;
+        case 2: GN_LAUNCH(2); break;
+        case 3: GN_LAUNCH(3); break;
+        case 4: GN_LAUNCH(4); break;
+        default: GN_LAUNCH(5); break;
+    }
+#undef GN_LAUNCH
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int mpcrl_qlearning_gn_apply(const double *msg, int K, const int32_t *idx, int n_theta, double lr, double damping, double *theta, double *step_out,
+                             int32_t *info, void *stream) {
+    if (!msg || K < 1 || K > GN_KMAX || !idx || n_theta < K || !(lr == lr) || !(damping >= 0.0) || !theta || !step_out || !info) return MPCRL_E_ARG;
+    ON_DEVICE_OF(theta);
+    hipLaunchKernelGGL(qlearning_gn_apply_kernel, dim3(1), dim3(GN_APPLY_NT), 0, (hipStream_t)stream, msg, K, (const int *)idx, n_theta, lr, damping,
+                       theta, step_out, (int *)info);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Callable, Optional
+from typing import Callable, Optional, Tuple
 
 import torch
 
@@ -32,6 +32,74 @@ class EpisodeStats:
     td_error_mean: float
     step: torch.Tensor          # parameter step that was applied
     converged_fraction: float
+    gn_info: int = 0            # method="gauss_newton": info of mpcrl_qlearning_gn_apply (0 stepped, -1 no usable term, a > 0 pivot a failed)
+
+
+GN_KMAX = 64                    # the cap on the learned entries of the Gauss-Newton step (GN_KMAX of csrc/qlearning_gn_kernel.hpp)
+METHODS = ("gradient", "gauss_newton")
+
+
+def gn_msg_len(K: int) -> int:
+    """The length of the Gauss-Newton message [G (upper triangle, K (K + 1) / 2) | b (K) | sum td | count]."""
+    return K * (K + 1) // 2 + K + 2
+
+
+def qlearning_gn_terms(q: torch.Tensor, v: torch.Tensor, dq: torch.Tensor, status_q: torch.Tensor, status_v: torch.Tensor, cost: torch.Tensor,
+                       live: torch.Tensor, gamma: float, idx) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The TD terms and Gauss-Newton sums of one episode in torch float64 (what mpcrl_qlearning_td_gn computes).  The arguments, the terms,
+    ``td`` and ``valid`` are those of ``qlearning_td_terms``; ``idx`` [K]: the learned columns of dq, strictly increasing.  With
+    g = nan_to_num(dq[..., idx]) over the valid terms (an invalid one is selected out) returns
+        msg = [G_ac = sum g_a g_c, a <= c, packed row-major | b_a = sum td g_a | sum td | count],  td [T-2, E],  valid [T-2, E] bool."""
+    from .qlearning_cartpole import qlearning_td_terms       # (that module imports this one)
+    _, td, valid = qlearning_td_terms(q, v, dq, status_q, status_v, cost, live, gamma, 0.0)
+    idx = torch.as_tensor(idx, dtype=torch.int64, device=dq.device).reshape(-1)
+    K, n_t = idx.numel(), td.shape[0]
+    g = torch.nan_to_num(dq[:n_t].to(torch.float64)[..., idx])
+    g = torch.where(valid[..., None], g, torch.zeros_like(g)).reshape(-1, K)
+    G = g.t() @ g
+    b = g.t() @ td.reshape(-1).to(torch.float64)
+    iu = torch.triu_indices(K, K, device=dq.device)            # row-major: (0, 0) .. (0, K-1), (1, 1) ..
+    msg = torch.cat([G[iu[0], iu[1]], b, td.sum().reshape(1).to(torch.float64), valid.sum().to(torch.float64).reshape(1)])
+    return msg, td, valid
+
+
+def qlearning_gn_step(msg: torch.Tensor, K: int, lr: float, damping: float) -> Tuple[torch.Tensor, int]:
+    """The damped Gauss-Newton step of a message in torch float64 (what mpcrl_qlearning_gn_apply computes before it scatters):
+    n = max(1, count), Gb = G / n, bb = b / n, d_max = max_a Gb_aa;  H = Gb + damping diag(Gb_aa > 0 ? Gb_aa : 1e-12 d_max) (Marquardt's
+    scaling: the step is covariant under a diagonal rescaling of the parameters for any damping; the floor is for an entry no term is
+    sensitive to, whose step is 0 whatever it is);  delta = lr H^-1 bb by a Cholesky factorisation.
+    Returns (delta [K], info): info = -1 (count 0, or d_max not finite or 0) or a + 1 (pivot a is no finite number > 0) with delta = 0,
+    else 0."""
+    msg = msg.to(torch.float64)
+    KK = K * (K + 1) // 2
+    count = float(msg[KK + K + 1])
+    n = max(1.0, count)
+    iu = torch.triu_indices(K, K, device=msg.device)
+    H = torch.zeros(K, K, dtype=torch.float64, device=msg.device)
+    H[iu[0], iu[1]] = msg[:KK] / n
+    H = torch.triu(H, 1).t() + H
+    y = msg[KK: KK + K] / n
+    zero = torch.zeros(K, dtype=torch.float64, device=msg.device)
+    d = torch.diagonal(H).clone()
+    d_max = float(d.max())                                      # (torch.max propagates a NaN)
+    if not count > 0.0 or not math.isfinite(d_max) or d_max == 0.0:
+        return zero, -1
+    H = H + damping * torch.diag(torch.where(d > 0.0, d, torch.full_like(d, 1e-12 * d_max)))
+    for k in range(K):                                          # right-looking, a column at a time (the kernel's order)
+        piv = float(H[k, k])
+        if not (math.isfinite(piv) and piv > 0.0):
+            return zero, k + 1
+        l = math.sqrt(piv)
+        H[k, k] = l
+        H[k + 1:, k] = H[k + 1:, k] / l
+        H[k + 1:, k + 1:] -= torch.outer(H[k + 1:, k], H[k + 1:, k])
+    for k in range(K):
+        y[k] = y[k] / H[k, k]
+        y[k + 1:] -= H[k + 1:, k] * y[k]
+    for k in range(K - 1, -1, -1):
+        y[k] = y[k] / H[k, k]
+        y[:k] -= H[k, :k] * y[k]
+    return lr * y, 0
 
 
 class BatchedQLearning:
@@ -99,6 +167,13 @@ class DeviceQLearning:
     sum lr td, count] of distributed.mean_update).  With several ranks only that message is all-reduced; then mpcrl_qlearning_apply
     takes the mean and steps theta.
 
+    ``method="gauss_newton"`` replaces that first-order step by the least-squares TD step over the entries ``learn_mask`` marks,
+    delta = lr (G/n + damping diag(G/n))^-1 (b/n) with G = sum g g', b = sum td g, g = dQ/dp on those entries: mpcrl_qlearning_td_gn in
+    the sweep (the message [G | b | sum td | count], additive: still one collective) and mpcrl_qlearning_gn_apply after it.  The step is
+    covariant under a rescaling of the parameters, so ``lr`` in (0, 1] means the same on every model; ``damping`` >= 0 is Marquardt's.  At
+    most 64 entries can be learned that way (the factorisation is one workgroup's, in LDS).  The entries are read from ``learn_mask`` at
+    the first sweep (or ``enable_graphs``) and kept.  ``EpisodeStats.gn_info`` reports a step that was not taken.
+
     A plant's class sets ``NX``, ``_COLLECT`` and, with more than one control, ``NU``, checks its OCP and environment, allocates
     ``live`` [T, E] (and what else its collect kernel needs) after this constructor, and defines ``_collect(r)`` (the collect launch
     after the roll-out solve r; returns its status), ``_stats()``, where the environment carries more than its state from step to step
@@ -112,8 +187,12 @@ class DeviceQLearning:
     _COLLECT: str = ""      # the library's collect entry point (for error messages)
 
     def __init__(self, ocp, env, episode_length: int, lr: float, gamma: float, noise_scale: float, seed: int, device, group,
-                 mpc_gamma: Optional[float] = None):
+                 mpc_gamma: Optional[float] = None, method: str = "gradient", damping: float = 1e-3):
         name = type(self).__name__
+        if method not in METHODS:
+            raise ValueError(f"method: unknown {method!r} (one of {', '.join(METHODS)})")
+        if isinstance(damping, bool) or not isinstance(damping, (int, float)) or not (math.isfinite(damping) and damping >= 0.0):
+            raise ValueError("damping must be finite and >= 0")
         if isinstance(episode_length, bool) or not isinstance(episode_length, int) or episode_length < 2:
             raise ValueError("episode_length must be an int >= 2 (a TD term needs two samples)")
         if not math.isfinite(lr):
@@ -131,6 +210,9 @@ class DeviceQLearning:
             raise ValueError("the environment must live on the learner's device (its state is updated in place by the library)")
         self.ocp, self.env, self.T, self.lr, self.gamma, self.noise_scale = ocp, env, episode_length, float(lr), float(gamma), float(noise_scale)
         self.E, self.device, self.group = env.num_envs, dev, group
+        self.method, self.damping = method, float(damping)
+        self.learn_idx = None               # gauss_newton: the learned entries [K] int32, built from learn_mask at the first sweep
+        self.gn_info = torch.zeros(1, dtype=torch.int32, device=dev)
         T, E, NX, NU = self.T, self.E, self.NX, self.NU
         if ocp.nu != NU:
             raise ValueError(f"{name} is written for {NU} control(s), the OCP has {ocp.nu}")
@@ -202,7 +284,26 @@ class DeviceQLearning:
             raise RuntimeError(f"{self._COLLECT} failed with {rc}")
         return r
 
+    def _gn_setup(self) -> None:
+        """The learned entries and the buffers of the Gauss-Newton step, from ``learn_mask`` as it stands (a plant's class sets it after
+        this constructor).  Runs once, before anything is captured; the buffers keep their addresses from then on."""
+        if self.learn_idx is not None:
+            return
+        idx = torch.nonzero(self.learn_mask != 0.0).reshape(-1)
+        K = int(idx.numel())
+        if K < 1 or K > GN_KMAX:
+            raise ValueError(f"method='gauss_newton' learns between 1 and {GN_KMAX} entries of theta; learn_mask marks {K}")
+        nb = int(self._lib.mpcrl_qlearning_gn_workspace_bytes(self.T, self.E, K))
+        if nb < 0:
+            raise RuntimeError(f"mpcrl_qlearning_gn_workspace_bytes failed with {nb}")
+        self.K = K
+        self.msg = torch.zeros(gn_msg_len(K), dtype=torch.float64, device=self.device)
+        self._gn_ws = torch.zeros(nb, dtype=torch.uint8, device=self.device)
+        self.learn_idx = idx.to(torch.int32).contiguous()
+
     def _sweep(self):
+        if self.method == "gauss_newton":
+            self._gn_setup()
         n = self.T - 1
         s = self.S[:n].reshape(n * self.E, self.NX)
         a = self.A[:n].reshape(n * self.E, self.NU)
@@ -210,6 +311,15 @@ class DeviceQLearning:
         rq = self.sample_mpc.solve(s, u0=a, sens_v=True, cold=True, store_bounds=False)
         # ... update: V(s_i) from the Q solve's primal iterate, interior point from its default point
         rv = self.sample_mpc.solve(s)
+        if self.method == "gauss_newton":
+            with torch.cuda.device(self.device):
+                rc = self._lib.mpcrl_qlearning_td_gn(
+                    _ptr(rq.V), _ptr(rv.V), _ptr(rq.dV_dp), _ptr(rq.status), _ptr(rv.status), _ptr(self.C), _ptr(self.live), self.T, self.E,
+                    self.n_p, self.gamma, _ptr(self.learn_idx), self.K, _ptr(self._gn_ws), _ptr(self.td), _ptr(self.valid), _ptr(self.msg),
+                    self._stream())
+            if rc != 0:
+                raise RuntimeError(f"mpcrl_qlearning_td_gn failed with {rc}")
+            return rq, rv
         with torch.cuda.device(self.device):
             rc = self._lib.mpcrl_qlearning_td_grad(
                 _ptr(rq.V), _ptr(rv.V), _ptr(rq.dV_dp), _ptr(rq.status), _ptr(rv.status), _ptr(self.C), _ptr(self.live), self.T, self.E, self.n_p,
@@ -224,11 +334,18 @@ class DeviceQLearning:
             dist.all_reduce(self.msg, op=dist.ReduceOp.SUM, group=self.group)
 
     def _apply(self) -> None:
-        with torch.cuda.device(self.device):
-            rc = self._lib.mpcrl_qlearning_apply(_ptr(self.msg), self.n_p, _ptr(self.learn_mask), _ptr(self.theta), _ptr(self.step_out),
-                                                 self._stream())
-        if rc != 0:
-            raise RuntimeError(f"mpcrl_qlearning_apply failed with {rc}")
+        if self.method == "gauss_newton":
+            with torch.cuda.device(self.device):
+                rc = self._lib.mpcrl_qlearning_gn_apply(_ptr(self.msg), self.K, _ptr(self.learn_idx), self.n_p, self.lr, self.damping,
+                                                        _ptr(self.theta), _ptr(self.step_out), _ptr(self.gn_info), self._stream())
+            if rc != 0:
+                raise RuntimeError(f"mpcrl_qlearning_gn_apply failed with {rc}")
+        else:
+            with torch.cuda.device(self.device):
+                rc = self._lib.mpcrl_qlearning_apply(_ptr(self.msg), self.n_p, _ptr(self.learn_mask), _ptr(self.theta), _ptr(self.step_out),
+                                                     self._stream())
+            if rc != 0:
+                raise RuntimeError(f"mpcrl_qlearning_apply failed with {rc}")
         for m in (self.rollout_mpc, self.sample_mpc):
             m.set_theta(self.theta)                                    # mpc.set_parameter
 
@@ -257,7 +374,10 @@ class DeviceQLearning:
         self._allreduce()                                               # the one collective of an episode (world > 1)
         self._apply()
         self.episodes += 1
-        return self._stats()
+        stats = self._stats()
+        if self.method == "gauss_newton":
+            stats.gn_info = int(self.gn_info.item())
+        return stats
 
     # ------------------------------------------------------------------ HIP graphs
     def enable_graphs(self) -> None:
@@ -267,6 +387,8 @@ class DeviceQLearning:
         environment's state is put back afterwards, and nothing else the learner carries from one episode to the next is touched by it."""
         if self._graphs is not None:
             return
+        if self.method == "gauss_newton":
+            self._gn_setup()
         dev = self.device
         snap = [t.clone() for t in self._env_carried()]
         side = torch.cuda.Stream(device=dev)

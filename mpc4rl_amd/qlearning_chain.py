@@ -118,6 +118,8 @@ class ChainQLearning(DeviceQLearning):
     the dynamics block only: an unconstrained gradient step on Q or R can leave the cone of positive semi-definite matrices, after which
     the OCP is no longer convex in the cost.  ``lr``: the default is 1e-6.  The gradient's scale grows quickly with the chain: with every
     entry learned, ``lr = 1e-4`` moved the dynamics block by 6e-5 at n_mass 3 but by 0.045 at n_mass 5, where m itself is 0.033.
+    ``method="gauss_newton"`` (``DeviceQLearning``) takes the damped least-squares TD step instead, whose ``lr`` in (0, 1] does not depend
+    on the parameters' units; it learns at most 64 entries (m, D, L, C are 20 at n_mass 3 and 40 at n_mass 5; Q alone is 81 or more).
 
     Sizing: ``sample_mpc`` holds E (T - 1) chain instances, each with its trajectories and factorisation workspace — about 2 MB each at
     n_mass 5, N 40, so E = 256, T = 5 (1024 instances, the benchmark's chain5 batch) is about 2 GB.  ``workspace_bytes()`` returns
@@ -128,7 +130,7 @@ class ChainQLearning(DeviceQLearning):
     BLOCKS = ("m", "D", "L", "C", "Q", "R", "w")
 
     def __init__(self, ocp, env, episode_length: int, lr: float = 1e-6, gamma: Optional[float] = None, noise_scale: float = 0.0, seed: int = 0,
-                 device=None, group=None, learn: Sequence[str] = ("m", "D", "L", "C")):
+                 device=None, group=None, learn: Sequence[str] = ("m", "D", "L", "C"), method: str = "gradient", damping: float = 1e-3):
         if getattr(ocp, "model", None) != _lib.MODEL_CHAIN or ocp.nu != 3:
             raise ValueError("ChainQLearning needs the chain-of-masses OCP (chain_mass_ocp())")
         if not isinstance(env, BatchedChainMassEnv):
@@ -142,12 +144,15 @@ class ChainQLearning(DeviceQLearning):
                 raise ValueError(f"learn: unknown block {key!r} (one of {', '.join(self.BLOCKS)})")
         self.NX = ocp.nx                                                     # per instance: the chain's size sets the state's width
         gamma = ocp.gamma if gamma is None else gamma
-        super().__init__(ocp, env, episode_length, lr, gamma, noise_scale, seed, device, group, mpc_gamma=gamma)
+        super().__init__(ocp, env, episode_length, lr, gamma, noise_scale, seed, device, group, mpc_gamma=gamma, method=method,
+                         damping=damping)
         self.n_mass, self.Ts, self.rk_steps, self.M, self.learn = n_mass, Ts, rk_steps, n_mass - 2, learn
         off = chain_param_layout(n_mass)[4]
         self.learn_mask.zero_()
         for key in learn:
             self.learn_mask[off[key][0]: off[key][1]] = 1.0
+        if method == "gauss_newton":
+            self._gn_setup()                                                 # (refuses more than 64 learned entries here, not at the first sweep)
         self.wn = torch.zeros(self.T, self.E, 3 * self.M, dtype=torch.float64, device=self.device)
         self.live = torch.ones(self.T, self.E, dtype=torch.uint8, device=self.device)    # the plant never terminates: every row is a sample
 

@@ -1,0 +1,214 @@
+"""CPU checks of the Q-learners' Gauss-Newton (least-squares TD) step: the C ABI's new symbols, the torch statements ``qlearning_gn_terms``
+and ``qlearning_gn_step`` of the two kernels against a brute-force loop over the terms and against ``np.linalg.solve``, the step's
+covariance under a rescaling of the parameters, and the constructor's argument checks.
+
+Bounds (derived, not measured), eps = 2^-53:
+  sums   |G_ac - G_ref,ac| <= 4 M eps sum_j |g_ja g_jc| over the M terms (any summation order), likewise b with |td_j g_ja|;
+  solve  ||d - d_ref||_2 <= 8 K (K + 1) eps cond_2(H) ||d_ref||_2 (backward stability of Cholesky, on both sides)."""
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ["mpcrl_qlearning_gn_workspace_bytes", "mpcrl_qlearning_td_gn", "mpcrl_qlearning_gn_apply"]
+EPS = 2.0 ** -53
+
+
+def test_new_symbols_in_header_and_binding_abi132():
+    from mpc4rl_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "mpcrl.h")).read()
+    api = open(os.path.join(ROOT, "mpc4rl_amd", "csrc", "mpcrl_api.hip")).read()
+    for name in NEW:
+        assert re.search(r"\b" + name + r"\(", hdr), name
+        assert re.search(r"\b" + name + r"\(", api), name
+        assert name in _lib.EXPORTS, name
+    assert int(re.search(r"#define MPCRL_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 132
+    if os.path.exists(_lib.LIB_PATH):
+        lib = _lib.load()
+        assert lib.mpcrl_version() == 132
+        for name in NEW:
+            getattr(lib, name)
+
+
+def make_table(T, E, n_p, idx, seed):
+    """An episode table with every kind of term: live columns that end after 1 and after 2 rows (and other lengths), failed Q and V solves
+    with NaN in their Q, V and dQ, NaN in the rows of dead environments, and one NaN inside a valid row's unlearned column."""
+    rng = np.random.default_rng(seed)
+    L = rng.integers(3, T + 1, E)
+    L[0], L[1 % E] = 1, 2
+    if E > 2:
+        L[2] = T
+    live = (np.arange(T)[:, None] < L[None, :]).astype(np.uint8)
+    cost = rng.uniform(0, 5, (T, E)) * live
+    q, v = rng.normal(size=(T - 1, E)), rng.normal(size=(T - 1, E))
+    dq = rng.normal(size=(T - 1, E, n_p)) * 10.0 ** rng.integers(-2, 3, n_p)
+    sq = np.where(rng.uniform(size=(T - 1, E)) < 0.15, 2, 0).astype(np.int32)
+    sv = np.where(rng.uniform(size=(T - 1, E)) < 0.1, 4, 0).astype(np.int32)
+    if E > 2:
+        sq[:, 2], sv[:, 2] = 0, 0                                   # one environment whose terms are all valid
+    q[sq != 0], v[sv != 0], dq[sq != 0] = np.nan, np.nan, np.nan
+    dead = live[: T - 1] == 0
+    q[dead], v[dead], dq[dead] = np.nan, np.nan, np.nan
+    free = [c for c in range(n_p) if c not in set(idx)]
+    if free and E > 2 and T > 2:
+        dq[0, 2, free[0]] = np.nan                                  # valid row, unlearned column: never read
+    return q, v, dq, sq, sv, cost, live
+
+
+def brute_force(q, v, dq, sq, sv, cost, live, gamma, idx):
+    """A loop over the terms: exact sums (math.fsum) of the valid terms' products, and the sums of their absolute values."""
+    T, E = cost.shape
+    K = len(idx)
+    prods = {(a, c): [] for a in range(K) for c in range(a, K)}
+    bprods = {a: [] for a in range(K)}
+    tds, terms = [], {}
+    for i in range(T - 2):
+        for e in range(E):
+            if not (live[i, e] and live[i + 1, e] and live[i + 2, e]):
+                continue
+            if sq[i, e] or sv[i, e] or sq[i + 1, e] or sv[i + 1, e]:
+                continue
+            td = cost[i, e] + gamma * v[i + 1, e] - q[i, e]
+            g = np.nan_to_num(dq[i, e, idx])
+            terms[(i, e)] = td
+            tds.append(td)
+            for a in range(K):
+                bprods[a].append(td * g[a])
+                for c in range(a, K):
+                    prods[(a, c)].append(g[a] * g[c])
+    G = np.array([math.fsum(prods[(a, c)]) for a in range(K) for c in range(a, K)])
+    Gabs = np.array([math.fsum(map(abs, prods[(a, c)])) for a in range(K) for c in range(a, K)])
+    b = np.array([math.fsum(bprods[a]) for a in range(K)])
+    babs = np.array([math.fsum(map(abs, bprods[a])) for a in range(K)])
+    return G, Gabs, b, babs, math.fsum(tds), math.fsum(map(abs, tds)), terms
+
+
+def _t(arrs):
+    return [torch.as_tensor(a) for a in arrs]
+
+
+def test_gn_terms_match_brute_force():
+    from mpc4rl_amd import qlearning_gn_terms, qlearning_td_terms
+    T, E, n_p, idx, gamma = 5, 7, 9, [0, 3, 4, 8], 0.97
+    d = make_table(T, E, n_p, idx, 5)
+    msg, td, valid = qlearning_gn_terms(*_t(d), gamma, idx)
+    _, td0, valid0 = qlearning_td_terms(*_t(d), gamma, 1e-3)
+    assert torch.equal(td, td0) and torch.equal(valid, valid0)
+    G, Gabs, b, babs, ts, tabs, terms = brute_force(*d, gamma, idx)
+    K, M = len(idx), (T - 2) * E
+    KK = K * (K + 1) // 2
+    assert msg.shape == (KK + K + 2,) and torch.isfinite(msg).all()
+    assert 0 < len(terms) < M                                          # valid and invalid terms both occur
+    assert int(msg[-1]) == len(terms) == int(valid.sum())
+    assert {(int(i), int(e)) for i, e in zip(*np.nonzero(valid.numpy()))} == set(terms)
+    m = msg.numpy()
+    assert (np.abs(m[:KK] - G) <= 4 * M * EPS * Gabs).all()
+    assert (np.abs(m[KK: KK + K] - b) <= 4 * M * EPS * babs).all()
+    assert abs(m[KK + K] - ts) <= 4 * M * EPS * tabs
+    # the packing: row-major upper triangle
+    assert abs(m[K] - math.fsum(np.nan_to_num(d[2][i, e, idx[1]]) ** 2 for (i, e) in terms)) <= 4 * M * EPS * Gabs[K]
+
+
+def test_gn_message_is_additive_over_environments():
+    from mpc4rl_amd import qlearning_gn_terms
+    T, E, n_p, idx, gamma = 6, 10, 7, [1, 2, 5], 0.99
+    d = make_table(T, E, n_p, idx, 11)
+    whole = qlearning_gn_terms(*_t(d), gamma, idx)[0].numpy()
+    h = E // 2
+    parts = [qlearning_gn_terms(*_t([a[:, sl] for a in d]), gamma, idx)[0].numpy() for sl in (slice(0, h), slice(h, E))]
+    G, Gabs, b, babs, ts, tabs, terms = brute_force(*d, gamma, idx)
+    bound = 4 * (T - 2) * E * EPS * np.concatenate([Gabs, babs, [tabs], [0.0]])
+    got = parts[0] + parts[1]
+    assert got[-1] == whole[-1] == len(terms)
+    assert (np.abs(got - whole) <= 2 * bound).all()                 # each side is within `bound` of the exact sums
+
+
+def _message(G, b, count):
+    K = G.shape[0]
+    iu = np.triu_indices(K)
+    return torch.as_tensor(np.concatenate([G[iu], b, [0.0], [float(count)]]))
+
+
+def _h_of(G, count, damping):
+    Gb = G / max(1.0, count)
+    d = np.diag(Gb)
+    return Gb + damping * np.diag(np.where(d > 0, d, 1e-12 * d.max()))
+
+
+@pytest.mark.parametrize("K", [1, 2, 17, 64])
+@pytest.mark.parametrize("damping", [0.0, 1e-3])
+def test_gn_step_matches_numpy_solve(K, damping):
+    from mpc4rl_amd import qlearning_gn_step
+    rng = np.random.default_rng(K)
+    M, lr = 4 * K + 3, 0.5
+    g = rng.normal(size=(M, K)) * 10.0 ** rng.uniform(-2, 2, K)
+    td = rng.normal(size=M)
+    G, b = g.T @ g, g.T @ td
+    delta, info = qlearning_gn_step(_message(G, b, M), K, lr, damping)
+    H = _h_of(G, M, damping)
+    ref = lr * np.linalg.solve(H, b / M)
+    assert info == 0
+    err, bound = np.linalg.norm(delta.numpy() - ref), 8 * K * (K + 1) * EPS * np.linalg.cond(H) * np.linalg.norm(ref)
+    print(f"K {K} damping {damping}: err {err:.3e} bound {bound:.3e}")
+    assert err <= bound
+
+
+def test_gn_step_singular_damped_and_empty():
+    from mpc4rl_amd import qlearning_gn_step
+    rng = np.random.default_rng(0)
+    K, M = 5, 40
+    g = rng.normal(size=(M, K))
+    g[:, 3] = 0.0                                                   # an entry no term is sensitive to: G has a zero row and column
+    td = rng.normal(size=M)
+    G, b = g.T @ g, g.T @ td
+    delta, info = qlearning_gn_step(_message(G, b, M), K, 1.0, 0.0)
+    assert info == 4 and float(delta.abs().sum()) == 0.0
+    delta, info = qlearning_gn_step(_message(G, b, M), K, 1.0, 1e-3)
+    assert info == 0 and float(delta[3]) == 0.0
+    H = _h_of(G, M, 1e-3)
+    ref = np.linalg.solve(H, b / M)
+    assert np.linalg.norm(delta.numpy() - ref) <= 8 * K * (K + 1) * EPS * np.linalg.cond(H) * np.linalg.norm(ref)
+    # no valid term / a NaN or zero diagonal
+    for msg in (_message(G, b, 0), _message(np.zeros((K, K)), b, M), _message(np.where(np.eye(K) > 0, np.nan, G), b, M)):
+        delta, info = qlearning_gn_step(msg, K, 1.0, 1e-3)
+        assert info == -1 and float(delta.abs().sum()) == 0.0
+
+
+def test_gn_step_is_covariant_under_parameter_rescaling():
+    """Scaling column a of dQ/dp by s_a = 2^k, k in -20 .. 20 (a parameter measured in other units), scales delta_a by 1 / s_a."""
+    from mpc4rl_amd import qlearning_gn_step, qlearning_gn_terms
+    T, E, n_p, gamma = 6, 9, 8, 0.99
+    idx = [0, 1, 2, 4, 5, 7]
+    K = len(idx)
+    d = list(make_table(T, E, n_p, idx, 3))
+    rng = np.random.default_rng(1)
+    k = rng.integers(-20, 21, n_p)
+    k[idx[0]], k[idx[1]] = -20, 20                                  # both ends of the range
+    s = 2.0 ** k
+    base, info0 = qlearning_gn_step(qlearning_gn_terms(*_t(d), gamma, idx)[0], K, 0.7, 1e-3)
+    d[2] = d[2] * s
+    scaled, info1 = qlearning_gn_step(qlearning_gn_terms(*_t(d), gamma, idx)[0], K, 0.7, 1e-3)
+    assert info0 == 0 and info1 == 0 and float(base.abs().min()) > 0.0
+    rel = (scaled * torch.as_tensor(s[idx]) - base).abs() / base.abs()
+    print("covariance: max relative deviation", float(rel.max()))
+    assert float(rel.max()) <= 1e-12
+
+
+def test_constructor_checks_come_before_the_device_check():
+    from mpc4rl_amd import (BatchedCartPoleSwingUpEnv, BatchedChainMassEnv, BatchedLinearSystemEnv, CartpoleQLearning, ChainQLearning,
+                            LinearQLearning, cartpole_ocp, chain_mass_ocp, linear_system_ocp)
+    cases = [(CartpoleQLearning, cartpole_ocp(), BatchedCartPoleSwingUpEnv(4, device="cpu")),
+             (LinearQLearning, linear_system_ocp(), BatchedLinearSystemEnv(4, device="cpu"))]
+    ocp = chain_mass_ocp(n_mass=3, N=10)
+    cases.append((ChainQLearning, ocp, BatchedChainMassEnv(4, ocp, device="cpu")))
+    for cls, ocp, env in cases:
+        for kw in (dict(method="newton"), dict(method=None), dict(method="gauss_newton", damping=-1e-3),
+                   dict(method="gauss_newton", damping=float("nan")), dict(damping=float("inf")), dict(damping="1e-3")):
+            with pytest.raises(ValueError):
+                cls(ocp, env, 6, **kw)
+        with pytest.raises(RuntimeError, match="no CPU fallback"):        # valid arguments, CPU environment: refused, never emulated
+            cls(ocp, env, 6, method="gauss_newton", damping=0.0)
