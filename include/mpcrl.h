@@ -34,7 +34,8 @@
  *   sweep; mpc.set_p(p + mean)                                  mpcrl_qlearning_apply
  *     scripts/cartpole_mpc_qlearning.py:255-269
  *   (none: the reference steps p by LR td dQ_dp only)          mpcrl_qlearning_td_gn / mpcrl_qlearning_gn_workspace_bytes,
- *   the same sweep's Gauss-Newton (least-squares TD) step        mpcrl_qlearning_gn_apply
+ *   the same sweep's Gauss-Newton (least-squares TD) step        mpcrl_qlearning_gn_apply, and inside bounds on the parameters
+ *                                                                and a trust region: mpcrl_qlearning_gn_apply_box
  *   MPCActorCriticPolicy.forward / evaluate_actions /          mpcrl_ppo_cartpole_collect, mpcrl_ppo_gae,
  *   predict_values (NotImplementedError in the reference)       mpcrl_ppo_surrogate_grad / mpcrl_ppo_surrogate_workspace_bytes,
  *   and the PPO roll-out / update around them                   mpcrl_ppo_log_std_apply,
@@ -104,7 +105,8 @@ extern "C" {
  *        PPO roll-out steps); mpcrl_env_chain_step; mpcrl_qlearning_chain_collect (the chain of masses as a plant and its Q-learning
  *        roll-out step); mpcrl_ppo_chain_collect; mpcrl_ppo_surrogate_grad_nu / mpcrl_ppo_surrogate_workspace_bytes_nu;
  *        mpcrl_ppo_log_std_apply_nu (PPO on the chain of masses: a diagonal Gaussian over its three controls);
- *        mpcrl_qlearning_td_gn / mpcrl_qlearning_gn_workspace_bytes; mpcrl_qlearning_gn_apply (the Q-learners' Gauss-Newton step) */
+ *        mpcrl_qlearning_td_gn / mpcrl_qlearning_gn_workspace_bytes; mpcrl_qlearning_gn_apply (the Q-learners' Gauss-Newton step);
+ *        mpcrl_qlearning_gn_apply_box (that step as a box QP: bounds on theta and a per-entry trust region) */
 #define MPCRL_ABI_VERSION 132
 
 enum { MPCRL_MODEL_CARTPOLE = 0, MPCRL_MODEL_LINEAR = 1, MPCRL_MODEL_CHAIN = 2 };
@@ -431,6 +433,24 @@ int mpcrl_qlearning_td_gn(const double *Q, const double *V, const double *dQ_dp,
  * idx as above (device, [K], an entry outside [0, n_theta) is skipped); info [1] int32 on the device; damping >= 0; K <= n_theta. */
 int mpcrl_qlearning_gn_apply(const double *msg, int K, const int32_t *idx, int n_theta, double lr, double damping, double *theta, double *step_out,
                              int32_t *info, void *stream);
+
+/* Added under ABI 132.  The same step inside a box and a per-entry trust region, one launch of one workgroup.  msg, K, idx, n_theta, lr,
+ * damping, H, bb and the codes -1 and a + 1 (1-based; H is factored whole first) as mpcrl_qlearning_gn_apply; lr and damping finite.
+ *   Delta = argmin 1/2 D' H D - lr bb' D   subject to  l_a <= D_a <= u_a  for the K learned entries a, c = idx[a]:
+ *   l_a = max(lo[c] - theta[c], -radius scale[c]),   u_a = min(hi[c] - theta[c], +radius scale[c])
+ * lo, hi, scale [n_theta] doubles on the device, read at idx only; lo, hi may be -+inf, radius +inf (no trust region), scale > 0.  A
+ * strictly convex box QP, solved exactly by a primal active-set method from clamp(0, l, u) (theta may start outside [lo, hi]: the step
+ * moves it back), one fp64 Cholesky of the free block per iteration.  With no bound active this is mpcrl_qlearning_gn_apply's Delta.
+ *   info [2] int32 on the device = {code, iterations}.  code 0: theta[c] = min(max(theta[c] + Delta_a, lo[c]), hi[c]), so lo <= theta <= hi
+ *   holds exactly; step_out [n_theta] = Delta at idx (an entry on a bound: l_a or u_a bit for bit) and 0 elsewhere; active [K] uint8 on the
+ *   device = 0 free, 1 at l_a, 2 at u_a.
+ *   code -1 (no usable term), -2 (l_a > u_a for some a, or one of them NaN), -3 (the iteration cap, 8 K + 16: not reached by a problem
+ *   the tests know), a + 1 (a pivot of entry a is no finite number > 0):  theta untouched, step_out = 0, active = 0.
+ * Fixed order, no atomics: the same inputs give the same bits.  MPCRL_E_ARG: K outside 1..64, K > n_theta, a NULL pointer, lr or damping
+ * not finite, damping < 0, radius not > 0 (NaN included). */
+int mpcrl_qlearning_gn_apply_box(const double *msg, int K, const int32_t *idx, int n_theta, double lr, double damping, const double *lo, const double *hi,
+                                 const double *scale, double radius, double *theta, double *step_out, uint8_t *active /* [K]: 0 free, 1 at l, 2 at u */,
+                                 int32_t *info /* [2]: code, iterations */, void *stream);
 
 /* Added under ABI 132.  Batched PPO with the MPC as Gaussian actor (ppo_kernel.hpp; mpc4rl_amd/ppo.py), cartpole environment, nu = 1, all
  * arithmetic fp64: a ~ N(mu, sigma^2) with mu = scale_action(u0*) of the solve and sigma = exp(log_std[0]), log_std a DEVICE double the

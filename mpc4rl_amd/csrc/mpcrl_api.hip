@@ -848,6 +848,18 @@ int mpcrl_qlearning_gn_apply(const double *msg, int K, const int32_t *idx, int n
     return 0;
 }
 
+int mpcrl_qlearning_gn_apply_box(const double *msg, int K, const int32_t *idx, int n_theta, double lr, double damping, const double *lo, const double *hi,
+                                 const double *scale, double radius, double *theta, double *step_out, uint8_t *active, int32_t *info, void *stream) {
+    if (!msg || K < 1 || K > GN_KMAX || !idx || n_theta < K || !std::isfinite(lr) || !(std::isfinite(damping) && damping >= 0.0) || !lo || !hi ||
+        !scale || !(radius > 0.0) || !theta || !step_out || !active || !info)
+        return MPCRL_E_ARG;
+    ON_DEVICE_OF(theta);
+    hipLaunchKernelGGL(qlearning_gn_apply_box_kernel, dim3(1), dim3(GN_APPLY_NT), 0, (hipStream_t)stream, msg, K, (const int *)idx, n_theta, lr, damping,
+                       lo, hi, scale, radius, theta, step_out, active, (int *)info);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 int mpcrl_ppo_cartpole_collect(const double *par, int E, int T, int t, double *state, int64_t *steps, const double *u0, const int32_t *status,
                                const float *eps, const double *u01, const double *value, const double *log_std, double lo, double hi,
                                double reward_scale, double *OBS, double *ACT, double *LOGP, double *VAL, double *REW, double *NEXT, uint8_t *TERM,

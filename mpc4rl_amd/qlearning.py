@@ -33,6 +33,8 @@ class EpisodeStats:
     step: torch.Tensor          # parameter step that was applied
     converged_fraction: float
     gn_info: int = 0            # method="gauss_newton": info of mpcrl_qlearning_gn_apply (0 stepped, -1 no usable term, a > 0 pivot a failed)
+    gn_active: int = 0          # with bounds or a trust region: the entries of the step that sit on a bound ...
+    gn_iterations: int = 0      # ... and the active-set iterations of mpcrl_qlearning_gn_apply_box (gn_info -2: empty box, -3: iteration cap)
 
 
 GN_KMAX = 64                    # the cap on the learned entries of the Gauss-Newton step (GN_KMAX of csrc/qlearning_gn_kernel.hpp)
@@ -85,10 +87,21 @@ def qlearning_gn_step(msg: torch.Tensor, K: int, lr: float, damping: float) -> T
     if not count > 0.0 or not math.isfinite(d_max) or d_max == 0.0:
         return zero, -1
     H = H + damping * torch.diag(torch.where(d > 0.0, d, torch.full_like(d, 1e-12 * d_max)))
-    for k in range(K):                                          # right-looking, a column at a time (the kernel's order)
+    fail = _gn_chol_solve(H, y)
+    if fail >= 0:
+        return zero, fail + 1
+    return lr * y, 0
+
+
+def _gn_chol_solve(H: torch.Tensor, y: torch.Tensor) -> int:
+    """gn_chol_solve of csrc/qlearning_gn_kernel.hpp: the Cholesky factorisation H = L L' in place (right-looking, a column at a time,
+    the kernel's order), then y <- H^-1 y.  Returns -1, or the index of the first pivot that is no finite number > 0 (H and y are then
+    left half done)."""
+    K = H.shape[0]
+    for k in range(K):
         piv = float(H[k, k])
         if not (math.isfinite(piv) and piv > 0.0):
-            return zero, k + 1
+            return k
         l = math.sqrt(piv)
         H[k, k] = l
         H[k + 1:, k] = H[k + 1:, k] / l
@@ -99,7 +112,110 @@ def qlearning_gn_step(msg: torch.Tensor, K: int, lr: float, damping: float) -> T
     for k in range(K - 1, -1, -1):
         y[k] = y[k] / H[k, k]
         y[:k] -= H[k, :k] * y[k]
-    return lr * y, 0
+    return -1
+
+
+def gn_box_iteration_cap(K: int) -> int:
+    """The cap on the active-set iterations of the box-constrained Gauss-Newton step (gn_box_iteration_cap of
+    csrc/qlearning_gn_kernel.hpp, where it is explained)."""
+    return 8 * K + 16
+
+
+def qlearning_gn_box_step(msg: torch.Tensor, K: int, lr: float, damping: float, lo: torch.Tensor, hi: torch.Tensor, scale: torch.Tensor,
+                          radius: float, theta_idx: torch.Tensor, with_iterations: bool = False):
+    """The Gauss-Newton step of a message inside a box and a per-entry trust region, in torch float64 on the CPU (what
+    mpcrl_qlearning_gn_apply_box computes before it scatters; the only CPU path).  With H and bb of ``qlearning_gn_step``,
+        delta = argmin 1/2 d' H d - lr bb' d   subject to  l <= d <= u,
+        l_a = max(lo_a - theta_a, -radius scale_a),  u_a = min(hi_a - theta_a, +radius scale_a)
+    where ``lo``, ``hi``, ``scale`` and ``theta_idx`` [K] are the bounds, the trust region's scales and theta AT THE LEARNED ENTRIES
+    (``lo[idx]`` ...); lo, hi may be -+inf, radius +inf.  A strictly convex box QP, solved exactly by a primal active-set method:
+      x = clamp(0, l, u), the entries that start on a bound are active (1 at l, 2 at u); H is factored whole first (its pivot codes);
+      every iteration solves the free block, H_FF z = lr bb_F - H_FB x_B, by ``_gn_chol_solve``;
+      if some z_a leaves [l_a, u_a], x moves towards z up to the first blocking bound (lowest entry on a tie), which it takes exactly
+      and which becomes active;
+      else x_F = z, and with the multipliers r = H x - lr bb the active entry with l_a < u_a whose r_a has the wrong sign by more than
+      tol_a / 2, tol_a = 4 (3 K + 1) eps (sum_c sqrt(H_aa H_cc) |x_c| + lr |bb_a|) (the backward error of the solve: a multiplier
+      below it is rounding), and the largest such r_a / sqrt(H_aa) (covariant under a rescaling of the parameters) is released; none: done.
+    An entry with l_a = u_a is reported at 1 or 2 by the sign of its multiplier.
+    Returns (delta [K], active [K] uint8, info): info = -1 (no usable term), -2 (l_a > u_a, or a bound that is NaN, for some a), -3 (the
+    iteration cap), a + 1 (a pivot of entry a is no finite number > 0), each with delta = 0 and active = 0; else 0.
+    ``with_iterations``: also returns the number of free-block solves."""
+    def out(delta, active, info, it):
+        return (delta, active, info, it) if with_iterations else (delta, active, info)
+
+    msg = msg.to(torch.float64).cpu()
+    f64 = dict(dtype=torch.float64)
+    lo, hi, scale, th = (torch.as_tensor(t, **f64).reshape(-1).cpu() for t in (lo, hi, scale, theta_idx))
+    if not (lo.numel() == hi.numel() == scale.numel() == th.numel() == K):
+        raise ValueError(f"lo, hi, scale and theta_idx hold the {K} learned entries")
+    if not radius > 0.0:
+        raise ValueError("radius must be > 0 (inf: no trust region)")
+    KK = K * (K + 1) // 2
+    count = float(msg[KK + K + 1])
+    n = max(1.0, count)
+    iu = torch.triu_indices(K, K)
+    H = torch.zeros(K, K, **f64)
+    H[iu[0], iu[1]] = msg[:KK] / n
+    H = torch.triu(H, 1).t() + H
+    g = lr * (msg[KK: KK + K] / n)
+    zero, none = torch.zeros(K, **f64), torch.zeros(K, dtype=torch.uint8)
+    d = torch.diagonal(H).clone()
+    d_max = float(d.max())
+    if not count > 0.0 or not math.isfinite(d_max) or d_max == 0.0:
+        return out(zero, none, -1, 0)
+    H = H + damping * torch.diag(torch.where(d > 0.0, d, torch.full_like(d, 1e-12 * d_max)))
+    t = radius * scale
+    a, b = lo - th, hi - th
+    l = torch.where((a > -t) | torch.isnan(a), a, -t)
+    u = torch.where((b < t) | torch.isnan(b), b, t)
+    if not bool((l <= u).all()):
+        return out(zero, none, -2, 0)
+    x = torch.where(l > 0.0, l, torch.where(u < 0.0, u, zero))
+    st = torch.where(x == l, 1, torch.where(x == u, 2, 0))
+    x = torch.where(st == 1, l, torch.where(st == 2, u, x))
+    L, z = H.clone(), g.clone()
+    fail = _gn_chol_solve(L, z)                                     # the whole of H first: its pivots' codes
+    if fail >= 0:
+        return out(zero, none, fail + 1, 0)
+    hd = torch.diagonal(H)
+    root = torch.sqrt(hd)
+    it, cap, first = 0, gn_box_iteration_cap(K), True
+    while True:
+        F = torch.nonzero(st == 0).reshape(-1)
+        B = torch.nonzero(st != 0).reshape(-1)
+        if it == cap:
+            return out(zero, none, -3, it)
+        it += 1
+        if not (first and F.numel() == K):                          # (else the factorisation above is this iteration's)
+            z = g[F] - H[F][:, B] @ x[B]
+            L = H[F][:, F].clone()
+            fail = _gn_chol_solve(L, z)
+            if fail >= 0:
+                return out(zero, none, int(F[fail]) + 1, it)
+        first = False
+        xf, lf, uf = x[F], l[F], u[F]
+        inf = torch.full_like(z, math.inf)
+        alpha = torch.where(z > uf, (uf - xf) / (z - xf), torch.where(z < lf, (lf - xf) / (z - xf), inf))
+        if F.numel() > 0 and float(alpha.min()) < math.inf:
+            p = int(torch.argmax((alpha == alpha.min()).to(torch.int8)))    # the lowest entry on a tie
+            al = float(alpha[p])
+            xn = torch.minimum(torch.maximum(xf + al * (z - xf), lf), uf)
+            side = 2 if float(z[p]) > float(uf[p]) else 1
+            xn[p] = uf[p] if side == 2 else lf[p]
+            x[F] = xn
+            st[F[p]] = side
+            continue
+        x[F] = z
+        r = H @ x - g
+        tol = 4.0 * (3 * K + 1) * 2.0 ** -53 * (root * (root @ x.abs()) + g.abs())
+        v = torch.where(st == 1, -r, r)
+        cand = (st != 0) & (l < u) & (v > 0.5 * tol)
+        if not bool(cand.any()):
+            break
+        score = torch.where(cand, v / root, torch.full_like(v, -math.inf))
+        st[int(torch.argmax((score == score.max()).to(torch.int8)))] = 0
+    st = torch.where(l == u, torch.where(r >= 0.0, 1, 2), st)
+    return out(x, st.to(torch.uint8), 0, it)
 
 
 class BatchedQLearning:
@@ -174,6 +290,12 @@ class DeviceQLearning:
     most 64 entries can be learned that way (the factorisation is one workgroup's, in LDS).  The entries are read from ``learn_mask`` at
     the first sweep (or ``enable_graphs``) and kept.  ``EpisodeStats.gn_info`` reports a step that was not taken.
 
+    ``trust_radius``, ``theta_bounds`` = (lo, hi) and ``theta_scale`` (each [n_p]; gauss_newton only) make that step the box QP of
+    ``qlearning_gn_box_step``: theta stays in [lo, hi] (-+inf: no bound) and no entry moves by more than trust_radius * theta_scale_a in
+    one episode, solved exactly by mpcrl_qlearning_gn_apply_box in one launch.  ``theta_scale`` defaults to |p0_a|, where that is 0 to the
+    largest |p0_c| over the learned entries, and to 1 if those are all 0.  With all three None the plain step runs, bit for bit as before.
+    ``EpisodeStats.gn_active`` counts the entries on a bound, ``gn_iterations`` the active-set iterations.
+
     A plant's class sets ``NX``, ``_COLLECT`` and, with more than one control, ``NU``, checks its OCP and environment, allocates
     ``live`` [T, E] (and what else its collect kernel needs) after this constructor, and defines ``_collect(r)`` (the collect launch
     after the roll-out solve r; returns its status), ``_stats()``, where the environment carries more than its state from step to step
@@ -187,12 +309,33 @@ class DeviceQLearning:
     _COLLECT: str = ""      # the library's collect entry point (for error messages)
 
     def __init__(self, ocp, env, episode_length: int, lr: float, gamma: float, noise_scale: float, seed: int, device, group,
-                 mpc_gamma: Optional[float] = None, method: str = "gradient", damping: float = 1e-3):
+                 mpc_gamma: Optional[float] = None, method: str = "gradient", damping: float = 1e-3, trust_radius: Optional[float] = None,
+                 theta_bounds: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, theta_scale: Optional[torch.Tensor] = None):
         name = type(self).__name__
         if method not in METHODS:
             raise ValueError(f"method: unknown {method!r} (one of {', '.join(METHODS)})")
         if isinstance(damping, bool) or not isinstance(damping, (int, float)) or not (math.isfinite(damping) and damping >= 0.0):
             raise ValueError("damping must be finite and >= 0")
+        box = trust_radius is not None or theta_bounds is not None or theta_scale is not None
+        if box and method != "gauss_newton":
+            raise ValueError("trust_radius, theta_bounds and theta_scale belong to method='gauss_newton' (no projected first-order step)")
+        if trust_radius is not None and (isinstance(trust_radius, bool) or not isinstance(trust_radius, (int, float)) or not trust_radius > 0.0):
+            raise ValueError("trust_radius must be > 0 (None or inf: no trust region)")
+        f64c = dict(dtype=torch.float64, device="cpu")
+        if theta_bounds is not None:
+            if not isinstance(theta_bounds, (tuple, list)) or len(theta_bounds) != 2:
+                raise ValueError("theta_bounds is a pair (lo, hi)")
+            theta_bounds = tuple(torch.as_tensor(t).detach().to(**f64c) for t in theta_bounds)
+            if any(t.shape != (ocp.n_p,) for t in theta_bounds):
+                raise ValueError(f"theta_bounds: lo and hi must have shape [{ocp.n_p}]")
+            if not bool((theta_bounds[0] <= theta_bounds[1]).all()):
+                raise ValueError("theta_bounds: lo <= hi must hold for every entry (and neither may be NaN)")
+        if theta_scale is not None:
+            theta_scale = torch.as_tensor(theta_scale).detach().to(**f64c)
+            if theta_scale.shape != (ocp.n_p,):
+                raise ValueError(f"theta_scale must have shape [{ocp.n_p}]")
+            if not bool((torch.isfinite(theta_scale) & (theta_scale > 0.0)).all()):
+                raise ValueError("theta_scale must be finite and > 0")
         if isinstance(episode_length, bool) or not isinstance(episode_length, int) or episode_length < 2:
             raise ValueError("episode_length must be an int >= 2 (a TD term needs two samples)")
         if not math.isfinite(lr):
@@ -212,7 +355,10 @@ class DeviceQLearning:
         self.E, self.device, self.group = env.num_envs, dev, group
         self.method, self.damping = method, float(damping)
         self.learn_idx = None               # gauss_newton: the learned entries [K] int32, built from learn_mask at the first sweep
-        self.gn_info = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.gn_info = torch.zeros(2, dtype=torch.int32, device=dev)      # [code, iterations of the box step]
+        self.box = box
+        self.trust_radius = math.inf if trust_radius is None else float(trust_radius)
+        self._box_args = (theta_bounds, theta_scale)                        # as given (CPU), until _gn_setup puts them on the device
         T, E, NX, NU = self.T, self.E, self.NX, self.NU
         if ocp.nu != NU:
             raise ValueError(f"{name} is written for {NU} control(s), the OCP has {ocp.nu}")
@@ -300,6 +446,17 @@ class DeviceQLearning:
         self.msg = torch.zeros(gn_msg_len(K), dtype=torch.float64, device=self.device)
         self._gn_ws = torch.zeros(nb, dtype=torch.uint8, device=self.device)
         self.learn_idx = idx.to(torch.int32).contiguous()
+        if self.box:
+            f64 = dict(dtype=torch.float64, device=self.device)
+            bounds, scale = self._box_args
+            if bounds is None:
+                bounds = (torch.full((self.n_p,), -math.inf), torch.full((self.n_p,), math.inf))
+            if scale is None:       # |p0_a|; where that is 0 the largest |p0_c| of the learned entries; 1 if those are all 0
+                p0 = torch.as_tensor(self.ocp.p0, dtype=torch.float64).abs()
+                top = float(p0[idx.cpu()].max())
+                scale = torch.where(p0 != 0.0, p0, torch.full_like(p0, top if top > 0.0 else 1.0))
+            self.theta_lo, self.theta_hi, self.theta_scale = bounds[0].to(**f64), bounds[1].to(**f64), scale.to(**f64)
+            self.gn_active = torch.zeros(K, dtype=torch.uint8, device=self.device)
 
     def _sweep(self):
         if self.method == "gauss_newton":
@@ -334,7 +491,15 @@ class DeviceQLearning:
             dist.all_reduce(self.msg, op=dist.ReduceOp.SUM, group=self.group)
 
     def _apply(self) -> None:
-        if self.method == "gauss_newton":
+        if self.method == "gauss_newton" and self.box:
+            with torch.cuda.device(self.device):
+                rc = self._lib.mpcrl_qlearning_gn_apply_box(_ptr(self.msg), self.K, _ptr(self.learn_idx), self.n_p, self.lr, self.damping,
+                                                            _ptr(self.theta_lo), _ptr(self.theta_hi), _ptr(self.theta_scale), self.trust_radius,
+                                                            _ptr(self.theta), _ptr(self.step_out), _ptr(self.gn_active), _ptr(self.gn_info),
+                                                            self._stream())
+            if rc != 0:
+                raise RuntimeError(f"mpcrl_qlearning_gn_apply_box failed with {rc}")
+        elif self.method == "gauss_newton":
             with torch.cuda.device(self.device):
                 rc = self._lib.mpcrl_qlearning_gn_apply(_ptr(self.msg), self.K, _ptr(self.learn_idx), self.n_p, self.lr, self.damping,
                                                         _ptr(self.theta), _ptr(self.step_out), _ptr(self.gn_info), self._stream())
@@ -376,7 +541,10 @@ class DeviceQLearning:
         self.episodes += 1
         stats = self._stats()
         if self.method == "gauss_newton":
-            stats.gn_info = int(self.gn_info.item())
+            info = self.gn_info.tolist()
+            stats.gn_info = info[0]
+            if self.box:
+                stats.gn_iterations, stats.gn_active = info[1], int((self.gn_active != 0).sum().item())
         return stats
 
     # ------------------------------------------------------------------ HIP graphs

@@ -78,12 +78,14 @@ class CartpoleQLearning(DeviceQLearning):
     _COLLECT = "mpcrl_qlearning_cartpole_collect"
 
     def __init__(self, ocp, env, episode_length: int, lr: float = 1e-4, gamma: float = 0.99, noise_scale: float = 0.1, seed: int = 0,
-                 device=None, group=None, method: str = "gradient", damping: float = 1e-3):
+                 device=None, group=None, method: str = "gradient", damping: float = 1e-3, trust_radius: Optional[float] = None,
+                 theta_bounds=None, theta_scale=None):
         if getattr(ocp, "model", None) != _lib.MODEL_CARTPOLE or ocp.nu != 1 or ocp.nx != 4:
             raise ValueError("CartpoleQLearning needs the cartpole OCP (cartpole_ocp())")
         if not isinstance(env, BatchedCartPoleSwingUpEnv):
             raise TypeError("CartpoleQLearning needs a BatchedCartPoleSwingUpEnv")
-        super().__init__(ocp, env, episode_length, lr, gamma, noise_scale, seed, device, group, method=method, damping=damping)
+        super().__init__(ocp, env, episode_length, lr, gamma, noise_scale, seed, device, group, method=method, damping=damping,
+                         trust_radius=trust_radius, theta_bounds=theta_bounds, theta_scale=theta_scale)
         self.alive = torch.zeros(self.E, dtype=torch.uint8, device=self.device)
         self.live = torch.zeros(self.T, self.E, dtype=torch.uint8, device=self.device)
 

@@ -109,6 +109,22 @@ def chain_collect_terms(ocp_or_dims, p: torch.Tensor, x_ss: torch.Tensor, state:
     return act, new_state, cost
 
 
+def chain_theta_bounds(ocp, rel: float = 0.5) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Physical bounds (lo, hi), [n_p] float64 each, for ``ChainQLearning(theta_bounds=...)``: the masses m and the spring constants D
+    within [(1 - rel) p0, (1 + rel) p0], 0 <= rel < 1 (they stay positive), every other entry unbounded (-inf, +inf)."""
+    if not (0.0 <= rel < 1.0):
+        raise ValueError("rel must lie in [0, 1)")
+    n_mass = _chain_dims(ocp)[0]
+    off = chain_param_layout(n_mass)[4]
+    p0 = torch.as_tensor(ocp.p0, dtype=torch.float64)
+    lo, hi = torch.full_like(p0, -float("inf")), torch.full_like(p0, float("inf"))
+    for key in ("m", "D"):
+        sl = slice(off[key][0], off[key][1])
+        a, b = (1.0 - rel) * p0[sl], (1.0 + rel) * p0[sl]
+        lo[sl], hi[sl] = torch.minimum(a, b), torch.maximum(a, b)
+    return lo, hi
+
+
 class ChainQLearning(DeviceQLearning):
     """Q-learning of the chain-of-masses MPC's parameters with E parallel chains (``env.num_envs``) and episodes of ``episode_length`` = T
     steps.  ``rollout_mpc`` solves the E policies, ``sample_mpc`` the E (T - 1) samples of the learning sweep.  ``gamma=None`` takes the
@@ -120,6 +136,8 @@ class ChainQLearning(DeviceQLearning):
     entry learned, ``lr = 1e-4`` moved the dynamics block by 6e-5 at n_mass 3 but by 0.045 at n_mass 5, where m itself is 0.033.
     ``method="gauss_newton"`` (``DeviceQLearning``) takes the damped least-squares TD step instead, whose ``lr`` in (0, 1] does not depend
     on the parameters' units; it learns at most 64 entries (m, D, L, C are 20 at n_mass 3 and 40 at n_mass 5; Q alone is 81 or more).
+    ``trust_radius``, ``theta_bounds`` and ``theta_scale`` (``DeviceQLearning``) keep that step inside bounds and a trust region;
+    ``chain_theta_bounds(ocp)`` keeps the masses and spring constants positive.
 
     Sizing: ``sample_mpc`` holds E (T - 1) chain instances, each with its trajectories and factorisation workspace — about 2 MB each at
     n_mass 5, N 40, so E = 256, T = 5 (1024 instances, the benchmark's chain5 batch) is about 2 GB.  ``workspace_bytes()`` returns
@@ -130,7 +148,8 @@ class ChainQLearning(DeviceQLearning):
     BLOCKS = ("m", "D", "L", "C", "Q", "R", "w")
 
     def __init__(self, ocp, env, episode_length: int, lr: float = 1e-6, gamma: Optional[float] = None, noise_scale: float = 0.0, seed: int = 0,
-                 device=None, group=None, learn: Sequence[str] = ("m", "D", "L", "C"), method: str = "gradient", damping: float = 1e-3):
+                 device=None, group=None, learn: Sequence[str] = ("m", "D", "L", "C"), method: str = "gradient", damping: float = 1e-3,
+                 trust_radius: Optional[float] = None, theta_bounds=None, theta_scale=None):
         if getattr(ocp, "model", None) != _lib.MODEL_CHAIN or ocp.nu != 3:
             raise ValueError("ChainQLearning needs the chain-of-masses OCP (chain_mass_ocp())")
         if not isinstance(env, BatchedChainMassEnv):
@@ -145,7 +164,7 @@ class ChainQLearning(DeviceQLearning):
         self.NX = ocp.nx                                                     # per instance: the chain's size sets the state's width
         gamma = ocp.gamma if gamma is None else gamma
         super().__init__(ocp, env, episode_length, lr, gamma, noise_scale, seed, device, group, mpc_gamma=gamma, method=method,
-                         damping=damping)
+                         damping=damping, trust_radius=trust_radius, theta_bounds=theta_bounds, theta_scale=theta_scale)
         self.n_mass, self.Ts, self.rk_steps, self.M, self.learn = n_mass, Ts, rk_steps, n_mass - 2, learn
         off = chain_param_layout(n_mass)[4]
         self.learn_mask.zero_()

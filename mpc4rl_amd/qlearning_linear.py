@@ -84,14 +84,15 @@ class LinearQLearning(DeviceQLearning):
     _COLLECT = "mpcrl_qlearning_linear_collect"
 
     def __init__(self, ocp, env, episode_length: int, lr: float = 1e-4, gamma: Optional[float] = None, noise_scale: float = 0.0, seed: int = 0,
-                 device=None, group=None, method: str = "gradient", damping: float = 1e-3):
+                 device=None, group=None, method: str = "gradient", damping: float = 1e-3, trust_radius: Optional[float] = None,
+                 theta_bounds=None, theta_scale=None):
         if getattr(ocp, "model", None) != _lib.MODEL_LINEAR or ocp.nu != 1 or ocp.nx != 2:
             raise ValueError("LinearQLearning needs the linear-system OCP (linear_system_ocp())")
         if not isinstance(env, BatchedLinearSystemEnv):
             raise TypeError("LinearQLearning needs a BatchedLinearSystemEnv")
         gamma = ocp.gamma if gamma is None else gamma
         super().__init__(ocp, env, episode_length, lr, gamma, noise_scale, seed, device, group, mpc_gamma=gamma, method=method,
-                         damping=damping)
+                         damping=damping, trust_radius=trust_radius, theta_bounds=theta_bounds, theta_scale=theta_scale)
         self.par = linear_env_par(env)
         self._par_c = (ctypes.c_double * 12)(*self.par)
         self.u01 = torch.zeros(self.T, self.E, dtype=torch.float64, device=self.device)
