@@ -106,7 +106,9 @@ extern "C" {
  *        roll-out step); mpcrl_ppo_chain_collect; mpcrl_ppo_surrogate_grad_nu / mpcrl_ppo_surrogate_workspace_bytes_nu;
  *        mpcrl_ppo_log_std_apply_nu (PPO on the chain of masses: a diagonal Gaussian over its three controls);
  *        mpcrl_qlearning_td_gn / mpcrl_qlearning_gn_workspace_bytes; mpcrl_qlearning_gn_apply (the Q-learners' Gauss-Newton step);
- *        mpcrl_qlearning_gn_apply_box (that step as a box QP: bounds on theta and a per-entry trust region) */
+ *        mpcrl_qlearning_gn_apply_box (that step as a box QP: bounds on theta and a per-entry trust region);
+ *        mpcrl_cdpg_record; mpcrl_cdpg_terms / mpcrl_cdpg_workspace_bytes; mpcrl_cdpg_apply (the deterministic policy gradient with a
+ *        compatible linear critic, from the roll-out's own du0/dp) */
 #define MPCRL_ABI_VERSION 132
 
 enum { MPCRL_MODEL_CARTPOLE = 0, MPCRL_MODEL_LINEAR = 1, MPCRL_MODEL_CHAIN = 2 };
@@ -451,6 +453,44 @@ int mpcrl_qlearning_gn_apply(const double *msg, int K, const int32_t *idx, int n
 int mpcrl_qlearning_gn_apply_box(const double *msg, int K, const int32_t *idx, int n_theta, double lr, double damping, const double *lo, const double *hi,
                                  const double *scale, double radius, double *theta, double *step_out, uint8_t *active /* [K]: 0 free, 1 at l, 2 at u */,
                                  int32_t *info /* [2]: code, iterations */, void *stream);
+
+/* Added under ABI 132.  The deterministic policy gradient with a compatible linear critic (cdpg_kernel.hpp; mpc4rl_amd/policy_gradient.py),
+ * from the roll-out solves alone: pi(s_t) = u0, J_t = du0/dp on the K learned entries idx (1 <= K <= 64), V(s_t) the baseline, nu in
+ * 1..3 controls.  Handle-less, asynchronous on `stream`, capture-safe; fixed order, no floating-point atomics: the same bits every time.
+ * MPCRL_E_ARG on K outside 1..64, nu outside 1..3, T < 2, E < 1 and a NULL required pointer (nothing is written then).
+ *
+ * mpcrl_cdpg_record, one launch after a roll-out solve and BEFORE the plant's collect launch: for every environment e with
+ * 0 <= row[e] < T (the row the collect is about to write; else nothing is written)
+ *   Vt[row][e] = V[e], U0[row][e][:] = u0[e][:], St[row][e] = status[e], Jt[row][e][c][a] = du0_dp[e][c][idx[a]]   (exact copies)
+ * V [E], u0 [E][nu], du0_dp [E][nu][n_p], status, row [E] int32, idx [K] int32, all on the device; an entry of idx outside [0, n_p)
+ * reads as a zero column.  Vt [T][E], U0 [T][E][nu], St [T][E] int32, Jt [T][E][nu][K].
+ *
+ * mpcrl_cdpg_terms, one launch after the episode: terms j = i E + e, i < T - 2, valid when live[i], live[i+1], live[i+2] (the liveness
+ * rule of mpcrl_qlearning_td_grad) and St[i] == 0 == St[i+1].  delta_j = (cost_j + gamma Vt_{j+E}) - Vt_j (three roundings, that order),
+ * d_j = act_j - U0_j, psi_ja = sum_c nan_to_num(Jt_jca) d_jc (fp64, no contraction, c in order).  delta [T-2][E] (0 where invalid),
+ * valid [T-2][E] uint8 (may be NULL) and
+ *   msg [K (K + 1) + K + 2] = [ G | b | M | sum_j delta_j | count ]      over the valid terms, an invalid one selected out
+ *     G_ac = sum_j psi_ja psi_jc,  M_ac = sum_j sum_c' J_jc'a J_jc'c:  upper triangles packed row-major as in mpcrl_qlearning_td_gn
+ *     (G at 0, M at K (K + 1) / 2 + K);  b_a = sum_j delta_j psi_ja at K (K + 1) / 2 + a.
+ * Additive over environments and ranks: one all-reduce (sum).  act [T][E][nu], cost [T][E], live [T][E] uint8: the episode tables.
+ * workspace: mpcrl_cdpg_workspace_bytes(T, E, K) bytes of device memory, ZERO before the first call (the call leaves it zero).
+ * T = 2: no term, msg = 0.
+ *
+ * mpcrl_cdpg_apply, after the collective, one launch of one workgroup: n, H = G/n + damping diag(..), the Cholesky solve and the codes -1
+ * and a + 1 exactly as mpcrl_qlearning_gn_apply;  w = H^-1 (b/n);  Delta = -lr w (natural != 0) or -lr (M/n) w, then clipped entrywise
+ * (a clip, not a QP) to [max(lo[c] - theta[c], -radius scale[c]), min(hi[c] - theta[c], +radius scale[c])], c = idx[a].  lo, hi, scale
+ * [n_theta] on the device may each be NULL (-inf, +inf, 1); all NULL with radius = +inf: no clip.  An empty interval or a NaN bound:
+ * info = -2.  On every code but 0 theta is untouched and step_out, w_out, active are 0.  Code 0: theta[c] = min(max(theta[c] + Delta_a,
+ * lo[c]), hi[c]), step_out [n_theta] = Delta at idx (a clipped entry: its bound bit for bit) and 0 elsewhere, w_out [K] = w, active [K]
+ * uint8 = 0 inside, 1 clipped to the lower end, 2 to the upper.  info [1] int32 on the device.  Also MPCRL_E_ARG: K > n_theta, lr or
+ * damping not finite, damping < 0, radius not > 0. */
+int mpcrl_cdpg_record(const double *V, const double *u0, const double *du0_dp, const int32_t *status, const int32_t *row, const int32_t *idx, int E, int T,
+                      int nu, int n_p, int K, double *Vt, double *U0, int32_t *St, double *Jt, void *stream);
+int64_t mpcrl_cdpg_workspace_bytes(int T, int E, int K);
+int mpcrl_cdpg_terms(const double *Vt, const double *U0, const double *Jt, const int32_t *St, const double *act, const double *cost, const uint8_t *live,
+                     int T, int E, int nu, int K, double gamma, void *workspace, double *delta, uint8_t *valid, double *msg, void *stream);
+int mpcrl_cdpg_apply(const double *msg, int K, const int32_t *idx, int n_theta, double lr, double damping, int natural, const double *lo, const double *hi,
+                     const double *scale, double radius, double *theta, double *step_out, double *w_out, uint8_t *active, int32_t *info, void *stream);
 
 /* Added under ABI 132.  Batched PPO with the MPC as Gaussian actor (ppo_kernel.hpp; mpc4rl_amd/ppo.py), cartpole environment, nu = 1, all
  * arithmetic fp64: a ~ N(mu, sigma^2) with mu = scale_action(u0*) of the solve and sigma = exp(log_std[0]), log_std a DEVICE double the

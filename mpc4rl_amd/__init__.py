@@ -14,6 +14,8 @@ from .qlearning import BatchedQLearning, qlearning_gn_box_step, qlearning_gn_ste
 from .qlearning_cartpole import CartpoleEpisodeStats, CartpoleQLearning, qlearning_td_terms  # noqa: F401
 from .qlearning_linear import LinearQLearning, linear_collect_terms, linear_env_par, linear_env_step_terms  # noqa: F401
 from .qlearning_chain import ChainQLearning, chain_collect_terms, chain_env_step_terms, chain_theta_bounds  # noqa: F401
+from .policy_gradient import (CartpolePolicyGradient, ChainPolicyGradient, DevicePolicyGradient, LinearPolicyGradient, cdpg_step,  # noqa: F401
+                              cdpg_terms)
 from .td3 import BatchedTD3, ContinuousCritic, DeviceReplayBuffer, MPCActor, MPCTD3Policy  # noqa: F401
 from .ppo import BatchedPPO, MPCActorCriticPolicy, ppo_collect_terms, ppo_gae, ppo_linear_collect_terms, ppo_surrogate_terms, ppo_value_terms  # noqa: F401
 from .ppo import ppo_chain_collect_terms, ppo_surrogate_terms_nu  # noqa: F401

@@ -37,7 +37,8 @@ EXPORTS = ["mpcrl_create", "mpcrl_destroy", "mpcrl_set_theta", "mpcrl_set_gamma"
            "mpcrl_qlearning_linear_collect", "mpcrl_ppo_linear_collect",
            "mpcrl_env_chain_step", "mpcrl_qlearning_chain_collect",
            "mpcrl_ppo_chain_collect", "mpcrl_ppo_surrogate_workspace_bytes_nu", "mpcrl_ppo_surrogate_grad_nu", "mpcrl_ppo_log_std_apply_nu",
-           "mpcrl_qlearning_gn_workspace_bytes", "mpcrl_qlearning_td_gn", "mpcrl_qlearning_gn_apply", "mpcrl_qlearning_gn_apply_box"]
+           "mpcrl_qlearning_gn_workspace_bytes", "mpcrl_qlearning_td_gn", "mpcrl_qlearning_gn_apply", "mpcrl_qlearning_gn_apply_box",
+           "mpcrl_cdpg_record", "mpcrl_cdpg_workspace_bytes", "mpcrl_cdpg_terms", "mpcrl_cdpg_apply"]
 
 _lib = None
 
@@ -130,12 +131,17 @@ def load():
     lib.mpcrl_qlearning_td_gn.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, C.c_int, vp, vp, vp, vp, vp]
     lib.mpcrl_qlearning_gn_apply.argtypes = [vp, C.c_int, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp]
     lib.mpcrl_qlearning_gn_apply_box.argtypes = [vp, C.c_int, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp]
+    lib.mpcrl_cdpg_record.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    lib.mpcrl_cdpg_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.mpcrl_cdpg_workspace_bytes.restype = C.c_int64
+    lib.mpcrl_cdpg_terms.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp]
+    lib.mpcrl_cdpg_apply.argtypes = [vp, C.c_int, vp, C.c_int, C.c_double, C.c_double, C.c_int, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]
     lib.mpcrl_workspace_bytes.argtypes = [vp]
     lib.mpcrl_workspace_bytes.restype = C.c_int64
     for name in EXPORTS:
         if name not in ("mpcrl_workspace_bytes", "mpcrl_critic_workspace_bytes", "mpcrl_dpg_workspace_bytes", "mpcrl_qlearning_td_workspace_bytes",
                         "mpcrl_ppo_surrogate_workspace_bytes", "mpcrl_value_workspace_bytes", "mpcrl_ppo_surrogate_workspace_bytes_nu",
-                        "mpcrl_qlearning_gn_workspace_bytes"):
+                        "mpcrl_qlearning_gn_workspace_bytes", "mpcrl_cdpg_workspace_bytes"):
             getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib

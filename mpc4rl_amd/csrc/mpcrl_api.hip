@@ -21,6 +21,7 @@
 #include "td3_kernel.hpp"
 #include "qlearning_kernel.hpp"
 #include "qlearning_gn_kernel.hpp"
+#include "cdpg_kernel.hpp"
 #include "ppo_kernel.hpp"
 #include "ppo_chain_kernel.hpp"
 #include "value_kernel.hpp"
@@ -856,6 +857,68 @@ int mpcrl_qlearning_gn_apply_box(const double *msg, int K, const int32_t *idx, i
     ON_DEVICE_OF(theta);
     hipLaunchKernelGGL(qlearning_gn_apply_box_kernel, dim3(1), dim3(GN_APPLY_NT), 0, (hipStream_t)stream, msg, K, (const int *)idx, n_theta, lr, damping,
                        lo, hi, scale, radius, theta, step_out, active, (int *)info);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int mpcrl_cdpg_record(const double *V, const double *u0, const double *du0_dp, const int32_t *status, const int32_t *row, const int32_t *idx, int E, int T,
+                      int nu, int n_p, int K, double *Vt, double *U0, int32_t *St, double *Jt, void *stream) {
+    if (K < 1 || K > GN_KMAX || nu < 1 || nu > CDPG_NU_MAX || T < 2 || E < 1 || n_p < 1 || !V || !u0 || !du0_dp || !status || !row || !idx || !Vt || !U0 ||
+        !St || !Jt)
+        return MPCRL_E_ARG;
+    ON_DEVICE_OF(Jt);
+    CdpgRecordArgs a;
+    a.V = V, a.u0 = u0, a.du0 = du0_dp, a.status = (const int *)status, a.row = (const int *)row, a.idx = (const int *)idx;
+    a.E = E, a.T = T, a.nu = nu, a.n_p = n_p, a.K = K, a.Vt = Vt, a.U0 = U0, a.St = (int *)St, a.Jt = Jt;
+    const int64_t lanes = (int64_t)E * nu * K;
+    hipLaunchKernelGGL(cdpg_record_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int64_t mpcrl_cdpg_workspace_bytes(int T, int E, int K) {
+    if (T < 2 || E < 1 || K < 1 || K > GN_KMAX) return MPCRL_E_ARG;
+    return ticket_workspace_bytes((int64_t)(T - 2) * E, TD_ROWS, cdpg_msg_len(K));
+}
+
+int mpcrl_cdpg_terms(const double *Vt, const double *U0, const double *Jt, const int32_t *St, const double *act, const double *cost, const uint8_t *live,
+                     int T, int E, int nu, int K, double gamma, void *workspace, double *delta, uint8_t *valid, double *msg, void *stream) {
+    if (!msg || T < 2 || E < 1 || nu < 1 || nu > CDPG_NU_MAX || K < 1 || K > GN_KMAX) return MPCRL_E_ARG;
+    const int64_t M = (int64_t)(T - 2) * E;
+    if (M > 0 && (!Vt || !U0 || !Jt || !St || !act || !cost || !live || !workspace || !delta)) return MPCRL_E_ARG;
+    ON_DEVICE_OF(msg);
+    if (M == 0) {   // no term: an empty message
+        HIP_OK(hipMemsetAsync(msg, 0, (size_t)cdpg_msg_len(K) * sizeof(double), (hipStream_t)stream));
+        return 0;
+    }
+    if (ticket_blocks(M, TD_ROWS) > 0x7fffffff) return MPCRL_E_ARG;
+    CdpgTermsArgs a;
+    a.Vt = Vt, a.U0 = U0, a.Jt = Jt, a.St = (const int *)St, a.act = act, a.cost = cost, a.live = live;
+    a.T = T, a.E = E, a.nu = nu, a.K = K, a.gamma = gamma, a.delta = delta, a.valid = valid;
+    a.msg = msg;
+    set_ticket_workspace(a, workspace);
+    const dim3 grid((unsigned)ticket_blocks(M, TD_ROWS)), block(TD_ROWS);
+#define CDPG_LAUNCH(NC) hipLaunchKernelGGL(cdpg_terms_kernel<NC>, grid, block, 0, (hipStream_t)stream, a)
+    switch (K / 16 + 1) {       // the column tiles of [G | b]: ceil((K + 1) / 16)
+        case 1: CDPG_LAUNCH(1); break;
+        case 2: CDPG_LAUNCH(2); break;
+        case 3: CDPG_LAUNCH(3); break;
+        case 4: CDPG_LAUNCH(4); break;
+        default: CDPG_LAUNCH(5); break;
+    }
+#undef CDPG_LAUNCH
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int mpcrl_cdpg_apply(const double *msg, int K, const int32_t *idx, int n_theta, double lr, double damping, int natural, const double *lo, const double *hi,
+                     const double *scale, double radius, double *theta, double *step_out, double *w_out, uint8_t *active, int32_t *info, void *stream) {
+    if (!msg || K < 1 || K > GN_KMAX || !idx || n_theta < K || !std::isfinite(lr) || !(std::isfinite(damping) && damping >= 0.0) || !(radius > 0.0) ||
+        !theta || !step_out || !w_out || !active || !info)
+        return MPCRL_E_ARG;
+    ON_DEVICE_OF(theta);
+    hipLaunchKernelGGL(cdpg_apply_kernel, dim3(1), dim3(GN_APPLY_NT), 0, (hipStream_t)stream, msg, K, (const int *)idx, n_theta, lr, damping, natural, lo,
+                       hi, scale, radius, theta, step_out, w_out, active, (int *)info);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -307,6 +307,7 @@ class DeviceQLearning:
     NX: int = 0             # the state's width
     NU: int = 1             # the number of controls
     _COLLECT: str = ""      # the library's collect entry point (for error messages)
+    _SAMPLE: bool = True    # False: a learner without a learning sweep (policy_gradient.py) builds no ``sample_mpc`` and no TD workspace
 
     def __init__(self, ocp, env, episode_length: int, lr: float, gamma: float, noise_scale: float, seed: int, device, group,
                  mpc_gamma: Optional[float] = None, method: str = "gradient", damping: float = 1e-3, trust_radius: Optional[float] = None,
@@ -364,9 +365,10 @@ class DeviceQLearning:
             raise ValueError(f"{name} is written for {NU} control(s), the OCP has {ocp.nu}")
         wide = () if NU == 1 else (NU,)      # one control: the tables keep no control axis
         self.rollout_mpc = MPCBatch(ocp, E, dev)
-        self.sample_mpc = MPCBatch(ocp, E * (T - 1), dev)
+        if self._SAMPLE:
+            self.sample_mpc = MPCBatch(ocp, E * (T - 1), dev)
         if mpc_gamma is not None:           # the handles' own discount factor (else the OCP's)
-            for m in (self.rollout_mpc, self.sample_mpc):
+            for m in self._handles():
                 m.set_discount_factor(mpc_gamma)
         self.n_p = ocp.n_p
         f64 = dict(dtype=torch.float64, device=dev)
@@ -392,10 +394,11 @@ class DeviceQLearning:
         self.msg = torch.zeros(self.n_p + 2, **f64)
         self.step_out = torch.zeros(self.n_p, **f64)
         self._lib = _lib.load()
-        nb = int(self._lib.mpcrl_qlearning_td_workspace_bytes(T, E, self.n_p))
-        if nb < 0:
-            raise RuntimeError(f"mpcrl_qlearning_td_workspace_bytes failed with {nb}")
-        self._td_ws = torch.zeros(nb, dtype=torch.uint8, device=dev)
+        if self._SAMPLE:
+            nb = int(self._lib.mpcrl_qlearning_td_workspace_bytes(T, E, self.n_p))
+            if nb < 0:
+                raise RuntimeError(f"mpcrl_qlearning_td_workspace_bytes failed with {nb}")
+            self._td_ws = torch.zeros(nb, dtype=torch.uint8, device=dev)
         # the roll-out handle holds an iterate from here on, so that the first solve of every episode (eager or replayed) is the
         # per-instance cold start of the cold mask, never the handle-wide one of a fresh handle
         x_init = self._initial_obs()
@@ -412,6 +415,9 @@ class DeviceQLearning:
     # ------------------------------------------------------------------ pieces (the same launches eager and captured)
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _handles(self):
+        return (self.rollout_mpc, self.sample_mpc) if self._SAMPLE else (self.rollout_mpc,)
 
     def _start_episode(self, x0: Optional[torch.Tensor] = None) -> None:
         self.env.reset()
@@ -447,16 +453,20 @@ class DeviceQLearning:
         self._gn_ws = torch.zeros(nb, dtype=torch.uint8, device=self.device)
         self.learn_idx = idx.to(torch.int32).contiguous()
         if self.box:
-            f64 = dict(dtype=torch.float64, device=self.device)
-            bounds, scale = self._box_args
-            if bounds is None:
-                bounds = (torch.full((self.n_p,), -math.inf), torch.full((self.n_p,), math.inf))
-            if scale is None:       # |p0_a|; where that is 0 the largest |p0_c| of the learned entries; 1 if those are all 0
-                p0 = torch.as_tensor(self.ocp.p0, dtype=torch.float64).abs()
-                top = float(p0[idx.cpu()].max())
-                scale = torch.where(p0 != 0.0, p0, torch.full_like(p0, top if top > 0.0 else 1.0))
-            self.theta_lo, self.theta_hi, self.theta_scale = bounds[0].to(**f64), bounds[1].to(**f64), scale.to(**f64)
-            self.gn_active = torch.zeros(K, dtype=torch.uint8, device=self.device)
+            self._box_setup(idx, K)
+
+    def _box_setup(self, idx: torch.Tensor, K: int) -> None:
+        """The bounds and the trust region's scales on the device, from the constructor's arguments and their defaults."""
+        f64 = dict(dtype=torch.float64, device=self.device)
+        bounds, scale = self._box_args
+        if bounds is None:
+            bounds = (torch.full((self.n_p,), -math.inf), torch.full((self.n_p,), math.inf))
+        if scale is None:       # |p0_a|; where that is 0 the largest |p0_c| of the learned entries; 1 if those are all 0
+            p0 = torch.as_tensor(self.ocp.p0, dtype=torch.float64).abs()
+            top = float(p0[idx.cpu()].max())
+            scale = torch.where(p0 != 0.0, p0, torch.full_like(p0, top if top > 0.0 else 1.0))
+        self.theta_lo, self.theta_hi, self.theta_scale = bounds[0].to(**f64), bounds[1].to(**f64), scale.to(**f64)
+        self.gn_active = torch.zeros(K, dtype=torch.uint8, device=self.device)
 
     def _sweep(self):
         if self.method == "gauss_newton":
@@ -511,7 +521,10 @@ class DeviceQLearning:
                                                      self._stream())
             if rc != 0:
                 raise RuntimeError(f"mpcrl_qlearning_apply failed with {rc}")
-        for m in (self.rollout_mpc, self.sample_mpc):
+        self._set_theta()
+
+    def _set_theta(self) -> None:
+        for m in self._handles():
             m.set_theta(self.theta)                                    # mpc.set_parameter
 
     def _initial_obs(self):
