@@ -733,6 +733,14 @@ int run(const OracleSpec *sp, int Bn, const double *x0, const double *u0fix, con
         S.exact = (flags & ORACLE_EXACT) != 0;
         const int st = S.sqp(x0 + (size_t)b * NX, u0fix ? u0fix + (size_t)b * NU : nullptr, warm, sp->max_iter, sp->tol, r4, ns, ni, cost,
                              (flags & ORACLE_RTI) != 0, sp->exit_window, sp->exit_factor);
+        // Rows this solve did not have (the bounds of u_0 in Q mode) leave as the cold iterate has them, lam = 0, t = 1, s = 0, as the
+        // kernels store them: a warm call would otherwise hand on the multipliers its warm start held for them (a V-mode solve's, two
+        // calls back), and the next V-mode call would start its interior point from those
+        for (int e = 0; e < n; ++e) {
+            for (int j = 0; j < 4; ++j)
+                if (!S.active(j, e)) S.lam[j][e] = 0.0, S.t[j][e] = 1.0;
+            if (!S.soft[e]) S.s[0][e] = S.s[1][e] = 0.0;
+        }
         if (status) status[b] = st;
         if (sqp_iter) sqp_iter[b] = ns;
         if (ipm_iter) ipm_iter[b] = ni;

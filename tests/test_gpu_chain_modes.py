@@ -20,6 +20,8 @@ import numpy as np
 import pytest
 import torch
 
+from small_mode_cases import bit_equal, largest_error, outputs, raw_solve, report, same_statuses
+
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-6
@@ -89,76 +91,7 @@ def case(port, n_mass, N, B, seed, tol=None):
 # ---------------------------------------------------------------------------------------------------------------------------------
 # device side
 # ---------------------------------------------------------------------------------------------------------------------------------
-def raw_solve(mpc, x0, u0=None, flags=None):
-    """mpcrl_solve through ctypes with every output buffer poisoned (NaN / -1) before the call, as
-    test_sensitivity_rows_are_written_in_full calls it: what comes back was written by this call."""
-    from mpc4rl_amd import _lib
-    from mpc4rl_amd.batch import SolveResult, _ptr
-    B = mpc.B
-    flags = (_lib.SENS_V | _lib.SENS_PI | _lib.COLD) if flags is None else flags
-    kw = dict(dtype=torch.float64, device=mpc.device)
-    xd = torch.as_tensor(x0, **kw).reshape(B, mpc.nx).contiguous()
-    ud = None if u0 is None else torch.as_tensor(u0, **kw).reshape(B, mpc.nu).contiguous()
-    u0o, V = torch.full((B, mpc.nu), np.nan, **kw), torch.full((B,), np.nan, **kw)
-    dV, dpi = torch.full((B, mpc.n_p), np.nan, **kw), torch.full((B, mpc.nu, mpc.n_p), np.nan, **kw)
-    st = torch.full((B,), -1, dtype=torch.int32, device=mpc.device)
-    it = torch.full((B, 2), -1, dtype=torch.int32, device=mpc.device)
-    with torch.cuda.device(mpc.device):
-        rc = mpc.lib.mpcrl_solve(mpc._h, _ptr(xd), _ptr(ud), flags, _ptr(u0o), _ptr(V), _ptr(dV), _ptr(dpi), _ptr(st), _ptr(it), mpc._stream())
-    torch.cuda.synchronize()
-    assert rc == 0
-    mpc.has_iterate = mpc.duals_valid = True
-    return SolveResult(u0o, V, st, it, dV, dpi)
-
-
-def outputs(mpc, r):
-    """What a call returned and left behind, as numpy arrays under the names of the port's result."""
-    x, u, pi, bnd, _ = mpc.get_iterate()
-    o = {"status": r.status, "iters": r.iters, "u0": r.u0, "V": r.V, "dV": r.dV_dp, "dpi": r.dpi_dp, "X": x, "U": u, "PI": pi, "BND": bnd}
-    return {k: (None if v is None else v.cpu().numpy()) for k, v in o.items()}
-
-
-def largest_error(got, ref, fields=FIELDS, rows=None):
-    """THE comparison: the largest |got - ref| over the named fields, every instance's row scaled by max(|reference row|, 1).
-    ref: a PortResult (or a dict of arrays under the same names); rows: the instances to compare (default: all of them)."""
-    worst, per = 0.0, {}
-    for f in fields:
-        a = got[f]
-        b = ref[f] if isinstance(ref, dict) else {"u0": ref.u0, "V": ref.V, "dV": ref.dV, "dpi": ref.dpi, "X": ref.X, "U": ref.U, "PI": ref.PI}[f]
-        B = len(b)
-        a, b = np.asarray(a, float).reshape(B, -1), np.asarray(b, float).reshape(B, -1)
-        if rows is not None:
-            a, b = a[rows], b[rows]
-        assert a.shape == b.shape and np.all(np.isfinite(b)), f
-        if a.shape[1] == 0:
-            continue
-        e = np.abs(a - b).max(1) / np.maximum(np.abs(b).max(1), 1.0)
-        per[f] = float(np.nan_to_num(e, nan=np.inf).max())
-        worst = max(worst, per[f])
-    largest_error.last = per
-    return worst
-
-
-def same_statuses(got, ref, expect=0):
-    """Statuses equal on both sides and, unless the case is about a status, all zero; SQP iteration counts within one."""
-    assert np.array_equal(got["status"], ref.status), (got["status"], ref.status)
-    if expect is not None:
-        assert np.all(ref.status == expect), ref.status
-    assert np.abs(got["iters"][:, 0] - ref.sqp_iter).max() <= 1, (got["iters"][:, 0], ref.sqp_iter)
-
-
-def report(tag, err):
-    print(f"[chain modes] {tag}: largest error {err:.3e}  {largest_error.last}")
-
-
-def bit_equal(ra, rb, rows=None):
-    for f in ("u0", "V", "status", "iters", "dV_dp", "dpi_dp"):
-        a, b = getattr(ra, f), getattr(rb, f)
-        assert (a is None) == (b is None), f
-        if a is not None:
-            if rows is not None:
-                a, b = a[rows], b[rows]
-            assert torch.equal(a, b), f
+# raw_solve, outputs, largest_error, same_statuses, report, bit_equal: tests/small_mode_cases.py (shared with test_gpu_small_modes.py)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
