@@ -333,8 +333,12 @@ int mpcrl_critic_dq_da(const float *obs, int obs_stride, int B, int nx, int nu, 
  *   idx [B] int64: the sampled rows (the caller draws them);  pos_t [1] int64: the slot the roll-out writes next;  steps: slots written;
  *   rows [B][row_len] float = table[idx];  obs64 / nxt64 [B][nx] double;
  *   iter_ok [cap * E] uint8 or NULL (then the four outputs below are not written):
- *     row_s = idx;  row_n = the row of the NEXT step of the same environment if done == 0 and that slot is written and is not pos_t,
- *     else idx;  cold_s / cold_n [B] int32 = 1 where iter_ok[row] == 0 (mpcrl_set_cold_mask takes them as they are).
+ *     row_s = idx;  row_n = the row of the NEXT step of the same environment if that slot is written and is not pos_t, done == 0 and
+ *     the obs stored in that row equals this row's next obs entry for entry (float ==; a NaN never does), else idx.  The done column
+ *     holds `terminated` only: an episode cut off at its time limit resets the environment with done == 0, and the comparison is what
+ *     keeps its solve at next obs from starting at the reset state's iterate.  The next row is read only after the two slot tests
+ *     passed (never slot pos_t, never an unwritten slot).
+ *     cold_s / cold_n [B] int32 = 1 where iter_ok[row] == 0 (mpcrl_set_cold_mask takes them as they are).
  *   exclude_pos != 0 (a full table only): slot pos_t is being written while the batch is drawn (a roll-out running beside the update):
  *     idx [B] in [0, (cap - 1) E) then counts the rows of the other slots, slot (pos_t + 1 + idx / E) % cap. */
 int mpcrl_replay_sample(const float *table, int row_len, int nx, int E, int cap, int steps, const int64_t *idx, int B, const int64_t *pos_t,

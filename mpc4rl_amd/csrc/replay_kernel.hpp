@@ -31,15 +31,29 @@ __global__ void __launch_bounds__(256) replay_sample_kernel(const ReplaySampleAr
         i = ((a.pos_t[0] + 1 + st) % a.cap) * a.E + (i - st * a.E);
     }
     const float *r = a.table + i * a.row_len;
+    int64_t n = i;
+    if (a.iter_ok) {
+        // the iterate for next obs: the roll-out solution of the NEXT step of the same environment where that exists and IS that state —
+        // the slot is neither the one about to be overwritten (or being written: exclude) nor one not yet written, the episode did not
+        // terminate, and the obs stored there equals this row's next obs entry for entry — else the one at obs.  The done column
+        // holds `terminated` alone (the TD target's flag): an episode cut off at the time limit resets its environment with the flag at
+        // 0, and only the comparison tells that row's obs (the reset state) from next obs.  Both are the same double rounded to float
+        // by the same cast where the episode went on; a NaN never compares equal (the safe side).  The next row is read only after
+        // the two slot tests passed: a slot that is being written or was never written is not touched.  (Ahead of the copies below
+        // and without a short circuit: these loads wait for nothing but the index.)
+        const int64_t step = i / a.E, env = i - step * a.E, nstep = (step + 1) % a.cap;
+        if (nstep != a.pos_t[0] && nstep < a.steps) {
+            const float *q = a.table + (nstep * a.E + env) * a.row_len;
+            bool cont = r[a.row_len - 1] == 0.0f;
+#pragma unroll 4
+            for (int k = 0; k < a.nx; ++k) cont &= q[k] == r[a.nx + k];
+            if (cont) n = nstep * a.E + env;
+        }
+    }
     float *o = a.rows + (long)b * a.row_len;
     for (int k = 0; k < a.row_len; ++k) o[k] = r[k];
     for (int k = 0; k < a.nx; ++k) a.obs64[(long)b * a.nx + k] = (double)r[k], a.nxt64[(long)b * a.nx + k] = (double)r[a.nx + k];
     if (a.iter_ok) {
-        // the iterate for next obs: the roll-out solution of the NEXT step of the same environment where that exists and is that state
-        // (the episode went on, the slot is neither the one about to be overwritten nor one not yet written) — else the one at obs
-        const int64_t step = i / a.E, env = i - step * a.E, nstep = (step + 1) % a.cap;
-        const bool cont = r[a.row_len - 1] == 0.0f && nstep != a.pos_t[0] && nstep < a.steps;
-        const int64_t n = cont ? nstep * a.E + env : i;
         a.row_s[b] = i, a.row_n[b] = n;
         a.cold_s[b] = a.iter_ok[i] ? 0 : 1, a.cold_n[b] = a.iter_ok[n] ? 0 : 1;
     }

@@ -351,13 +351,19 @@ class DeviceReplayBuffer:
     def iterates_of_last_sample(self):
         """For the transitions of the last sample(): (rows for obs, ok, rows for next_obs, ok) — row numbers into ``iters``.  The
         iterate for obs is the roll-out policy's own solution there.  For next_obs it is the roll-out solution of the NEXT step of the
-        same environment where that exists and is that state (the episode went on, the slot is not the one about to be overwritten /
-        not yet written) — else the solution at obs, one step earlier: the warm start the closed loop itself uses."""
+        same environment where that exists and IS that state (the slot is not the one about to be overwritten / not yet written, the
+        episode did not terminate, and the obs stored there equals this row's next_obs entry for entry) — else the solution at obs, one
+        step earlier: the warm start the closed loop itself uses.  The done column holds ``terminated`` alone, so an episode cut off
+        at the time limit (its environment was reset, the flag is 0) is told by the comparison only; where the episode went on both
+        values are the same double rounded by the same cast.  The same expressions as replay_sample_kernel, csrc/replay_kernel.hpp."""
         idx, steps, E = self.last_idx, self.last_steps, self.E
         step, env = idx // E, idx % E
         nstep = (step + 1) % self.cap
         flat = lambda t: t.reshape(self.cap * E, *t.shape[2:])
+        nx = self._nx
         cont = (self.last_rows[:, -1] == 0) & (nstep != self.pos_t) & (nstep < steps)
+        cand = torch.where(cont, nstep * E + env, idx)      # (a slot that failed its test is not read: the row itself stands in)
+        cont = cont & (flat(self.data)[cand, :nx] == self.last_rows[:, nx: 2 * nx]).all(dim=1)
         nidx = torch.where(cont, nstep * E + env, idx)
         ok = flat(self.iter_ok)
         return idx, ok[idx], nidx, ok[nidx]

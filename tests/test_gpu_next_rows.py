@@ -542,8 +542,15 @@ def test_td3_replay_iterates():
     obs, nxt, act, rew, done = buf.sample(E, agent.gen)
     i_s, ok_s, i_n, ok_n = buf.iterates_of_last_sample()
     step, nstep = buf.last_idx // E, (buf.last_idx // E + 1) % buf.cap
-    cont = (done == 0) & (nstep != buf.pos)
-    assert torch.equal(i_n, torch.where(cont, nstep * E + buf.last_idx % E, buf.last_idx)) and bool(cont.any()) and bool((~cont).any())
+    # the property, not the code's formula: wherever the start for next_obs is another row than the one for obs, it is the next step's
+    # row of the same environment and the obs stored there IS this row's next_obs, bit for bit
+    cont = i_n != buf.last_idx
+    assert torch.equal(i_s, buf.last_idx) and torch.equal(i_n, torch.where(cont, nstep * E + buf.last_idx % E, buf.last_idx))
+    assert torch.equal(buf.obs.reshape(-1, ocp.nx)[i_n[cont]].view(torch.int32), nxt[cont].contiguous().view(torch.int32))
+    assert bool(cont.any()) and bool((~cont).any())
+    # (eight steps of episodes of at most nine: none is cut off at the time limit, so every row whose episode did not terminate moves,
+    # unless its next slot is the write position)
+    assert torch.equal(cont, (done == 0) & (nstep != buf.pos))
     for handle, states, rows_, okr in ((agent.target_mpc.mpc, nxt, i_n, ok_n), (agent.pi_mpc.mpc, obs, i_s, ok_s)):
         states = states.double()
         handle.set_iterate_rows(*buf.iters, index=rows_.contiguous())
@@ -813,13 +820,16 @@ def test_td3_cartpole_collect_kernel_vs_the_kernels_it_stands_for():
 def test_replay_sample_excluding_the_slot_being_written():
     """mpcrl_replay_sample with exclude_pos (the pipelined TD3 loop: a roll-out writes slot pos while the batch is drawn): the rows of the
     other cap - 1 slots in the order after pos, the excluded slot never touched, and pos standing in for the write position in the choice
-    of the iterate for next_obs — against the index expressions in torch."""
+    of the iterate for next_obs — against a scripted episode log (tests/replay_cases.py: twelve steps into five slots, episodes that
+    terminate and episodes cut off at the time limit, whose done flag is 0), not against a copy of the kernel's expression."""
+    import replay_cases
     from mpc4rl_amd.td3 import DeviceReplayBuffer
     dev, E, cap, nx, nu, n = torch.device("cuda"), 37, 5, 4, 1, 4000
+    log = replay_cases.make_log(E, 12, nx, nu, cap, seed=0)
     buf = DeviceReplayBuffer(cap, E, nx, nu, dev, iterate_dims=(3, 2, 2, 4))
-    buf.data.copy_(torch.randn_like(buf.data))
-    buf.data[..., -1] = (torch.rand(cap, E, device=dev) < 0.3).float()
-    buf.iter_ok.copy_(torch.rand(cap, E, device=dev) < 0.8)
+    buf.data.copy_(torch.from_numpy(log.table))
+    buf.iter_ok.copy_(torch.from_numpy(log.iter_ok).bool())
+    assert log.pos == 2
     buf.pos, buf.full = 2, True
     buf.pos_t.fill_(2)
     gen = torch.Generator(device=dev).manual_seed(3)
@@ -834,12 +844,14 @@ def test_replay_sample_excluding_the_slot_being_written():
         rows = buf.data[step, env]
         assert torch.equal(buf.last_rows, rows) and torch.equal(buf.last_x64[0], rows[:, :nx].double()) and torch.equal(buf.last_x64[1], rows[:, nx: 2 * nx].double())
         row_s, cold_s, row_n, cold_n = buf.last_starts
-        nstep = (step + 1) % cap
-        cont = (rows[:, -1] == 0) & (nstep != pos)
-        rn = torch.where(cont, nstep * E + env, step * E + env)
+        ref = replay_cases.expected_starts(log, idx.cpu().numpy(), exclude_pos=pos)
+        replay_cases.assert_every_class(replay_cases.class_counts(log, ref, pos), f"sample without slot {pos}")
+        cont, rn = torch.from_numpy(ref["cont"]).to(dev), torch.from_numpy(ref["row_n"]).to(dev)
         ok = buf.iter_ok.reshape(-1)
         assert torch.equal(row_s, step * E + env) and torch.equal(row_n, rn) and int(cont.sum()) > 0 and int((~cont).sum()) > 0
+        assert torch.equal(cont, row_n != row_s) and torch.equal(buf.obs.reshape(-1, nx)[row_n[cont]], rows[cont][:, nx: 2 * nx])
         assert torch.equal(cold_s.bool(), ~ok[row_s]) and torch.equal(cold_n.bool(), ~ok[rn])
+        assert torch.equal(cold_s, torch.from_numpy(ref["cold_s"]).to(dev)) and torch.equal(cold_n, torch.from_numpy(ref["cold_n"]).to(dev))
     with pytest.raises(RuntimeError):
         buf.full = False
         buf.sample_fused(n, gen, exclude_pos=ex)
