@@ -108,7 +108,8 @@ extern "C" {
  *        mpcrl_qlearning_td_gn / mpcrl_qlearning_gn_workspace_bytes; mpcrl_qlearning_gn_apply (the Q-learners' Gauss-Newton step);
  *        mpcrl_qlearning_gn_apply_box (that step as a box QP: bounds on theta and a per-entry trust region);
  *        mpcrl_cdpg_record; mpcrl_cdpg_terms / mpcrl_cdpg_workspace_bytes; mpcrl_cdpg_apply (the deterministic policy gradient with a
- *        compatible linear critic, from the roll-out's own du0/dp) */
+ *        compatible linear critic, from the roll-out's own du0/dp); mpcrl_debug_seg_reduce (test probe of the small-model
+ *        kernels' segmented reductions) */
 #define MPCRL_ABI_VERSION 132
 
 enum { MPCRL_MODEL_CARTPOLE = 0, MPCRL_MODEL_LINEAR = 1, MPCRL_MODEL_CHAIN = 2 };
@@ -680,6 +681,15 @@ int mpcrl_ppo_surrogate_grad_nu(const int64_t *idx, int M, int64_t n_rows, const
 /* Added under ABI 132.  mpcrl_ppo_log_std_apply for nu entries (1 <= nu <= 3), c = max(1, msg[n_p + 1]):
  * log_std[0] += msg[n_p] / c;  log_std[j] += msg[n_p + 7 + j] / c for j = 1 .. nu-1 (the layout of mpcrl_ppo_surrogate_grad_nu). */
 int mpcrl_ppo_log_std_apply_nu(const double *msg, int n_p, int nu, double *log_std, void *stream);
+
+/* Added under ABI 132.  TEST PROBE of the segmented reductions of the cartpole / linear-system kernels (small_kernel.hpp, seg_reduce):
+ * one launch of one wavefront.  in, out: device arrays [n_max + n_sum][64] double, the max-values first; lane l of a value belongs
+ * to instance slot l / lpi, stage l % lpi, 1 <= lpi <= 64.  Every value is reduced over the lanes of each slot (fmax for the
+ * max-values, + for the sum-values, the kernels' tree and operand order) and out holds what each of the 64 lanes ends up with.
+ * which: 0 = a reference copy of the tree with every move a __shfl_down / __shfl (it exists in the probe only), 1 = the helpers as
+ * the cartpole kernels instantiate them, 2 = as the linear system's.  (n_max, n_sum) is one of (0,1) (1,0) (1,1) (2,2) (1,2) (4,1),
+ * the shapes the kernels reduce; anything else: MPCRL_E_ARG. */
+int mpcrl_debug_seg_reduce(const double *in, int lpi, int n_max, int n_sum, int which, double *out, void *stream);
 
 /* Bytes of device memory held by the handle; library version (MPCRL_ABI_VERSION of the header it was built from). */
 int64_t mpcrl_workspace_bytes(mpcrl_handle h);

@@ -46,7 +46,9 @@ struct CartpoleDev {
 #ifndef MPCRL_CARTPOLE_SEG_SKIP
 #define MPCRL_CARTPOLE_SEG_SKIP 0
 #endif
-    static constexpr bool SEG_SKIP = MPCRL_CARTPOLE_SEG_SKIP != 0;   // segmented reductions: full trees (small_kernel.hpp, measured)
+    // segmented reductions: no run-time test per tree level (measured slower, small_kernel.hpp seg_reduce); the level at distance 32
+    // is left out at compile time instead, in the instantiations launch_small picks for horizons of at most 32 lanes per instance
+    static constexpr bool SEG_SKIP = MPCRL_CARTPOLE_SEG_SKIP != 0;
     MPCRL_DI static int td_index(int i) { return i; }
     MPCRL_DI static int tc_index(int) { return 0; }
     MPCRL_DI static bool p_has_gradient(int e) { return e < NTD; }   // entries of p the sensitivity kernel computes; the rest are zeros

@@ -255,6 +255,34 @@ bool plan_time_sliced(const MpcrlSolver *h, int flags, long *waves) {
     return by_rule && tuned_shape(h->tune[(flags & MPCRL_COLD) ? 0 : 1], nullptr) == TUNE_SLICED;
 }
 
+// The kernels of the small models exist in two forms of their segmented reductions (small_kernel.hpp, seg_reduce): SHORT for horizons
+// whose instances take at most 32 lanes, where the tree has no level at distance 32, and the full tree for the longer ones.  A model
+// whose reductions leave levels out at run time (M::SEG_SKIP: the linear system) has the full form only.  Only the combinations a
+// launch can reach are instantiated: an instance that parks in LDS (sliced_parks_in_lds) is short wherever the cap says so.
+template <class M>
+inline bool seg_short(int N) { return !M::SEG_SKIP && N + 1 <= 32; }
+
+template <class M, bool SHORT>
+void launch_sliced(const MpcrlSolver *h, const SmallArgs &a, unsigned waves, hipStream_t st) {
+    const bool lds = sliced_parks_in_lds<M>(h->N), warm = !(a.flags & MPCRL_COLD);
+    if constexpr (SHORT || sliced_park_cap<M>() >= 33 * sliced_park_words<M>()) {
+        if (lds && !warm) hipLaunchKernelGGL((small_solve_sliced_kernel<M, true, false, SHORT>), dim3(waves), dim3(64), 0, st, h->small, a);
+        if (lds && warm) hipLaunchKernelGGL((small_solve_sliced_kernel<M, true, true, SHORT>), dim3(waves), dim3(64), 0, st, h->small, a);
+    }
+    if (!lds && !warm) hipLaunchKernelGGL((small_solve_sliced_kernel<M, false, false, SHORT>), dim3(waves), dim3(64), 0, st, h->small, a);
+    if (!lds && warm) hipLaunchKernelGGL((small_solve_sliced_kernel<M, false, true, SHORT>), dim3(waves), dim3(64), 0, st, h->small, a);
+}
+template <class M>
+void launch_sens(const MpcrlSolver *h, const SmallArgs &a, int blocks, hipStream_t st) {
+    if constexpr (!M::SEG_SKIP) {
+        if (seg_short<M>(h->N)) {
+            hipLaunchKernelGGL((small_sens_kernel<M, true>), dim3(blocks), dim3(64), 0, st, h->small, a);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((small_sens_kernel<M, false>), dim3(blocks), dim3(64), 0, st, h->small, a);
+}
+
 template <class M>
 int launch_small(MpcrlSolver *h, const SmallArgs &a, hipStream_t st) {
     const int lpi = h->N + 1, ipw = std::min(64 / lpi, M::MAX_IPW);
@@ -262,7 +290,7 @@ int launch_small(MpcrlSolver *h, const SmallArgs &a, hipStream_t st) {
     if constexpr (std::is_same<M, CartpoleDev>::value) {
         if (a.flags & MPCRL_EXACT_QP) {   // test-only: the exact-QP instantiation of the plain solve kernel, then the shipped sensitivity pass
             hipLaunchKernelGGL(small_solve_kernel<CartpoleDevExact>, dim3(blocks), dim3(64), 0, st, h->small, a);
-            if (a.flags & (MPCRL_SENS_V | MPCRL_SENS_PI)) hipLaunchKernelGGL(small_sens_kernel<M>, dim3(blocks), dim3(64), 0, st, h->small, a);
+            if (a.flags & (MPCRL_SENS_V | MPCRL_SENS_PI)) launch_sens<M>(h, a, blocks, st);
             HIP_OK(hipGetLastError());
             return 0;
         }
@@ -302,11 +330,10 @@ int launch_small(MpcrlSolver *h, const SmallArgs &a, hipStream_t st) {
         }
         h->planned = -1;
         if (sliced) {
-            const bool lds = sliced_parks_in_lds<M>(h->N), warm = !(a.flags & MPCRL_COLD);
-            if (lds && !warm) hipLaunchKernelGGL((small_solve_sliced_kernel<M, true, false>), dim3((unsigned)waves4), dim3(64), 0, st, h->small, a);
-            if (lds && warm) hipLaunchKernelGGL((small_solve_sliced_kernel<M, true, true>), dim3((unsigned)waves4), dim3(64), 0, st, h->small, a);
-            if (!lds && !warm) hipLaunchKernelGGL((small_solve_sliced_kernel<M, false, false>), dim3((unsigned)waves4), dim3(64), 0, st, h->small, a);
-            if (!lds && warm) hipLaunchKernelGGL((small_solve_sliced_kernel<M, false, true>), dim3((unsigned)waves4), dim3(64), 0, st, h->small, a);
+            if (seg_short<M>(h->N))
+                launch_sliced<M, true>(h, a, (unsigned)waves4, st);
+            else
+                launch_sliced<M, false>(h, a, (unsigned)waves4, st);
         }
     }
     bool lq = false;
@@ -330,7 +357,16 @@ int launch_small(MpcrlSolver *h, const SmallArgs &a, hipStream_t st) {
                 hipLaunchKernelGGL((lq_solve_kernel<3, 8>), grid, dim3(64), 0, st, h->small, a);
         }
     }
-    if (!sliced && !lq) hipLaunchKernelGGL(small_solve_kernel<M>, dim3(blocks), dim3(64), 0, st, h->small, a);
+    if (!sliced && !lq) {
+        bool done = false;
+        if constexpr (!M::SEG_SKIP) {
+            if (seg_short<M>(h->N)) {
+                hipLaunchKernelGGL((small_solve_kernel<M, true>), dim3(blocks), dim3(64), 0, st, h->small, a);
+                done = true;
+            }
+        }
+        if (!done) hipLaunchKernelGGL((small_solve_kernel<M, false>), dim3(blocks), dim3(64), 0, st, h->small, a);
+    }
     HIP_OK(hipGetLastError());
     if (timed_shape >= 0) {
         MpcrlSolver::Tuner &t = h->tune[(a.flags & MPCRL_COLD) ? 0 : 1];
@@ -338,7 +374,7 @@ int launch_small(MpcrlSolver *h, const SmallArgs &a, hipStream_t st) {
         t.pending[timed_shape] = true;
     }
     if ((a.flags & (MPCRL_SENS_V | MPCRL_SENS_PI)) && !lq) {   // (lq_solve_kernel runs the pass itself)
-        hipLaunchKernelGGL(small_sens_kernel<M>, dim3(blocks), dim3(64), 0, st, h->small, a);
+        launch_sens<M>(h, a, blocks, st);
         HIP_OK(hipGetLastError());
     }
     return 0;
@@ -377,6 +413,22 @@ int mpcrl_debug_phases(unsigned long long *out, int reset) {   // summed over th
 #endif
 
 int mpcrl_version(void) { return MPCRL_ABI_VERSION; }
+
+int mpcrl_debug_seg_reduce(const double *in, int lpi, int n_max, int n_sum, int which, double *out, void *stream) {
+    if (!in || !out || lpi < 1 || lpi > 64 || which < 0 || which > 2) return MPCRL_E_ARG;
+    ON_DEVICE_OF(out);
+    const hipStream_t st = (hipStream_t)stream;
+#define MPCRL_SEG_PROBE(NM, NS) \
+    if (n_max == NM && n_sum == NS) { \
+        hipLaunchKernelGGL((seg_probe_kernel<NM, NS>), dim3(1), dim3(64), 0, st, in, lpi, which, out); \
+        HIP_OK(hipGetLastError()); \
+        return 0; \
+    }
+    // the shapes the kernels reduce (small_kernel.hpp): single sums and maxima, the interior point's three passes, the SQP round's
+    MPCRL_SEG_PROBE(0, 1) MPCRL_SEG_PROBE(1, 0) MPCRL_SEG_PROBE(1, 1) MPCRL_SEG_PROBE(2, 2) MPCRL_SEG_PROBE(1, 2) MPCRL_SEG_PROBE(4, 1)
+#undef MPCRL_SEG_PROBE
+    return MPCRL_E_ARG;
+}
 
 int mpcrl_create(const MpcrlProblemSpec *spec, int batch, int device, mpcrl_handle *out) {
     if (!spec || !out || batch <= 0) return MPCRL_E_ARG;

@@ -107,58 +107,71 @@ MPCRL_DI double lane_select(unsigned long long mask, double yes, double no) {
 }
 constexpr unsigned long long LANES_C0 = 0x1111111111111111ull, LANES_C1 = 0x2222222222222222ull, LANES_C01 = 0x3333333333333333ull;   // lane & 3 == 0 / == 1 / < 2
 
-// segmented reductions over the LPI lanes of one instance; result broadcast to all of its lanes
-// SKIP (a model constant, M::SEG_SKIP): leave out the tree levels at which no lane has a partner (s >= lpi, wave-uniform).  One
-// cross-lane round trip less per reduction on paper; measured with everything else equal it is 2.3 % SLOWER for the cartpole kernels
-// (the branches change the schedule around the reductions) and 4 % faster for the linear system's, so each model states its own.
-template <bool SKIP>
-MPCRL_DI double seg_sum(double v, int k, int lpi, int base) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        if (SKIP && s >= lpi) continue;   // wave-uniform: no lane has a partner at this distance (a cross-lane round trip saved)
-        const double o = __shfl_down(v, s);
-        if (k + s < lpi) v += o;
-    }
-    return __shfl(v, base);
+// segmented reductions over the LPI lanes of one instance; result broadcast to all of its lanes.  One tree for every reduction:
+// distances 32, 16, 8, 4, 2, 1, lane k takes its partner's value in when k + s < lpi, operands in the order (own, partner).
+// How the partner's value travels is the only thing the template parameters and the distance decide:
+//   * distances 1 and 2 are one and two one-lane wave shifts (lane_dn: DPP moves, no LDS round trip).  Lane 63 keeps its own value
+//     either way.  After two shifts lane 62 holds lane 63's value where __shfl_down(v, 2) hands it its own: that lane never takes it
+//     in — in an instance slot that lies inside the wave k + 2 >= lpi there (its partner would be lane 64).  Only a slot cut off by
+//     the end of the wave (lanes that shadow an instance and never store) can see the difference.
+//   * SHORT (a property of the kernel instantiation, chosen by the host from the horizon): lpi <= 32, so at distance 32 no lane
+//     has a partner and the level does not exist in the code.  Horizons with lpi > 32 run the full tree.
+//   * SKIP (a model constant, M::SEG_SKIP): the same decision per level at run time (s >= lpi, wave-uniform).  Measured with
+//     everything else equal it is 2.3 % SLOWER for the cartpole kernels (the branches change the schedule around the reductions)
+//     and 4 % faster for the linear system's, so each model states its own; the cartpole takes the compile-time form above.
+template <int S>
+MPCRL_DI double seg_partner(double v) {   // value of lane + S (S a power of two), the lane's own where the wave ends first
+    if constexpr (S == 1)
+        return lane_dn(v);
+    else if constexpr (S == 2)
+        return lane_dn(lane_dn(v));
+    else
+        return __shfl_down(v, S);
 }
-template <bool SKIP>
-MPCRL_DI double seg_max(double v, int k, int lpi, int base) {
+template <int S, int NMAX, int NSUM, bool SKIP>
+MPCRL_DI void seg_level(double *mx, double *sm, int k, int lpi) {
+    if (SKIP && S >= lpi) return;   // wave-uniform: no lane has a partner at this distance (a cross-lane round trip saved)
+    double om[NMAX > 0 ? NMAX : 1], os[NSUM > 0 ? NSUM : 1];
 #pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        if (SKIP && s >= lpi) continue;
-        const double o = __shfl_down(v, s);
-        if (k + s < lpi) v = fmax(v, o);
+    for (int i = 0; i < NMAX; ++i) om[i] = seg_partner<S>(mx[i]);
+#pragma unroll
+    for (int i = 0; i < NSUM; ++i) os[i] = seg_partner<S>(sm[i]);
+    if (k + S < lpi) {
+#pragma unroll
+        for (int i = 0; i < NMAX; ++i) mx[i] = fmax(mx[i], om[i]);
+#pragma unroll
+        for (int i = 0; i < NSUM; ++i) sm[i] += os[i];
     }
-    return __shfl(v, base);
 }
-template <bool SKIP>
-MPCRL_DI double seg_min(double v, int k, int lpi, int base) { return -seg_max<SKIP>(-v, k, lpi, base); }
 // several reductions in one pass: the cross-lane moves of the different values overlap instead of queueing behind each other
-template <int NMAX, int NSUM, bool SKIP>
+template <int NMAX, int NSUM, bool SKIP, bool SHORT>
 MPCRL_DI void seg_reduce(double *mx, double *sm, int k, int lpi, int base) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        if (SKIP && s >= lpi) continue;
-        double om[NMAX > 0 ? NMAX : 1], os[NSUM > 0 ? NSUM : 1];
-#pragma unroll
-        for (int i = 0; i < NMAX; ++i) om[i] = __shfl_down(mx[i], s);
-#pragma unroll
-        for (int i = 0; i < NSUM; ++i) os[i] = __shfl_down(sm[i], s);
-        if (k + s < lpi) {
-#pragma unroll
-            for (int i = 0; i < NMAX; ++i) mx[i] = fmax(mx[i], om[i]);
-#pragma unroll
-            for (int i = 0; i < NSUM; ++i) sm[i] += os[i];
-        }
-    }
+    if constexpr (!SHORT) seg_level<32, NMAX, NSUM, SKIP>(mx, sm, k, lpi);
+    seg_level<16, NMAX, NSUM, SKIP>(mx, sm, k, lpi);
+    seg_level<8, NMAX, NSUM, SKIP>(mx, sm, k, lpi);
+    seg_level<4, NMAX, NSUM, SKIP>(mx, sm, k, lpi);
+    seg_level<2, NMAX, NSUM, SKIP>(mx, sm, k, lpi);
+    seg_level<1, NMAX, NSUM, SKIP>(mx, sm, k, lpi);
 #pragma unroll
     for (int i = 0; i < NMAX; ++i) mx[i] = __shfl(mx[i], base);
 #pragma unroll
     for (int i = 0; i < NSUM; ++i) sm[i] = __shfl(sm[i], base);
 }
+template <bool SKIP, bool SHORT>
+MPCRL_DI double seg_sum(double v, int k, int lpi, int base) {
+    seg_reduce<0, 1, SKIP, SHORT>(nullptr, &v, k, lpi, base);
+    return v;
+}
+template <bool SKIP, bool SHORT>
+MPCRL_DI double seg_max(double v, int k, int lpi, int base) {
+    seg_reduce<1, 0, SKIP, SHORT>(&v, nullptr, k, lpi, base);
+    return v;
+}
 
-template <class M>
+// SHORT: every instance takes at most 32 lanes (N + 1 <= 32), see seg_reduce; the host picks the instantiation (launch_small)
+template <class M, bool SHORT = false>
 struct SmallSolver {
+    static constexpr bool SEG_SHORT = SHORT;
     static constexpr int NX = M::NX, NU = M::NU, NW = NX + NU, NTD = M::NTD, NTC = M::NTC, NP = M::NP;
     static constexpr int NPK = NX * (NX + 1) / 2, NLK = NU * (NU + 1) / 2;
     static constexpr bool SOFT = M::HAS_SOFT;
@@ -1124,7 +1137,7 @@ struct SmallSolver {
             }
         }
         // number of bound rows of the instance: a property of the problem's structure, the same for every QP of the launch
-        if (n_rows_c < 0.0) n_rows_c = seg_sum<M::SEG_SKIP>(cnt, k, lpi, base);
+        if (n_rows_c < 0.0) n_rows_c = seg_sum<M::SEG_SKIP, SHORT>(cnt, k, lpi, base);
         const double n_rows = n_rows_c;
         PHW(11);
         bool qlive = act, ok = false;
@@ -1182,7 +1195,7 @@ struct SmallSolver {
                         }
                     }
                 }
-                seg_reduce<1, 1, M::SEG_SKIP>(&rloc, &muloc, k, lpi, base);
+                seg_reduce<1, 1, M::SEG_SKIP, SHORT>(&rloc, &muloc, k, lpi, base);
                 rinf = rloc, musum = muloc;   // musum: sum of the complementarity products
             } else
                 rinf = rinf_c, musum = musum_c;
@@ -1243,7 +1256,7 @@ struct SmallSolver {
             }
             {
                 double two[2] = {rmax, okbad};
-                seg_reduce<2, 2, M::SEG_SKIP>(two, c12, k, lpi, base);
+                seg_reduce<2, 2, M::SEG_SKIP, SHORT>(two, c12, k, lpi, base);
                 rmax = two[0];
                 if (two[1] > 0.5) qlive = false;   // non-positive pivot: QP failure
             }
@@ -1337,7 +1350,7 @@ struct SmallSolver {
                     }
                 }
             }
-            seg_reduce<1, 2, M::SEG_SKIP>(&rmax, d12, k, lpi, base);
+            seg_reduce<1, 2, M::SEG_SKIP, SHORT>(&rmax, d12, k, lpi, base);
             if (corr) take_step(1, smu, fmin(1.0, frac * fast_rcp(rmax)), d12);
             PHW(8);
         }
@@ -1348,9 +1361,13 @@ struct SmallSolver {
     // nun: multiplier nu_{k+1} of the dynamics leaving this stage.  dVa / dpia: per-instance output rows.
     // hdd: sum_m nu_{k+1,m} hess F_m along the non-trivial coordinates, from linearize<true>() (only read when du0*/dp is wanted)
     MPCRL_DI void sensitivities(int flags, bool valid, const double *nun, double *dVa, double *dpia, const double *hdd) {
-        // dF/dtheta of the stage: from a first-order evaluation of the map when only dV/dp is wanted; with du0*/dp it is the
-        // first-order part of the mixed second-order evaluation below (one evaluation of the map less)
-        const bool want_pi = (flags & 2) && dpia && !qmode;   // wave-uniform.  Q-mode: u_0 is pinned (mpc.py:71-76), du0/dp = 0
+        // dF/dtheta of the stage is the first-order part of the mixed second-order evaluation of the map below — for du0*/dp and
+        // for dV/dp alike, whichever of the two is asked for: dV/dp is the same bits with and without du0*/dp, because the same
+        // instructions compute it (a request for dV/dp alone runs the evaluation with a zero direction and skips the adjoint solve).
+        // Q-mode (u_0 is pinned, mpc.py:71-76: du0/dp = 0, no second-order pass): a first-order evaluation of the map.
+        const bool store_pi = (flags & 2) && dpia && !qmode;   // wave-uniform, as the two below
+        const bool want_v = (flags & 1) && dVa;
+        const bool want_pi = store_pi || (want_v && !qmode);   // the second-order pass runs
         double Fth[NX * NTD];
         if (!term && !want_pi) {
             Jet1<NTD> jx[NX], ju[NU], jt[NTD], jn[NX];
@@ -1369,8 +1386,11 @@ struct SmallSolver {
 #pragma unroll
             for (int i = 0; i < NX * NTD; ++i) Fth[i] = 0.0;
         }
-        auto emit_dV = [&]() {
-            if (!((flags & 1) && dVa)) return;
+        // With du0*/dp the per-instance sums of the pass — dV/dp: NT = NTD + NTC of them, du0*/dp: NT per control — travel through
+        // ONE reduction tree (seg_reduce<0, ...>): the trees of the single sums were walked one after the other, each level waiting
+        // for its cross-lane move.  Every sum keeps its own tree (same partners, same order of the additions).
+        constexpr int NT = NTD + NTC;
+        auto dV_parts = [&](double *dvp) {   // this stage's terms of dV/dp, differentiable parameters first
             double cpart[NTC > 0 ? NTC : 1];
 #pragma unroll
             for (int i = 0; i < (NTC > 0 ? NTC : 1); ++i) cpart[i] = 0.0;
@@ -1380,17 +1400,42 @@ struct SmallSolver {
                 double a = 0.0;
 #pragma unroll
                 for (int m = 0; m < NX; ++m) a = fma(nun[m], Fth[m * NTD + d], a);
-                a = seg_sum<M::SEG_SKIP>(a, k, lpi, base);
+                dvp[d] = a;
+            }
+#pragma unroll
+            for (int d = 0; d < NTC; ++d) dvp[NTD + d] = cpart[d];
+        };
+        auto store_dV = [&](const double *dvs) {
+#pragma unroll
+            for (int d = 0; d < NTD; ++d)
+                if (first && valid) dVa[M::td_index(d)] = dvs[d];
+#pragma unroll
+            for (int d = 0; d < NTC; ++d)
+                if (first && valid) dVa[M::tc_index(d)] = dvs[NTD + d];
+        };
+        if (!want_pi) {
+            // dV/dp in Q-mode: one tree per sum, as this request always ran.  With its NT sums in one tree 5 of the 39 entries of a
+            // 13-instance batch came out one unit in the last place away, although no tree changed and the builds with either half of
+            // that change alone kept every bit (profiles/seg_reduce_moves.txt) — presumably the first-order jet evaluation above
+            // compiles into another instruction sequence next to the gathered pass.  The request keeps its bits.
+            if (!want_v) return;
+            double cpart[NTC > 0 ? NTC : 1];
+#pragma unroll
+            for (int i = 0; i < (NTC > 0 ? NTC : 1); ++i) cpart[i] = 0.0;
+            M::cost_dp(term, k, x, u, ck, cpart);
+#pragma unroll
+            for (int d = 0; d < NTD; ++d) {
+                double a = 0.0;
+#pragma unroll
+                for (int m = 0; m < NX; ++m) a = fma(nun[m], Fth[m * NTD + d], a);
+                a = seg_sum<M::SEG_SKIP, SHORT>(a, k, lpi, base);
                 if (first && valid) dVa[M::td_index(d)] = a;
             }
 #pragma unroll
             for (int d = 0; d < NTC; ++d) {
-                const double a = seg_sum<M::SEG_SKIP>(cpart[d], k, lpi, base);
+                const double a = seg_sum<M::SEG_SKIP, SHORT>(cpart[d], k, lpi, base);
                 if (first && valid) dVa[M::tc_index(d)] = a;
             }
-        };
-        if (!want_pi) {
-            emit_dV();
             return;
         }
         // exact Lagrangian Hessian of the stage (nlp.py:1202,1224): c hess l + sum_m nu_{k+1,m} hess F_m
@@ -1432,17 +1477,24 @@ struct SmallSolver {
         for (int iu = 0; iu < NU; ++iu) {
 #pragma unroll
             for (int i = 0; i < NW; ++i) rt[i] = (first && i == iu) ? -1.0 : 0.0;
-            if constexpr (MX) {   // NU = 1: one adjoint solve
+            if (!store_pi) {      // dV/dp alone: no adjoint solve, the direction of the evaluation below is zero
+#pragma unroll
+                for (int i = 0; i < NX; ++i) Dx[i] = 0.0, Dnu[i] = 0.0;
+#pragma unroll
+                for (int i = 0; i < NU; ++i) Du[i] = 0.0;
+            } else if constexpr (MX) {   // NU = 1: one adjoint solve
                 const bool okf = mx_pred<true>(Hs, rt, zero);
                 mx_dnu(rt, true);
-                okall = seg_max<M::SEG_SKIP>(okf ? 0.0 : 1.0, k, lpi, base) < 0.5;
+                double oe[2] = {okf ? 0.0 : 1.0, capped_x ? 1.0 : 0.0};   // the two flags of the instance in one reduction pass
+                seg_reduce<2, 0, M::SEG_SKIP, SHORT>(oe, nullptr, k, lpi, base);
+                okall = oe[0] < 0.5;
                 // Richardson extrapolation in the stiffness cap (round 6).  Where the cap binds on a STATE row the capped solve is off by
                 // c / W — 1.5e-6 ... 3.6e-6 of du0/dp on cartpole states with the cart at the end of its track, measured against
                 // third-party finite differences (G7b) — linear in 1 / W down to W ~ 1e11, while the recursion's rounding grows with W
                 // (table at SENS_W_MAX).  y = 2 y(W) - y(W / 2) takes the bias out at W's rounding level (3e-9 on the same states).
                 // Decided per INSTANCE (an instance's numbers never depend on its wavefront neighbours); the second solve runs for the
                 // wavefront when any of its instances needs it — none of the benchmark's, whose state bounds are inactive.
-                const bool extrap = seg_max<M::SEG_SKIP>(capped_x ? 1.0 : 0.0, k, lpi, base) > 0.5;
+                const bool extrap = oe[1] > 0.5;
                 if (__any(extrap)) {
                     double y1x[NX], y1n[NX];
                     const double y1u = Du[0];
@@ -1458,7 +1510,7 @@ struct SmallSolver {
                     }
                     const bool okf2 = mx_pred<true>(Hs, rt, zero);
                     mx_dnu(rt, true);
-                    const bool ok2 = seg_max<M::SEG_SKIP>(okf2 ? 0.0 : 1.0, k, lpi, base) < 0.5;
+                    const bool ok2 = seg_max<M::SEG_SKIP, SHORT>(okf2 ? 0.0 : 1.0, k, lpi, base) < 0.5;
                     okall = okall && (ok2 || !extrap);
                     Du[0] = extrap ? fma(2.0, y1u, -Du[0]) : y1u;
 #pragma unroll
@@ -1467,7 +1519,7 @@ struct SmallSolver {
             } else {
                 if (iu == 0) {
                     const bool okf = backward(Hs, rt, zero);
-                    okall = seg_max<M::SEG_SKIP>(okf ? 0.0 : 1.0, k, lpi, base) < 0.5;
+                    okall = seg_max<M::SEG_SKIP, SHORT>(okf ? 0.0 : 1.0, k, lpi, base) < 0.5;
                 } else
                     backward_scan(rt, zero);
                 forward_scan(zero);
@@ -1506,17 +1558,24 @@ struct SmallSolver {
                     outd[d] = a;
                 }
             }
-            if (iu == 0) emit_dV();
+            // the sums of this control's row of du0*/dp and, with the first control, those of dV/dp
+            double sums[2 * NT];
 #pragma unroll
-            for (int d = 0; d < NTD; ++d) {
-                const double a = seg_sum<M::SEG_SKIP>(outd[d], k, lpi, base);
-                if (first && valid) dpia[iu * NP + M::td_index(d)] = okall ? -a : NAN;
-            }
+            for (int d = 0; d < NTD; ++d) sums[d] = outd[d];
 #pragma unroll
-            for (int d = 0; d < NTC; ++d) {
-                const double a = seg_sum<M::SEG_SKIP>(outc[d], k, lpi, base);
-                if (first && valid) dpia[iu * NP + M::tc_index(d)] = okall ? -a : NAN;
-            }
+            for (int d = 0; d < NTC; ++d) sums[NTD + d] = outc[d];
+            if (iu == 0 && want_v) {   // (wave-uniform)
+                dV_parts(sums + NT);
+                seg_reduce<0, 2 * NT, M::SEG_SKIP, SHORT>(nullptr, sums, k, lpi, base);
+                store_dV(sums + NT);
+            } else
+                seg_reduce<0, NT, M::SEG_SKIP, SHORT>(nullptr, sums, k, lpi, base);
+#pragma unroll
+            for (int d = 0; d < NTD; ++d)
+                if (first && valid && store_pi) dpia[iu * NP + M::td_index(d)] = okall ? -sums[d] : NAN;
+#pragma unroll
+            for (int d = 0; d < NTC; ++d)
+                if (first && valid && store_pi) dpia[iu * NP + M::tc_index(d)] = okall ? -sums[NTD + d] : NAN;
         }
     }
 
@@ -1531,7 +1590,7 @@ struct SmallSolver {
 #ifndef MPCRL_CARTPOLE_OCC
 #define MPCRL_CARTPOLE_OCC 1     // (2 + MPCRL_CARTPOLE_MAX_IPW=2 + MPCRL_MX_SLOTS=43: the two-wavefronts-per-SIMD experiment of round 6, profiles/README.md)
 #endif
-template <class M>
+template <class M, bool SHORT = false>
 __global__ void __launch_bounds__(64, M::DISCRETE ? MPCRL_LINEAR_OCC : MPCRL_CARTPOLE_OCC) small_solve_kernel(const SmallSpec sp, const SmallArgs a) {
     constexpr int NX = M::NX, NU = M::NU, NW = NX + NU, NP = M::NP, NTD = M::NTD, NTC = M::NTC;
     constexpr bool SOFT = M::HAS_SOFT;
@@ -1542,8 +1601,8 @@ __global__ void __launch_bounds__(64, M::DISCRETE ? MPCRL_LINEAR_OCC : MPCRL_CAR
     const bool valid = slot < ipw && inst < a.B;
     if (!valid) inst = a.B - 1;   // dead lanes shadow the last instance and never store
     if (a.perm) inst = a.perm[inst];
-    SmallSolver<M> S(sp, k, lpi, base);
-    __shared__ __attribute__((aligned(16))) double mx_lds[SmallSolver<M>::MX ? SmallSolver<M>::MX_LDS : 2];
+    SmallSolver<M, SHORT> S(sp, k, lpi, base);
+    __shared__ __attribute__((aligned(16))) double mx_lds[SmallSolver<M, SHORT>::MX ? SmallSolver<M, SHORT>::MX_LDS : 2];
     S.ms = mx_lds;
     const bool term = S.term, first = S.first;
     S.qmode = a.u0fix != nullptr;
@@ -1553,13 +1612,13 @@ __global__ void __launch_bounds__(64, M::DISCRETE ? MPCRL_LINEAR_OCC : MPCRL_CAR
     else
         S.ck = first ? sp.dT : (term ? pow(sp.gamma, (double)N) : pow(sp.gamma, (double)k) * sp.dT);   // nlp.py:1083-1091
     const double *th = a.theta + (size_t)inst * a.theta_stride;
-    __shared__ double c_lds[M::MAX_IPW * SmallSolver<M>::CTAB];
+    __shared__ double c_lds[M::MAX_IPW * SmallSolver<M, SHORT>::CTAB];
     S.fill_cost_table(c_lds, slot < ipw ? slot : 0, slot < ipw, th);
-    SmallSolver<M>::wave_lds_sync();
+    SmallSolver<M, SHORT>::wave_lds_sync();
     S.load_hc();
     // (lanes past the last instance slot shadow another instance: they get a slot of their own)
-    __shared__ double th_slots[SmallSolver<M>::TH_LDS ? (M::MAX_IPW + 1) * SmallSolver<M>::TH_DOUBLES : 1];
-    S.bind_theta(th_slots + (slot < ipw ? slot : M::MAX_IPW) * SmallSolver<M>::TH_DOUBLES);
+    __shared__ double th_slots[SmallSolver<M, SHORT>::TH_LDS ? (M::MAX_IPW + 1) * SmallSolver<M, SHORT>::TH_DOUBLES : 1];
+    S.bind_theta(th_slots + (slot < ipw ? slot : M::MAX_IPW) * SmallSolver<M, SHORT>::TH_DOUBLES);
 #pragma unroll
     for (int i = 0; i < NTD; ++i) S.thd.set(i, th[M::td_index(i)]);
 #pragma unroll
@@ -1651,7 +1710,7 @@ __global__ void __launch_bounds__(64, M::DISCRETE ? MPCRL_LINEAR_OCC : MPCRL_CAR
                 for (int i = 0; i < NU; ++i) sl = fmax(sl, fabs(S.u0r[i] - S.u[i]));
             }
         }
-        stepn = seg_max<M::SEG_SKIP>(sl, k, lpi, base);
+        stepn = seg_max<M::SEG_SKIP, SHORT>(sl, k, lpi, base);
         if (cold) stepn = -1.0;
     }
     double Vout = 0.0, res_out[4] = {0, 0, 0, 0};
@@ -1667,7 +1726,7 @@ __global__ void __launch_bounds__(64, M::DISCRETE ? MPCRL_LINEAR_OCC : MPCRL_CAR
         double rl[4];
         S.nlp_res_local(nun, S.x0r, S.u0r, rl);
         double res[4] = {rl[0], rl[1], rl[2], rl[3]}, cost = cl;
-        seg_reduce<4, 1, M::SEG_SKIP>(res, &cost, k, lpi, base);
+        seg_reduce<4, 1, M::SEG_SKIP, SHORT>(res, &cost, k, lpi, base);
 #ifdef MPCRL_PROFILE_PHASES
         { unsigned long long n_ = clock64(); S.phw[9] += n_ - S.pht; S.pht = n_; }
 #endif
@@ -1715,7 +1774,7 @@ __global__ void __launch_bounds__(64, M::DISCRETE ? MPCRL_LINEAR_OCC : MPCRL_CAR
 #pragma unroll
                 for (int i = 0; i < NU; ++i) sl = fmax(sl, fabs(S.du[i]));
             }
-            stepn = seg_max<M::SEG_SKIP>(sl, k, lpi, base);
+            stepn = seg_max<M::SEG_SKIP, SHORT>(sl, k, lpi, base);
         }
         if (live) {
 #pragma unroll
@@ -1748,7 +1807,7 @@ __global__ void __launch_bounds__(64, M::DISCRETE ? MPCRL_LINEAR_OCC : MPCRL_CAR
                     }
                 }
         }
-        lag = seg_sum<M::SEG_SKIP>(lag, k, lpi, base);
+        lag = seg_sum<M::SEG_SKIP, SHORT>(lag, k, lpi, base);
     }
     if (valid && first) {
         if (a.LAG) a.LAG[inst] = Vout + lag;
@@ -1810,7 +1869,7 @@ inline bool sliced_parks_in_lds(int N) { return (N + 1) * sliced_park_words<M>()
 
 // WARM: the instances start from their stored iterates (and the per-instance cold mask), as in small_solve_kernel — a separate
 // instantiation, so that the cold one keeps its register allocation.
-template <class M, bool LDSPARK, bool WARM = false>
+template <class M, bool LDSPARK, bool WARM = false, bool SHORT = false>
 __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSpec sp, const SmallArgs a) {
     constexpr int NX = M::NX, NU = M::NU, NW = NX + NU, NP = M::NP, NTD = M::NTD, NTC = M::NTC;
     static_assert(!M::HAS_SOFT, "hard bounds only");
@@ -1830,9 +1889,9 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
     const double *x0 = nullptr, *u0f = nullptr, *th = nullptr;
     double *bnd = nullptr;
     const size_t nb = (size_t)(N + 1) * NW;
-    SmallSolver<M> S(sp, k, lpi, base);
-    __shared__ __attribute__((aligned(16))) double mx_lds[SmallSolver<M>::MX ? SmallSolver<M>::MX_LDS : 2];
-    __shared__ double c_lds[M::MAX_IPW * SmallSolver<M>::CTAB];
+    SmallSolver<M, SHORT> S(sp, k, lpi, base);
+    __shared__ __attribute__((aligned(16))) double mx_lds[SmallSolver<M, SHORT>::MX ? SmallSolver<M, SHORT>::MX_LDS : 2];
+    __shared__ double c_lds[M::MAX_IPW * SmallSolver<M, SHORT>::CTAB];
     // parked scalars: live, status, iterations, interior-point iterations, ... (5 doubles; a stride of 5 costs the WARM
     // instantiations 12 more spilled VGPRs, measured: the slots stay 6 doubles apart)
     constexpr int SC = 6;
@@ -1875,7 +1934,7 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
         S.ck = first ? sp.dT : (term ? pow(sp.gamma, (double)N) : pow(sp.gamma, (double)k) * sp.dT);
     // cost tables of all ipw + 1 instances (the parked one's by the first lane past the slots, which is a stage-0 lane)
     S.fill_cost_table(c_lds, loc, (slot_on || (slot == ipw && k == 0)) && posof(loc) < a.B, th);
-    SmallSolver<M>::wave_lds_sync();
+    SmallSolver<M, SHORT>::wave_lds_sync();
     auto bind = [&](int l) {
         valid = slot_on && posof(l) < a.B;
         const long i = gi_lds[l];
@@ -1887,7 +1946,7 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
     if (!slot_on) loc = 0;                            // from here on the lanes past the slots shadow slot 0's instance
     bind(loc);
     auto load_params = [&]() {
-        S.ctab = c_lds + loc * SmallSolver<M>::CTAB + S.stage_kind() * SmallSolver<M>::CSET;
+        S.ctab = c_lds + loc * SmallSolver<M, SHORT>::CTAB + S.stage_kind() * SmallSolver<M, SHORT>::CSET;
         S.load_hc();
 #pragma unroll
         for (int i = 0; i < NTD; ++i) S.thd.set(i, th_lds[loc * TH + i]);
@@ -1933,7 +1992,7 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
                 for (int i = 0; i < NU; ++i) sl = fmax(sl, fabs(S.u0r[i] - S.u[i]));
             }
         }
-        const double sn = seg_max<M::SEG_SKIP>(sl, k, lpi, base);
+        const double sn = seg_max<M::SEG_SKIP, SHORT>(sl, k, lpi, base);
         return ((a.flags & (8 | 16)) || (a.cold && a.cold[inst])) ? -1.0 : sn;
     };
     if constexpr (WARM) load_stored();
@@ -1971,7 +2030,7 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
         double rl[4];
         S.nlp_res_local(nun, S.x0r, S.u0r, rl);
         double res[4] = {rl[0], rl[1], rl[2], rl[3]}, cost = cl;
-        seg_reduce<4, 1, M::SEG_SKIP>(res, &cost, k, lpi, base);
+        seg_reduce<4, 1, M::SEG_SKIP, SHORT>(res, &cost, k, lpi, base);
 #ifdef MPCRL_PROFILE_PHASES
         { unsigned long long n_ = clock64(); S.phw[9] += n_ - S.pht; S.pht = n_; }
 #endif
@@ -2009,7 +2068,7 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
                     for (int sd = 0; sd < 2; ++sd)
                         if (S.has(sd, i)) lag = fma(-S.lam[sd][i], S.bslack(sd, i, S.vc(i)), lag);
                 }
-                lag = seg_sum<M::SEG_SKIP>(lag, k, lpi, base);
+                lag = seg_sum<M::SEG_SKIP, SHORT>(lag, k, lpi, base);
             }
             if (fin_now && valid) {
                 if (first) {
@@ -2055,7 +2114,7 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
 #pragma unroll
                     for (int i = 0; i < NU; ++i) sl = fmax(sl, fabs(S.du[i]));
                 }
-                const double sn = seg_max<M::SEG_SKIP>(sl, k, lpi, base);
+                const double sn = seg_max<M::SEG_SKIP, SHORT>(sl, k, lpi, base);
                 if (live) stepn = sn;
             }
             if (live && ok) {
@@ -2102,13 +2161,15 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
 #endif
         // ---- rotation: one slot hands its instance over to the parked one.  The slot of a finished instance first (for good),
         // else round robin.  Every decision below is a function of wave-uniform values.
+        // (the lanes asked are wave-uniform: one ballot and a scalar lane read instead of an LDS round trip per slot)
         int v = -1;
+        const unsigned long long livem = __ballot(live);
         for (int s_ = 0; s_ < ipw; ++s_)
-            if (v < 0 && !__shfl(live ? 1 : 0, s_ * lpi)) v = s_;
+            if (v < 0 && !((livem >> (s_ * lpi)) & 1ull)) v = s_;
         const bool for_good = v >= 0;
         if (v < 0) v = rr % ipw, ++rr;
         const bool sw = slot_on && slot == v;
-        const int lo = __shfl(loc, v * lpi);            // local index of the outgoing instance
+        const int lo = __builtin_amdgcn_readlane(loc, v * lpi);   // local index of the outgoing instance
         if (sw && !for_good) {                          // park: state to LDS (or the instance's stored-iterate arrays), scalars to LDS
             if (valid && !lds_park) {
 #pragma unroll
@@ -2130,7 +2191,7 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
                 sc[1] = (double)n_ipm, sc[2] = stepn, sc[3] = rbest, sc[4] = rchk;
             }
         }
-        SmallSolver<M>::wave_lds_sync();                // orders the stores above before the loads below (same wavefront: in order)
+        SmallSolver<M, SHORT>::wave_lds_sync();                // orders the stores above before the loads below (same wavefront: in order)
         // take the parked instance: every lane runs the same loads, the lanes of the slot keep the results
         const int newloc = sw ? pk : loc;
         loc = newloc;
@@ -2262,7 +2323,7 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
 // instance zero every entry sensitivities() does not store — the cost block of p (zero gradient of the mirror, nlp.py:1039-1055),
 // everything of an instance that was not solved, du0*/dp in Q-mode.
 // =====================================================================================================
-template <class M>
+template <class M, bool SHORT = false>
 __global__ void __launch_bounds__(64) small_sens_kernel(const SmallSpec sp, const SmallArgs a) {
     constexpr int NX = M::NX, NU = M::NU, NW = NX + NU, NP = M::NP, NTD = M::NTD, NTC = M::NTC;
     const int lane = threadIdx.x;
@@ -2272,8 +2333,8 @@ __global__ void __launch_bounds__(64) small_sens_kernel(const SmallSpec sp, cons
     const bool valid = slot < ipw && inst < a.B;
     if (!valid) inst = a.B - 1;
     if (a.perm) inst = a.perm[inst];
-    SmallSolver<M> S(sp, k, lpi, base);
-    __shared__ __attribute__((aligned(16))) double mx_lds[SmallSolver<M>::MX ? SmallSolver<M>::MX_LDS : 2];
+    SmallSolver<M, SHORT> S(sp, k, lpi, base);
+    __shared__ __attribute__((aligned(16))) double mx_lds[SmallSolver<M, SHORT>::MX ? SmallSolver<M, SHORT>::MX_LDS : 2];
     S.ms = mx_lds;
     const bool term = S.term, first = S.first;
     S.qmode = a.u0fix != nullptr;
@@ -2283,13 +2344,13 @@ __global__ void __launch_bounds__(64) small_sens_kernel(const SmallSpec sp, cons
     else
         S.ck = first ? sp.dT : (term ? pow(sp.gamma, (double)N) : pow(sp.gamma, (double)k) * sp.dT);
     const double *th = a.theta + (size_t)inst * a.theta_stride;
-    __shared__ double c_lds[M::MAX_IPW * SmallSolver<M>::CTAB];
+    __shared__ double c_lds[M::MAX_IPW * SmallSolver<M, SHORT>::CTAB];
     S.fill_cost_table(c_lds, slot < ipw ? slot : 0, slot < ipw, th);
-    SmallSolver<M>::wave_lds_sync();
+    SmallSolver<M, SHORT>::wave_lds_sync();
     S.load_hc();
     // (lanes past the last instance slot shadow another instance: they get a slot of their own)
-    __shared__ double th_slots[SmallSolver<M>::TH_LDS ? (M::MAX_IPW + 1) * SmallSolver<M>::TH_DOUBLES : 1];
-    S.bind_theta(th_slots + (slot < ipw ? slot : M::MAX_IPW) * SmallSolver<M>::TH_DOUBLES);
+    __shared__ double th_slots[SmallSolver<M, SHORT>::TH_LDS ? (M::MAX_IPW + 1) * SmallSolver<M, SHORT>::TH_DOUBLES : 1];
+    S.bind_theta(th_slots + (slot < ipw ? slot : M::MAX_IPW) * SmallSolver<M, SHORT>::TH_DOUBLES);
 #pragma unroll
     for (int i = 0; i < NTD; ++i) S.thd.set(i, th[M::td_index(i)]);
 #pragma unroll
@@ -2343,6 +2404,54 @@ __global__ void __launch_bounds__(64) small_sens_kernel(const SmallSpec sp, cons
     { unsigned long long n_ = clock64(); S.phw[8] += n_ - S.pht; }
     if ((threadIdx.x & 63) == 0) for (int i_ = 0; i_ < 16; ++i_) atomicAdd(&g_phase_ticks[i_], S.phw[i_]);
 #endif
+}
+
+// =====================================================================================================
+// probe of the segmented reductions (mpcrl_debug_seg_reduce; tests/test_gpu_seg_reduce.py): one wavefront reduces NMAX max-values and
+// NSUM sum-values, 64 lanes each, over segments of lpi lanes laid out as the kernels above lay their instances out.
+//   which 0: the tree as it was written before the helpers learnt other ways to move a value — every level a __shfl_down, all six
+//            levels, the broadcast a __shfl.  It lives here only; it is what "the same tree" is measured against.
+//   which 1: the helpers as the cartpole kernels use them (no run-time skip; the short form for lpi <= 32)
+//   which 2: the helpers as the linear system's kernels use them (run-time skip, full form)
+// =====================================================================================================
+template <int NMAX, int NSUM>
+__global__ void __launch_bounds__(64) seg_probe_kernel(const double *in, int lpi, int which, double *out) {
+    const int lane = threadIdx.x;
+    const int slot = lane / lpi, k = lane - slot * lpi, base = slot * lpi;
+    double mx[NMAX > 0 ? NMAX : 1], sm[NSUM > 0 ? NSUM : 1];
+#pragma unroll
+    for (int i = 0; i < NMAX; ++i) mx[i] = in[i * 64 + lane];
+#pragma unroll
+    for (int i = 0; i < NSUM; ++i) sm[i] = in[(NMAX + i) * 64 + lane];
+    if (which == 0) {   // (wave-uniform, as every branch below)
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) {
+            double om[NMAX > 0 ? NMAX : 1], os[NSUM > 0 ? NSUM : 1];
+#pragma unroll
+            for (int i = 0; i < NMAX; ++i) om[i] = __shfl_down(mx[i], s);
+#pragma unroll
+            for (int i = 0; i < NSUM; ++i) os[i] = __shfl_down(sm[i], s);
+            if (k + s < lpi) {
+#pragma unroll
+                for (int i = 0; i < NMAX; ++i) mx[i] = fmax(mx[i], om[i]);
+#pragma unroll
+                for (int i = 0; i < NSUM; ++i) sm[i] += os[i];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NMAX; ++i) mx[i] = __shfl(mx[i], base);
+#pragma unroll
+        for (int i = 0; i < NSUM; ++i) sm[i] = __shfl(sm[i], base);
+    } else if (which == 2)
+        seg_reduce<NMAX, NSUM, true, false>(mx, sm, k, lpi, base);
+    else if (lpi <= 32)
+        seg_reduce<NMAX, NSUM, false, true>(mx, sm, k, lpi, base);
+    else
+        seg_reduce<NMAX, NSUM, false, false>(mx, sm, k, lpi, base);
+#pragma unroll
+    for (int i = 0; i < NMAX; ++i) out[i * 64 + lane] = mx[i];
+#pragma unroll
+    for (int i = 0; i < NSUM; ++i) out[(NMAX + i) * 64 + lane] = sm[i];
 }
 
 }  // namespace mpcrl
