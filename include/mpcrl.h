@@ -68,6 +68,8 @@
  *   - linear-system model, warm calls: an instance whose WARM-started interior point runs out of iterations (it can jam against the
  *     rows a moved x0 activates) solves that QP once more from the cold interior point before status 4 is reported — the QP is convex,
  *     the cold start solves it; its iteration count then includes both attempts (> 60).  No signature or output layout changes.
+ *   - cartpole: environment MPCRL_GENERIC_ROWS=1 at mpcrl_create keeps the generic solve kernels where the bounds would select the
+ *     ones with the full-box bound pattern compiled in (mpcrl_query_box_rows); the two forms return the same bits.
  *   - cartpole: a wavefront holds min(floor(64 / (N + 1)), 4) instances — four is the number of 4x4 blocks of the
  *     matrix-core sweeps — so horizons below N = 15 use fewer of its lanes than a lane-per-stage packing could.
  */
@@ -109,7 +111,7 @@ extern "C" {
  *        mpcrl_qlearning_gn_apply_box (that step as a box QP: bounds on theta and a per-entry trust region);
  *        mpcrl_cdpg_record; mpcrl_cdpg_terms / mpcrl_cdpg_workspace_bytes; mpcrl_cdpg_apply (the deterministic policy gradient with a
  *        compatible linear critic, from the roll-out's own du0/dp); mpcrl_debug_seg_reduce (test probe of the small-model
- *        kernels' segmented reductions) */
+ *        kernels' segmented reductions); mpcrl_query_box_rows (which form of the cartpole solve kernels the handle's bounds select) */
 #define MPCRL_ABI_VERSION 132
 
 enum { MPCRL_MODEL_CARTPOLE = 0, MPCRL_MODEL_LINEAR = 1, MPCRL_MODEL_CHAIN = 2 };
@@ -217,6 +219,12 @@ int mpcrl_get_launch_times(mpcrl_handle h, int warm, double *sliced_ms, double *
  * The pin lbu_0 = ubu_0 = u0 of Q(s,a) is the u0_fixed argument of mpcrl_solve (per instance), not this call. */
 enum { MPCRL_BOUNDS_U0 = 0, MPCRL_BOUNDS_STAGE = 1, MPCRL_BOUNDS_TERMINAL = 2 };
 int mpcrl_set_bounds(mpcrl_handle h, int which, const double *lb, const double *ub);
+/* 1 if the handle's solves run the cartpole solve kernels that have the full-box bound pattern compiled in, 0 if the generic ones,
+ * < 0 on misuse.  No effect on results: the two forms return the same bits.  The pattern: cartpole model, every bound of the interior
+ * stages present (|b| < 1e29), the bounds of u_0 bitwise equal to the interior control bounds and the terminal bounds bitwise equal to
+ * the interior state bounds — evaluated at mpcrl_create and again by every mpcrl_set_bounds.  Environment MPCRL_GENERIC_ROWS=1 read at
+ * mpcrl_create keeps the generic kernels whatever the bounds are. */
+int mpcrl_query_box_rows(mpcrl_handle h);
 
 /* Cold iterate: x_k := x0 for all k (x0: [B, nx] device, or NULL: 0), u := 0, all multipliers 0, slacks 1; the next solve
  * starts cold (interior point from its default point). */

@@ -39,7 +39,7 @@ EXPORTS = ["mpcrl_create", "mpcrl_destroy", "mpcrl_set_theta", "mpcrl_set_gamma"
            "mpcrl_ppo_chain_collect", "mpcrl_ppo_surrogate_workspace_bytes_nu", "mpcrl_ppo_surrogate_grad_nu", "mpcrl_ppo_log_std_apply_nu",
            "mpcrl_qlearning_gn_workspace_bytes", "mpcrl_qlearning_td_gn", "mpcrl_qlearning_gn_apply", "mpcrl_qlearning_gn_apply_box",
            "mpcrl_cdpg_record", "mpcrl_cdpg_workspace_bytes", "mpcrl_cdpg_terms", "mpcrl_cdpg_apply",
-           "mpcrl_debug_seg_reduce"]
+           "mpcrl_debug_seg_reduce", "mpcrl_query_box_rows"]
 
 _lib = None
 
@@ -77,6 +77,7 @@ def load():
     lib.mpcrl_get_lagrangian.argtypes = [vp, vp, vp]
     lib.mpcrl_auto_order.argtypes = [vp, vp, vp]
     lib.mpcrl_query_time_sliced.argtypes = [vp, C.c_int, vp]
+    lib.mpcrl_query_box_rows.argtypes = [vp]
     lib.mpcrl_set_launch_mode.argtypes = [vp, C.c_int]
     lib.mpcrl_get_launch_times.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.mpcrl_weighted_grad_sum.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp]

@@ -262,15 +262,55 @@ bool plan_time_sliced(const MpcrlSolver *h, int flags, long *waves) {
 template <class M>
 inline bool seg_short(int N) { return !M::SEG_SKIP && N + 1 <= 32; }
 
-template <class M, bool SHORT>
+// The cartpole solve kernels exist in a third form, BOX (small_kernel.hpp): the full-box bound pattern compiled in.  It is the same
+// iteration bit for bit, taken when the handle's bounds are that pattern (box_rows_spec) and MPCRL_GENERIC_ROWS=1 did not switch it off;
+// any other bounds run the generic kernels.  The linear system has soft rows and the generic form only.
+template <class M>
+constexpr bool HAS_BOX_ROWS = std::is_same<M, CartpoleDev>::value;
+
+// every interior bound present, u_0's bounds the interior control bounds and the terminal bounds the interior state bounds, bitwise
+inline bool box_rows_spec(const SmallSpec &sp, int nx, int nu) {
+    for (int i = 0; i < nx + nu; ++i)
+        if (!(std::fabs(sp.lb[i]) < NO_BOUND) || !(std::fabs(sp.ub[i]) < NO_BOUND)) return false;
+    return std::memcmp(sp.lb0, sp.lb, nu * sizeof(double)) == 0 && std::memcmp(sp.ub0, sp.ub, nu * sizeof(double)) == 0 &&
+           std::memcmp(sp.lbe, sp.lb + nu, nx * sizeof(double)) == 0 && std::memcmp(sp.ube, sp.ub + nu, nx * sizeof(double)) == 0;
+}
+inline void refresh_box_rows(MpcrlSolver *h) {
+    h->box_rows = !h->is_large && !h->generic_rows && h->model == MPCRL_MODEL_CARTPOLE && box_rows_spec(h->small, h->nx, h->nu);
+}
+
+template <class M, bool SHORT, bool BOX>
 void launch_sliced(const MpcrlSolver *h, const SmallArgs &a, unsigned waves, hipStream_t st) {
     const bool lds = sliced_parks_in_lds<M>(h->N), warm = !(a.flags & MPCRL_COLD);
     if constexpr (SHORT || sliced_park_cap<M>() >= 33 * sliced_park_words<M>()) {
-        if (lds && !warm) hipLaunchKernelGGL((small_solve_sliced_kernel<M, true, false, SHORT>), dim3(waves), dim3(64), 0, st, h->small, a);
-        if (lds && warm) hipLaunchKernelGGL((small_solve_sliced_kernel<M, true, true, SHORT>), dim3(waves), dim3(64), 0, st, h->small, a);
+        if (lds && !warm) hipLaunchKernelGGL((small_solve_sliced_kernel<M, true, false, SHORT, BOX>), dim3(waves), dim3(64), 0, st, h->small, a);
+        if (lds && warm) hipLaunchKernelGGL((small_solve_sliced_kernel<M, true, true, SHORT, BOX>), dim3(waves), dim3(64), 0, st, h->small, a);
     }
-    if (!lds && !warm) hipLaunchKernelGGL((small_solve_sliced_kernel<M, false, false, SHORT>), dim3(waves), dim3(64), 0, st, h->small, a);
-    if (!lds && warm) hipLaunchKernelGGL((small_solve_sliced_kernel<M, false, true, SHORT>), dim3(waves), dim3(64), 0, st, h->small, a);
+    if (!lds && !warm) hipLaunchKernelGGL((small_solve_sliced_kernel<M, false, false, SHORT, BOX>), dim3(waves), dim3(64), 0, st, h->small, a);
+    if (!lds && warm) hipLaunchKernelGGL((small_solve_sliced_kernel<M, false, true, SHORT, BOX>), dim3(waves), dim3(64), 0, st, h->small, a);
+}
+// the solve launch of the small models in either shape (waves: of the time-sliced one); SHORT as seg_short says
+template <class M, bool BOX>
+void launch_solve(const MpcrlSolver *h, const SmallArgs &a, bool sliced, unsigned waves, int blocks, hipStream_t st) {
+    if constexpr (!M::SEG_SKIP) {
+        if (seg_short<M>(h->N)) {
+            if constexpr (!M::HAS_SOFT) {
+                if (sliced) {
+                    launch_sliced<M, true, BOX>(h, a, waves, st);
+                    return;
+                }
+            }
+            hipLaunchKernelGGL((small_solve_kernel<M, true, BOX>), dim3(blocks), dim3(64), 0, st, h->small, a);
+            return;
+        }
+    }
+    if constexpr (!M::HAS_SOFT) {
+        if (sliced) {
+            launch_sliced<M, false, BOX>(h, a, waves, st);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((small_solve_kernel<M, false, BOX>), dim3(blocks), dim3(64), 0, st, h->small, a);
 }
 template <class M>
 void launch_sens(const MpcrlSolver *h, const SmallArgs &a, int blocks, hipStream_t st) {
@@ -296,6 +336,7 @@ int launch_small(MpcrlSolver *h, const SmallArgs &a, hipStream_t st) {
         }
     }
     bool sliced = false;
+    unsigned waves_sliced = 0;
     int timed_shape = -1;
     if constexpr (!M::HAS_SOFT) {
         long waves4 = 0;
@@ -329,12 +370,7 @@ int launch_small(MpcrlSolver *h, const SmallArgs &a, hipStream_t st) {
             }
         }
         h->planned = -1;
-        if (sliced) {
-            if (seg_short<M>(h->N))
-                launch_sliced<M, true>(h, a, (unsigned)waves4, st);
-            else
-                launch_sliced<M, false>(h, a, (unsigned)waves4, st);
-        }
+        waves_sliced = (unsigned)waves4;
     }
     bool lq = false;
     if constexpr (std::is_same<M, LinearDev>::value) {
@@ -357,15 +393,15 @@ int launch_small(MpcrlSolver *h, const SmallArgs &a, hipStream_t st) {
                 hipLaunchKernelGGL((lq_solve_kernel<3, 8>), grid, dim3(64), 0, st, h->small, a);
         }
     }
-    if (!sliced && !lq) {
+    if (!lq) {
         bool done = false;
-        if constexpr (!M::SEG_SKIP) {
-            if (seg_short<M>(h->N)) {
-                hipLaunchKernelGGL((small_solve_kernel<M, true>), dim3(blocks), dim3(64), 0, st, h->small, a);
+        if constexpr (HAS_BOX_ROWS<M>) {
+            if (h->box_rows) {
+                launch_solve<M, true>(h, a, sliced, waves_sliced, blocks, st);
                 done = true;
             }
         }
-        if (!done) hipLaunchKernelGGL((small_solve_kernel<M, false>), dim3(blocks), dim3(64), 0, st, h->small, a);
+        if (!done) launch_solve<M, false>(h, a, sliced, waves_sliced, blocks, st);
     }
     HIP_OK(hipGetLastError());
     if (timed_shape >= 0) {
@@ -443,6 +479,8 @@ int mpcrl_create(const MpcrlProblemSpec *spec, int batch, int device, mpcrl_hand
         if (e && *e) h->slice_mode = (*e == '0') ? -1 : 1;
         const char *l = std::getenv("MPCRL_LINEAR_SPL");   // stages per lane of the linear-system solve kernel: 3 (default) or 1
         if (l && *l == '1') h->linear_spl = 1;
+        const char *g = std::getenv("MPCRL_GENERIC_ROWS");   // tests, A/B runs: the generic cartpole solve kernels whatever the bounds are
+        if (g && *g == '1') h->generic_rows = true;
     }
     int rc = 0;
     switch (spec->model) {
@@ -472,6 +510,7 @@ int mpcrl_create(const MpcrlProblemSpec *spec, int batch, int device, mpcrl_hand
         delete h;
         return rc;
     }
+    refresh_box_rows(h);
     const size_t B = batch, N = spec->N, nx = spec->nx, nu = spec->nu, nw = nx + nu;
     rc = dev_alloc(&h->X, B * (N + 1) * nx, h->bytes);
     if (!rc) rc = dev_alloc(&h->U, B * N * nu, h->bytes);
@@ -664,7 +703,13 @@ int mpcrl_set_bounds(mpcrl_handle h, int which, const double *lb, const double *
         for (int i = 0; i < n; ++i)
             if (h->small.soft[i] && (lb[i] <= -MPCRL_NO_BOUND * 0.1 || ub[i] >= MPCRL_NO_BOUND * 0.1)) return MPCRL_E_ARG;
     for (int i = 0; i < n; ++i) dl[i] = lb[i], du[i] = ub[i];
+    refresh_box_rows(h);
     return 0;
+}
+
+int mpcrl_query_box_rows(mpcrl_handle h) {
+    if (!h) return MPCRL_E_ARG;
+    return h->box_rows ? 1 : 0;
 }
 
 int mpcrl_reset(mpcrl_handle h, const double *x0, void *stream) {

@@ -169,7 +169,10 @@ MPCRL_DI double seg_max(double v, int k, int lpi, int base) {
 }
 
 // SHORT: every instance takes at most 32 lanes (N + 1 <= 32), see seg_reduce; the host picks the instantiation (launch_small)
-template <class M, bool SHORT = false>
+// BOX: the full-box bound pattern (chosen by the host from the handle's bounds, box_rows_spec): every interior bound is present, and
+// stage 0 / the terminal stage carry the interior bounds of their coordinates.  Which rows a lane has then follows from its stage kind
+// alone, see init_bounds / each_coord.  The iteration is the same, bit for bit.
+template <class M, bool SHORT = false, bool BOX = false>
 struct SmallSolver {
     static constexpr bool SEG_SHORT = SHORT;
     static constexpr int NX = M::NX, NU = M::NU, NW = NX + NU, NTD = M::NTD, NTC = M::NTC, NP = M::NP;
@@ -236,9 +239,24 @@ struct SmallSolver {
     // ---- static problem data of this stage -------------------------------------------------------
     // bounds of THIS lane's stage in registers (init_bounds, once per launch): read out of the problem descriptor at every use they
     // cost a three-way select on the stage kind each time and keep ~40 scalar registers busy for the whole kernel
+    // BOX: every lane holds the descriptor's interior bounds (stage 0 and the terminal stage carry the same values for the rows they
+    // have) and there is no mask: a row exists where the stage kind says so — control rows on every stage but the terminal one and a
+    // pinned stage 0, state rows on every stage but stage 0.  The copies are still VECTOR registers, made opaque so that they stay
+    // such: read as scalar operands, the ten bounds went into a scalar file that already spills (+274 v_readlane in the time-sliced
+    // kernel) and the launch was no faster than the generic one (profiles/box_rows.txt).
     double lbr[NW], ubr[NW];
     unsigned hasm = 0;   // bit 2 i + sd: the bound row (i, sd) exists
     MPCRL_DI void init_bounds() {
+        if constexpr (BOX) {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) {
+                double l = sp.lb[i], u_ = sp.ub[i];
+                asm volatile("" : "+v"(l));
+                asm volatile("" : "+v"(u_));
+                lbr[i] = l, ubr[i] = u_;
+            }
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < NW; ++i) {
             double l, u_;
@@ -254,7 +272,29 @@ struct SmallSolver {
     }
     MPCRL_DI double lbv(int i) const { return lbr[i]; }
     MPCRL_DI double ubv(int i) const { return ubr[i]; }
-    MPCRL_DI bool has(int sd, int i) const { return (hasm >> (2 * i + sd)) & 1u; }
+    MPCRL_DI bool has(int sd, int i) const {
+        if constexpr (BOX) return i < NU ? (!term && !(first && qmode)) : !first; else return (hasm >> (2 * i + sd)) & 1u;
+    }
+    // f(i) for the coordinates of v = [u; x] in ascending order — for the row passes, whose f does nothing on a coordinate without
+    // bound rows.  BOX: the control coordinates inside ONE lane-divergent region (the lanes that have control rows) and the state
+    // coordinates inside another, so that a pass costs two exec-mask regions with loop-invariant masks instead of one per row; inside
+    // them has() is known to hold.  Same rows, same order, same arithmetic per row as the generic walk.
+    template <class F>
+    MPCRL_DI void each_coord(F f) const {
+        if constexpr (BOX) {
+            if (has(0, 0)) {
+#pragma unroll
+                for (int i = 0; i < NU; ++i) f(i);
+            }
+            if (has(0, NU)) {
+#pragma unroll
+                for (int i = NU; i < NW; ++i) f(i);
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) f(i);
+        }
+    }
     // (M::soft_coord: which coordinates of v = [u; x] the model's OCP can have L1-soft bounds on — a compile-time fact, so the
     // slack state of the other coordinates never occupies registers; mpcrl_create rejects a spec that asks for more)
     MPCRL_DI bool softc(int i) const { return SOFT && M::soft_coord(i) && !first && !term && sp.soft[i] != 0; }
@@ -363,9 +403,8 @@ struct SmallSolver {
     // ---- NLP residuals (stationarity, equality, inequality, complementarity), local maxima -------
     MPCRL_DI void nlp_res_local(const double *nu_next, const double *x0, const double *u0f, double *res) const {
         double rs = 0, re = 0, ri = 0, rc = 0;
-#pragma unroll
-        for (int i = 0; i < NW; ++i) {
-            if (term && i < NU) continue;
+        each_coord([&](int i) {   // (BOX: a coordinate without rows is a pinned one or the terminal stage's control: nothing to do there)
+            if (term && i < NU) return;
             if (!fixed(i)) {
                 double g = q[i] + GTnu(nu_next, nu_, i);
                 if (has(0, i)) g -= lam[0][i];
@@ -386,7 +425,7 @@ struct SmallSolver {
                         }
                     }
                 }
-        }
+        });
         if (!term) {
 #pragma unroll
             for (int i = 0; i < NX; ++i) re = fmax(re, fabs(r[i]));
@@ -1052,6 +1091,20 @@ struct SmallSolver {
             }
         }
     }
+    // the barrier diagonal dg and the right-hand side rt = rg + (barrier term) of every coordinate at the current QP iterate; a
+    // coordinate without rows has the terms 0.0 (BOX: set before the regions of each_coord, with the same addition)
+    MPCRL_DI void barrier_pass(int pass, double smu, double *dg) {
+        if constexpr (BOX) {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) dg[i] = 0.0, rt[i] = rg[i] + 0.0;
+        }
+        each_coord([&](int i) {
+            const double v = vc(i) + dvc(dx, du, i);
+            double er;
+            barrier_terms(i, v, pass, smu, dg[i], er);
+            rt[i] = rg[i] + er;
+        });
+    }
     // steps of the rows of coordinate i, side sd, for a primal step dv of the coordinate.  rat = the largest of -dlam/lam and
     // -dt/t over these rows: the step to the boundary is 1 / max(rat), so no division is needed per row.
     MPCRL_DI void row_steps(int i, int sd, double v, double dv, int pass, double smu, double &dt1, double &dl1, double &dt2,
@@ -1103,6 +1156,9 @@ struct SmallSolver {
             }
         };
         double cnt = 0.0;
+        // (this pass and the residual rows of a QP's first iteration below run once per QP and keep the per-row walk in BOX too:
+        // walked through each_coord they tip the linear system's one-stage kernel, which shares them, into 43 more spilled VGPRs
+        // — profiles/box_rows.txt)
 #pragma unroll
         for (int i = 0; i < NW; ++i) {
             if (term && i < NU) continue;
@@ -1212,13 +1268,7 @@ struct SmallSolver {
             if (qlive) ++n_it;
             PHW(0);
             // ---- predictor
-            double eaff[NW];
-#pragma unroll
-            for (int i = 0; i < NW; ++i) {
-                const double v = vc(i) + dvc(dx, du, i);
-                barrier_terms(i, v, 0, 0.0, Dg[i], eaff[i]);
-                rt[i] = rg[i] + eaff[i];
-            }
+            barrier_pass(0, 0.0, Dg);
             bool okf;
             PHW(1);
             if constexpr (MX)
@@ -1235,9 +1285,8 @@ struct SmallSolver {
             // length, so the predictor needs ONE cross-lane reduction and one pass over its rows (it was two of each: the rows were
             // walked again, Newton quantities and all, once the step length was known)
             double c12[2] = {0.0, 0.0};
-#pragma unroll
-            for (int i = 0; i < NW; ++i) {
-                if (term && i < NU) continue;
+            each_coord([&](int i) {
+                if (term && i < NU) return;
                 const double v = vc(i) + dvc(dx, du, i), dv = dvc(Dx, Du, i);
 #pragma unroll
                 for (int sd = 0; sd < 2; ++sd) {
@@ -1253,7 +1302,7 @@ struct SmallSolver {
                         c12[0] = fma(lams[sd][ii], dt2, fma(ts[sd][ii], dl2, c12[0])), c12[1] = fma(dl2, dt2, c12[1]);
                     }
                 }
-            }
+            });
             {
                 double two[2] = {rmax, okbad};
                 seg_reduce<2, 2, M::SEG_SKIP, SHORT>(two, c12, k, lpi, base);
@@ -1269,9 +1318,8 @@ struct SmallSolver {
             // the step along (Dx, Du, Dnu) and the rows' directions of `pass`: rows of (i, sd) only read their own side's state, so they
             // can be advanced in place; e12: sum lam t after the step = musum + alpha e12[0] + alpha^2 e12[1]
             auto take_step = [&](int pass, double smu_, double alpha, const double *e12) {
-#pragma unroll
-                for (int i = 0; i < NW; ++i) {
-                    if (term && i < NU) continue;
+                each_coord([&](int i) {
+                    if (term && i < NU) return;
                     const double v = vc(i) + dvc(dx, du, i), dv = dvc(Dx, Du, i);
 #pragma unroll
                     for (int sd = 0; sd < 2; ++sd) {
@@ -1287,7 +1335,7 @@ struct SmallSolver {
                             s[sd][ii] = fma(alpha, dss, s[sd][ii]);
                         }
                     }
-                }
+                });
 #pragma unroll
                 for (int i = 0; i < NX; ++i) dx[i] = fma(alpha, Dx[i], dx[i]), nuq[i] = fma(alpha, Dnu[i], nuq[i]);
 #pragma unroll
@@ -1315,12 +1363,9 @@ struct SmallSolver {
             }
             PHW(4);
             // ---- corrector (same factorisation, vector sweep only)
-#pragma unroll
-            for (int i = 0; i < NW; ++i) {
-                const double v = vc(i) + dvc(dx, du, i);
-                double dgi, ec;
-                barrier_terms(i, v, 1, smu, dgi, ec);
-                rt[i] = rg[i] + ec;
+            {
+                double dgc[NW];   // (the corrector re-uses the predictor's factorisation: its barrier diagonal is computed and discarded)
+                barrier_pass(1, smu, dgc);
             }
             if constexpr (MX)
                 mx_corr(rt, rb);
@@ -1333,9 +1378,8 @@ struct SmallSolver {
             }
             rmax = 1.0;
             double d12[2] = {0.0, 0.0};   // sum lam t after the step = musum + alpha d12[0] + alpha^2 d12[1]
-#pragma unroll
-            for (int i = 0; i < NW; ++i) {
-                if (term && i < NU) continue;
+            each_coord([&](int i) {
+                if (term && i < NU) return;
                 const double v = vc(i) + dvc(dx, du, i), dv = dvc(Dx, Du, i);
 #pragma unroll
                 for (int sd = 0; sd < 2; ++sd) {
@@ -1349,7 +1393,7 @@ struct SmallSolver {
                         d12[0] = fma(lams[sd][ii], dt2, fma(ts[sd][ii], dl2, d12[0])), d12[1] = fma(dl2, dt2, d12[1]);
                     }
                 }
-            }
+            });
             seg_reduce<1, 2, M::SEG_SKIP, SHORT>(&rmax, d12, k, lpi, base);
             if (corr) take_step(1, smu, fmin(1.0, frac * fast_rcp(rmax)), d12);
             PHW(8);
@@ -1590,7 +1634,7 @@ struct SmallSolver {
 #ifndef MPCRL_CARTPOLE_OCC
 #define MPCRL_CARTPOLE_OCC 1     // (2 + MPCRL_CARTPOLE_MAX_IPW=2 + MPCRL_MX_SLOTS=43: the two-wavefronts-per-SIMD experiment of round 6, profiles/README.md)
 #endif
-template <class M, bool SHORT = false>
+template <class M, bool SHORT = false, bool BOX = false>
 __global__ void __launch_bounds__(64, M::DISCRETE ? MPCRL_LINEAR_OCC : MPCRL_CARTPOLE_OCC) small_solve_kernel(const SmallSpec sp, const SmallArgs a) {
     constexpr int NX = M::NX, NU = M::NU, NW = NX + NU, NP = M::NP, NTD = M::NTD, NTC = M::NTC;
     constexpr bool SOFT = M::HAS_SOFT;
@@ -1601,8 +1645,8 @@ __global__ void __launch_bounds__(64, M::DISCRETE ? MPCRL_LINEAR_OCC : MPCRL_CAR
     const bool valid = slot < ipw && inst < a.B;
     if (!valid) inst = a.B - 1;   // dead lanes shadow the last instance and never store
     if (a.perm) inst = a.perm[inst];
-    SmallSolver<M, SHORT> S(sp, k, lpi, base);
-    __shared__ __attribute__((aligned(16))) double mx_lds[SmallSolver<M, SHORT>::MX ? SmallSolver<M, SHORT>::MX_LDS : 2];
+    SmallSolver<M, SHORT, BOX> S(sp, k, lpi, base);
+    __shared__ __attribute__((aligned(16))) double mx_lds[SmallSolver<M, SHORT, BOX>::MX ? SmallSolver<M, SHORT, BOX>::MX_LDS : 2];
     S.ms = mx_lds;
     const bool term = S.term, first = S.first;
     S.qmode = a.u0fix != nullptr;
@@ -1612,13 +1656,13 @@ __global__ void __launch_bounds__(64, M::DISCRETE ? MPCRL_LINEAR_OCC : MPCRL_CAR
     else
         S.ck = first ? sp.dT : (term ? pow(sp.gamma, (double)N) : pow(sp.gamma, (double)k) * sp.dT);   // nlp.py:1083-1091
     const double *th = a.theta + (size_t)inst * a.theta_stride;
-    __shared__ double c_lds[M::MAX_IPW * SmallSolver<M, SHORT>::CTAB];
+    __shared__ double c_lds[M::MAX_IPW * SmallSolver<M, SHORT, BOX>::CTAB];
     S.fill_cost_table(c_lds, slot < ipw ? slot : 0, slot < ipw, th);
-    SmallSolver<M, SHORT>::wave_lds_sync();
+    SmallSolver<M, SHORT, BOX>::wave_lds_sync();
     S.load_hc();
     // (lanes past the last instance slot shadow another instance: they get a slot of their own)
-    __shared__ double th_slots[SmallSolver<M, SHORT>::TH_LDS ? (M::MAX_IPW + 1) * SmallSolver<M, SHORT>::TH_DOUBLES : 1];
-    S.bind_theta(th_slots + (slot < ipw ? slot : M::MAX_IPW) * SmallSolver<M, SHORT>::TH_DOUBLES);
+    __shared__ double th_slots[SmallSolver<M, SHORT, BOX>::TH_LDS ? (M::MAX_IPW + 1) * SmallSolver<M, SHORT, BOX>::TH_DOUBLES : 1];
+    S.bind_theta(th_slots + (slot < ipw ? slot : M::MAX_IPW) * SmallSolver<M, SHORT, BOX>::TH_DOUBLES);
 #pragma unroll
     for (int i = 0; i < NTD; ++i) S.thd.set(i, th[M::td_index(i)]);
 #pragma unroll
@@ -1795,9 +1839,8 @@ __global__ void __launch_bounds__(64, M::DISCRETE ? MPCRL_LINEAR_OCC : MPCRL_CAR
 #pragma unroll
             for (int m = 0; m < NX; ++m) lag = fma(nun[m], S.r[m], lag);
         }
-#pragma unroll
-        for (int i = 0; i < NW; ++i) {
-            if (term && i < NU) continue;
+        S.each_coord([&](int i) {
+            if (term && i < NU) return;
 #pragma unroll
             for (int sd = 0; sd < 2; ++sd)
                 if (S.has(sd, i)) {
@@ -1806,7 +1849,7 @@ __global__ void __launch_bounds__(64, M::DISCRETE ? MPCRL_LINEAR_OCC : MPCRL_CAR
                         if (S.softc(i)) lag = fma(-S.lams[sd][S.ss(i)], S.s[sd][S.ss(i)], lag);
                     }
                 }
-        }
+        });
         lag = seg_sum<M::SEG_SKIP, SHORT>(lag, k, lpi, base);
     }
     if (valid && first) {
@@ -1869,7 +1912,7 @@ inline bool sliced_parks_in_lds(int N) { return (N + 1) * sliced_park_words<M>()
 
 // WARM: the instances start from their stored iterates (and the per-instance cold mask), as in small_solve_kernel — a separate
 // instantiation, so that the cold one keeps its register allocation.
-template <class M, bool LDSPARK, bool WARM = false, bool SHORT = false>
+template <class M, bool LDSPARK, bool WARM = false, bool SHORT = false, bool BOX = false>
 __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSpec sp, const SmallArgs a) {
     constexpr int NX = M::NX, NU = M::NU, NW = NX + NU, NP = M::NP, NTD = M::NTD, NTC = M::NTC;
     static_assert(!M::HAS_SOFT, "hard bounds only");
@@ -1889,9 +1932,9 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
     const double *x0 = nullptr, *u0f = nullptr, *th = nullptr;
     double *bnd = nullptr;
     const size_t nb = (size_t)(N + 1) * NW;
-    SmallSolver<M, SHORT> S(sp, k, lpi, base);
-    __shared__ __attribute__((aligned(16))) double mx_lds[SmallSolver<M, SHORT>::MX ? SmallSolver<M, SHORT>::MX_LDS : 2];
-    __shared__ double c_lds[M::MAX_IPW * SmallSolver<M, SHORT>::CTAB];
+    SmallSolver<M, SHORT, BOX> S(sp, k, lpi, base);
+    __shared__ __attribute__((aligned(16))) double mx_lds[SmallSolver<M, SHORT, BOX>::MX ? SmallSolver<M, SHORT, BOX>::MX_LDS : 2];
+    __shared__ double c_lds[M::MAX_IPW * SmallSolver<M, SHORT, BOX>::CTAB];
     // parked scalars: live, status, iterations, interior-point iterations, ... (5 doubles; a stride of 5 costs the WARM
     // instantiations 12 more spilled VGPRs, measured: the slots stay 6 doubles apart)
     constexpr int SC = 6;
@@ -1934,7 +1977,7 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
         S.ck = first ? sp.dT : (term ? pow(sp.gamma, (double)N) : pow(sp.gamma, (double)k) * sp.dT);
     // cost tables of all ipw + 1 instances (the parked one's by the first lane past the slots, which is a stage-0 lane)
     S.fill_cost_table(c_lds, loc, (slot_on || (slot == ipw && k == 0)) && posof(loc) < a.B, th);
-    SmallSolver<M, SHORT>::wave_lds_sync();
+    SmallSolver<M, SHORT, BOX>::wave_lds_sync();
     auto bind = [&](int l) {
         valid = slot_on && posof(l) < a.B;
         const long i = gi_lds[l];
@@ -1946,7 +1989,7 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
     if (!slot_on) loc = 0;                            // from here on the lanes past the slots shadow slot 0's instance
     bind(loc);
     auto load_params = [&]() {
-        S.ctab = c_lds + loc * SmallSolver<M, SHORT>::CTAB + S.stage_kind() * SmallSolver<M, SHORT>::CSET;
+        S.ctab = c_lds + loc * SmallSolver<M, SHORT, BOX>::CTAB + S.stage_kind() * SmallSolver<M, SHORT, BOX>::CSET;
         S.load_hc();
 #pragma unroll
         for (int i = 0; i < NTD; ++i) S.thd.set(i, th_lds[loc * TH + i]);
@@ -2061,13 +2104,12 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
 #pragma unroll
                     for (int m = 0; m < NX; ++m) lag = fma(nun[m], S.r[m], lag);
                 }
-#pragma unroll
-                for (int i = 0; i < NW; ++i) {
-                    if (term && i < NU) continue;
+                S.each_coord([&](int i) {
+                    if (term && i < NU) return;
 #pragma unroll
                     for (int sd = 0; sd < 2; ++sd)
                         if (S.has(sd, i)) lag = fma(-S.lam[sd][i], S.bslack(sd, i, S.vc(i)), lag);
-                }
+                });
                 lag = seg_sum<M::SEG_SKIP, SHORT>(lag, k, lpi, base);
             }
             if (fin_now && valid) {
@@ -2191,7 +2233,7 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
                 sc[1] = (double)n_ipm, sc[2] = stepn, sc[3] = rbest, sc[4] = rchk;
             }
         }
-        SmallSolver<M, SHORT>::wave_lds_sync();                // orders the stores above before the loads below (same wavefront: in order)
+        SmallSolver<M, SHORT, BOX>::wave_lds_sync();                // orders the stores above before the loads below (same wavefront: in order)
         // take the parked instance: every lane runs the same loads, the lanes of the slot keep the results
         const int newloc = sw ? pk : loc;
         loc = newloc;
