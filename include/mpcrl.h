@@ -111,7 +111,8 @@ extern "C" {
  *        mpcrl_qlearning_gn_apply_box (that step as a box QP: bounds on theta and a per-entry trust region);
  *        mpcrl_cdpg_record; mpcrl_cdpg_terms / mpcrl_cdpg_workspace_bytes; mpcrl_cdpg_apply (the deterministic policy gradient with a
  *        compatible linear critic, from the roll-out's own du0/dp); mpcrl_debug_seg_reduce (test probe of the small-model
- *        kernels' segmented reductions); mpcrl_query_box_rows (which form of the cartpole solve kernels the handle's bounds select) */
+ *        kernels' segmented reductions); mpcrl_query_box_rows (which form of the cartpole solve kernels the handle's bounds select);
+ *        mpcrl_debug_model_jets (test probe of the dynamics jets: the discrete map and its derivatives, point by point) */
 #define MPCRL_ABI_VERSION 132
 
 enum { MPCRL_MODEL_CARTPOLE = 0, MPCRL_MODEL_LINEAR = 1, MPCRL_MODEL_CHAIN = 2 };
@@ -698,6 +699,22 @@ int mpcrl_ppo_log_std_apply_nu(const double *msg, int n_p, int nu, double *log_s
  * the cartpole kernels instantiate them, 2 = as the linear system's.  (n_max, n_sum) is one of (0,1) (1,0) (1,1) (2,2) (1,2) (4,1),
  * the shapes the kernels reduce; anything else: MPCRL_E_ARG. */
 int mpcrl_debug_seg_reduce(const double *in, int lpi, int n_max, int n_sum, int which, double *out, void *stream);
+
+/* Added under ABI 132.  TEST PROBE of the dynamics jets of the cartpole / linear-system kernels (jet_probe_kernel.hpp): the discrete map
+ * of the model (RK4^rk_steps with step h; the linear system's map is discrete, h and rk_steps are not read) evaluated at n >= 1
+ * points, one lane each, with the jets seeded as the kernels seed them.  x [n][nx], u [n][nu], th [n][NTD] (the parameters the
+ * dynamics depend on: M, m, l / A column-major, B, b), out [n][row]: device arrays of doubles on one device.  With NW = nu + nx,
+ * NLD = 3 directions (cartpole: u, theta, theta_dot; linear system: u, x_0, x_1), NH = NLD (NLD + 1) / 2 (packed lower triangle,
+ * (i, j) at i (i + 1) / 2 + j) one row of out is
+ *   which 0  Jet1<NLD>, the solve's linearisation:      F[nx], BA[nx][NW] (columns in stage-vector order v = [u; x], all of them)
+ *   which 1  JetH<NLD>, the sensitivity pass's:         F, BA, H[nx][NH], hdd[NH] = sum_m aux[m] H[m];    aux = nu [n][nx]
+ *   which 2  Jet1<NTD>, dF/dtheta:                      F, Fth[nx][NTD]
+ *   which 3  Jet2<NTD>, the mixed second-order pass:    F, e[nx] = dF/dv y, g[nx][NTD] = dF/dtheta, m[nx][NTD] = d2F/dtheta dv y;  aux = y [n][NW]
+ *   which 4  out[i] = 1 / x[i] as the jets compute it (jet_rcp), n doubles; model, h, rk_steps, u, th, aux are not read.
+ * MPCRL_E_ARG: a null or non-device pointer among those the form reads, n < 1, which outside 0..4, rk_steps outside 1..4 for the
+ * cartpole, MPCRL_MODEL_CHAIN (its derivatives do not go through the jets). */
+int mpcrl_debug_model_jets(int model, int which, int n, double h, int rk_steps, const double *x, const double *u, const double *th,
+                           const double *aux, double *out, void *stream);
 
 /* Bytes of device memory held by the handle; library version (MPCRL_ABI_VERSION of the header it was built from). */
 int64_t mpcrl_workspace_bytes(mpcrl_handle h);

@@ -27,6 +27,7 @@
 #include "value_kernel.hpp"
 #include "linear_loop_kernel.hpp"
 #include "chain_env_kernel.hpp"
+#include "jet_probe_kernel.hpp"
 
 using namespace mpcrl;
 
@@ -463,6 +464,39 @@ int mpcrl_debug_seg_reduce(const double *in, int lpi, int n_max, int n_sum, int 
     // the shapes the kernels reduce (small_kernel.hpp): single sums and maxima, the interior point's three passes, the SQP round's
     MPCRL_SEG_PROBE(0, 1) MPCRL_SEG_PROBE(1, 0) MPCRL_SEG_PROBE(1, 1) MPCRL_SEG_PROBE(2, 2) MPCRL_SEG_PROBE(1, 2) MPCRL_SEG_PROBE(4, 1)
 #undef MPCRL_SEG_PROBE
+    return MPCRL_E_ARG;
+}
+
+int mpcrl_debug_model_jets(int model, int which, int n, double h, int rk_steps, const double *x, const double *u, const double *th,
+                           const double *aux, double *out, void *stream) {
+    if (n < 1 || which < 0 || which > 4 || !x || !out) return MPCRL_E_ARG;
+    const hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((n + 63) / 64)), block(64);
+    if (which == 4) {
+        if (device_of(x) < 0 || device_of(x) != device_of(out)) return MPCRL_E_ARG;
+        ON_DEVICE_OF(out);
+        hipLaunchKernelGGL(jet_rcp_probe_kernel, grid, block, 0, st, n, x, out);
+        HIP_OK(hipGetLastError());
+        return 0;
+    }
+    const bool need_aux = which == 1 || which == 3;
+    if (!u || !th || (need_aux && !aux)) return MPCRL_E_ARG;
+    if (model != MPCRL_MODEL_CARTPOLE && model != MPCRL_MODEL_LINEAR) return MPCRL_E_ARG;   // the chain's derivatives do not go through the jets
+    if (model == MPCRL_MODEL_CARTPOLE && (rk_steps < 1 || rk_steps > 4)) return MPCRL_E_ARG;
+    for (const void *q : {(const void *)x, (const void *)u, (const void *)th, (const void *)(need_aux ? aux : x)})
+        if (device_of(q) < 0 || device_of(q) != device_of(out)) return MPCRL_E_ARG;
+    ON_DEVICE_OF(out);
+#define MPCRL_JET_PROBE(MODEL, DEV, W) \
+    if (model == MODEL && which == W) { \
+        hipLaunchKernelGGL((jet_probe_kernel<DEV, W>), grid, block, 0, st, n, h, rk_steps, x, u, th, aux, out); \
+        HIP_OK(hipGetLastError()); \
+        return 0; \
+    }
+    MPCRL_JET_PROBE(MPCRL_MODEL_CARTPOLE, CartpoleDev, 0) MPCRL_JET_PROBE(MPCRL_MODEL_CARTPOLE, CartpoleDev, 1)
+    MPCRL_JET_PROBE(MPCRL_MODEL_CARTPOLE, CartpoleDev, 2) MPCRL_JET_PROBE(MPCRL_MODEL_CARTPOLE, CartpoleDev, 3)
+    MPCRL_JET_PROBE(MPCRL_MODEL_LINEAR, LinearDev, 0) MPCRL_JET_PROBE(MPCRL_MODEL_LINEAR, LinearDev, 1)
+    MPCRL_JET_PROBE(MPCRL_MODEL_LINEAR, LinearDev, 2) MPCRL_JET_PROBE(MPCRL_MODEL_LINEAR, LinearDev, 3)
+#undef MPCRL_JET_PROBE
     return MPCRL_E_ARG;
 }
 
