@@ -112,7 +112,8 @@ extern "C" {
  *        mpcrl_cdpg_record; mpcrl_cdpg_terms / mpcrl_cdpg_workspace_bytes; mpcrl_cdpg_apply (the deterministic policy gradient with a
  *        compatible linear critic, from the roll-out's own du0/dp); mpcrl_debug_seg_reduce (test probe of the small-model
  *        kernels' segmented reductions); mpcrl_query_box_rows (which form of the cartpole solve kernels the handle's bounds select);
- *        mpcrl_debug_model_jets (test probe of the dynamics jets: the discrete map and its derivatives, point by point) */
+ *        mpcrl_debug_model_jets (test probe of the dynamics jets: the discrete map and its derivatives, point by point);
+ *        mpcrl_debug_launch_plan (test probe of the launch plan of the small-model solves: a pure host function) */
 #define MPCRL_ABI_VERSION 132
 
 enum { MPCRL_MODEL_CARTPOLE = 0, MPCRL_MODEL_LINEAR = 1, MPCRL_MODEL_CHAIN = 2 };
@@ -715,6 +716,20 @@ int mpcrl_debug_seg_reduce(const double *in, int lpi, int n_max, int n_sum, int 
  * cartpole, MPCRL_MODEL_CHAIN (its derivatives do not go through the jets). */
 int mpcrl_debug_model_jets(int model, int which, int n, double h, int rk_steps, const double *x, const double *u, const double *th,
                            const double *aux, double *out, void *stream);
+
+/* Added under ABI 132.  TEST PROBE of the launch plan of the cartpole / linear-system solves (csrc/launch_plan.hpp, plan_small): the
+ * pure function mpcrl_solve and mpcrl_query_time_sliced decide with, for inputs given as numbers.  No handle, no device, no launch.
+ * model: MPCRL_MODEL_CARTPOLE or _LINEAR; N: horizon, 2 .. 63; B >= 1: batch; n_simd >= 1: SIMDs of the device; flags: of mpcrl_solve,
+ * COLD already resolved; slice_mode: -1, 0, 1 as mpcrl_set_launch_mode; box_rows: what mpcrl_query_box_rows says; linear_spl: 3, or 1
+ * for MPCRL_LINEAR_SPL=1; shape: what the tuner says, 0 = time-sliced, 1 = plain (read only where slice_mode == 0 and out[9], out[10]
+ * are both 1).  Anything else: MPCRL_E_ARG.  out:
+ *   [0] family: 0 plain (small_solve_kernel), 1 time-sliced (small_solve_sliced_kernel), 2 lq_solve_kernel, 3 the exact-QP instantiation
+ *   [1] SHORT form of the segmented reductions   [2] BOX form (families 0, 1)   [3] parked instance in LDS (family 1)   [4] warm
+ *   [5], [6] stages per lane and row lanes of lq_solve_kernel (family 2, else 0)
+ *   [7] workgroups of the solve launch   [8] workgroups of the separate sensitivity launch, 0 = none
+ *   [9] a time-sliced launch is legal   [10] the wave-count rule favours it   [11] 0 (reserved) */
+int mpcrl_debug_launch_plan(int model, int N, int B, int n_simd, int flags, int slice_mode, int box_rows, int linear_spl, int shape,
+                            int32_t out[12]);
 
 /* Bytes of device memory held by the handle; library version (MPCRL_ABI_VERSION of the header it was built from). */
 int64_t mpcrl_workspace_bytes(mpcrl_handle h);

@@ -1,7 +1,9 @@
-// mpcrl_host.hpp — what the translation units of libmpcrl_hip.so share on the host side: the handle, the error macro, and the table
-// through which mpcrl_api.hip reaches the chain-of-masses kernels.  The library is built from one translation unit per chain size
-// (chain_inst.hip, -DMPCRL_CHAIN_NMASS=3..7) next to mpcrl_api.hip (C ABI, cartpole / linear-system kernels, library kernels), so that
-// the sizes compile in parallel (csrc/Makefile); every unit carries its own device code, nothing is linked on the device side.
+// mpcrl_host.hpp — what the translation units of libmpcrl_hip.so share on the host side: the handle, the error macro, the device
+// guards, the workspace layout of the kernels that hand off to their last workgroup, and the table through which mpcrl_api.hip
+// reaches the chain-of-masses kernels.  The library is built from one translation unit per chain size (chain_inst.hip,
+// -DMPCRL_CHAIN_NMASS=3..7) next to mpcrl_api.hip (the handle's C ABI, cartpole / linear-system solve kernels) and mpcrl_loops.hip
+// (the handle-less library kernels of the RL loops), so that they compile in parallel and an edit recompiles its own unit only
+// (csrc/Makefile); every unit carries its own device code, nothing is linked on the device side.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,12 +39,10 @@ struct MpcrlSolver {
     bool generic_rows = false;  // MPCRL_GENERIC_ROWS=1 at mpcrl_create: never the BOX instantiations of the cartpole solve kernels
     bool box_rows = false;      // the bounds are the full-box pattern those instantiations compile in (box_rows_spec; mpcrl_set_bounds keeps it current)
     // automatic mode: the two launch shapes of the small solve kernel are timed against each other on the caller's own batches
-    // (choose_launch below): [0] = time-sliced, [1] = plain
-    struct Tuner {
+    // (choose_shape in mpcrl_api.hip; times and call count: launch_plan.hpp): [0] = time-sliced, [1] = plain
+    struct Tuner : mpcrl::TunerState {
         hipEvent_t ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
         bool pending[2] = {false, false};
-        float ms[2] = {-1.f, -1.f};
-        unsigned calls = 0;
     } tune[2];                  // [0] cold calls, [1] warm calls (different work per instance: timed separately)
     int planned = -1;           // what mpcrl_query_time_sliced promised for the next solve (-1: nothing promised)
     bool have_iterate = false;
@@ -68,3 +68,47 @@ struct MpcrlChainEntry {
     int (*debug_phases)(unsigned long long *out16, int reset);      // -DMPCRL_PROFILE_PHASES builds: the unit's phase ticks (else null)
 };
 const MpcrlChainEntry *mpcrl_chain_entry_3(), *mpcrl_chain_entry_4(), *mpcrl_chain_entry_5(), *mpcrl_chain_entry_6(), *mpcrl_chain_entry_7();
+
+// switches to the handle's device for the duration of a call and restores the caller's device afterwards
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = true;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceGuard() {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+#define ON_DEVICE(dev)            \
+    DeviceGuard guard_((dev));    \
+    if (!guard_.ok) return MPCRL_E_HIP
+
+// the handle-less library kernels (reduction, environments) launch on the device that OWNS the memory they are given, whatever device
+// is current in the calling thread; -1 if the pointer is not device memory
+inline int device_of(const void *p) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
+    }
+    // device memory, or managed memory (its home device); host-registered / unregistered pointers are refused
+    return (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged) ? at.device : -1;
+}
+#define ON_DEVICE_OF(ptr)                       \
+    const int dev_of_ = device_of((ptr));       \
+    if (dev_of_ < 0) return MPCRL_E_ARG;        \
+    ON_DEVICE(dev_of_)
+
+// The workspace of a kernel that hands off to its last workgroup (batch_sum.hpp): the ticket, then one row of `cols` doubles per
+// workgroup, a workgroup taking `rows_per_block` of the `rows` terms.
+inline int64_t ticket_blocks(int64_t rows, int rows_per_block) { return (rows + rows_per_block - 1) / rows_per_block; }
+inline int64_t ticket_workspace_bytes(int64_t rows, int rows_per_block, int cols) {
+    return 16 + ticket_blocks(rows, rows_per_block) * cols * (int64_t)sizeof(double);
+}
+template <class Args>
+void set_ticket_workspace(Args &a, void *workspace) {
+    a.ticket = (unsigned int *)workspace, a.partial = (double *)((char *)workspace + 16);
+}

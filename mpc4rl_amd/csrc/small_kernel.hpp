@@ -21,6 +21,9 @@
 // The interior-point iteration (initial point, Mehrotra predictor-corrector, single step length,
 // fraction to the boundary max(0.995, 1 - mu), stopping rule) is the one documented in DESIGN.md; its constants are below.
 #pragma once
+#include <type_traits>
+
+#include "launch_plan.hpp"
 #include "models_dev.hpp"
 
 namespace mpcrl {
@@ -1901,14 +1904,15 @@ __global__ void __launch_bounds__(64, M::DISCRETE ? MPCRL_LINEAR_OCC : MPCRL_CAR
 // attempt of round 1 (claims by compare-and-swap) could not have.  An instance that finishes is written out at once and
 // its slot goes to the parked instance for good.  The iteration of an instance is bit-for-bit the one of small_solve_kernel.
 // =====================================================================================================
-// LDSPARK: where the parked instance lives (chosen by the host from the horizon: sliced_parks_in_lds); a template parameter so that
+// LDSPARK: where the parked instance lives (chosen by the host from the horizon: sliced_parks_in_lds, launch_plan.hpp); a template parameter so that
 // the kernel of the short horizons carries neither the code nor the pointers of the HBM exchange.
+// What the host's launch plan (launch_plan.hpp) knows of model M — the one place it consults the model classes; the kernel below
+// reads the parked state's size and LDS cap from the same constants.
 template <class M>
-constexpr int sliced_park_words() { return 2 * M::NX + M::NU + 4 * (M::NX + M::NU); }
-template <class M>
-constexpr int sliced_park_cap() { return (M::NX == 4 && M::NU == 1) ? 21 * sliced_park_words<M>() : 64 * sliced_park_words<M>(); }
-template <class M>
-inline bool sliced_parks_in_lds(int N) { return (N + 1) * sliced_park_words<M>() <= sliced_park_cap<M>(); }
+constexpr SmallTraits small_traits() {
+    return {M::NX, M::NU, M::MAX_IPW, sliced_park_words(M::NX, M::NU), sliced_park_cap(M::NX, M::NU), M::HAS_SOFT, M::SEG_SKIP,
+            std::is_same<M, CartpoleDev>::value, std::is_same<M, LinearDev>::value};
+}
 
 // WARM: the instances start from their stored iterates (and the per-instance cold mask), as in small_solve_kernel — a separate
 // instantiation, so that the cold one keeps its register allocation.
@@ -1944,8 +1948,8 @@ __global__ void __launch_bounds__(64, 1) small_solve_sliced_kernel(const SmallSp
     // the LDS of a CU is shared by four wavefronts, 40 960 B each); longer horizons park in the instance's stored-iterate arrays
     // in HBM, which costs a global round trip per round (3.3 us of a 45 us round: 8 % of the launch).
     constexpr int PK = 2 * NX + NU + 4 * NW;
-    static_assert(PK == sliced_park_words<M>(), "host and kernel agree on the parked state");
-    constexpr int PARK_CAP = LDSPARK ? sliced_park_cap<M>() : 1;
+    static_assert(PK == small_traits<M>().park_words, "host and kernel agree on the parked state");
+    constexpr int PARK_CAP = LDSPARK ? small_traits<M>().park_cap : 1;
     __shared__ double park_lds[PARK_CAP];
     constexpr bool lds_park = LDSPARK;
     S.ms = mx_lds;

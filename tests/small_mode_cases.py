@@ -2,7 +2,7 @@
 linear-system kernels at every horizon where their lane layout or their kernel changes, the references of the C++ CPU port (oracle/cpu)
 on those inputs, computed once per (model, N), and the comparison helpers (used by tests/test_gpu_chain_modes.py as well).
 
-Lane layouts (mpcrl_api.hip launch_small, sliced_candidate; small_kernel.hpp sliced_parks_in_lds):
+Lane layouts (csrc/launch_plan.hpp: plan_small, sliced_parks_in_lds):
   cartpole   min(64 / (N + 1), 4) instances per wavefront: 4 up to N = 15, 3 up to N = 20, 2 up to N = 31, 1 from N = 32.  The
              time-sliced launch holds one instance fewer per round (at most 3) plus a parked one, in LDS up to N = 20 and in HBM from
              N = 21; it needs a spare lane, so it is illegal at N = 31 (two 32-lane slots) and N = 63 (64 stages).

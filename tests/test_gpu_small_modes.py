@@ -21,17 +21,20 @@ have (the bounds of u_0 in Q mode), the multipliers its warm start held, where t
 next V-mode call then started its interior point elsewhere on the two sides (35 against 20 interior-point iterations on one instance at
 linear N = 48) and stopped 3.1e-6 (X) from the kernel's answer, both 1e-5 from the solution along a weakly active row; cartpole 7.8e-8.
 The port now stores the cold values for such rows (oracle/cpu/mpc_oracle.cpp), and the counts are equal on every instance."""
+import os
+
 import numpy as np
 import pytest
 import torch
 
+import launch_plan_cases as P
 import small_mode_cases as C
 from small_mode_cases import RTOL, bit_equal, compare, outputs, raw_solve, same_statuses
 
 pytestmark = pytest.mark.gpu
 
 CARTPOLE_MODES = (-1, 1)      # set_launch_mode: plain, time-sliced where legal
-SLICING_ILLEGAL = (31, 63)    # sliced_candidate: no spare lane beside the resident slots (2 x 32 and 1 x 64 lanes)
+SLICING_ILLEGAL = (31, 63)    # launch_plan.hpp, candidate: no spare lane beside the resident slots (2 x 32 and 1 x 64 lanes)
 
 
 def shapes(model, horizons):
@@ -98,7 +101,7 @@ def horizon_case(c, mode):
     snaps = []
     for u0, ref in ((None, c.ref_v), (c.u0, c.ref_q)):
         mpc = handle(c, mode)
-        if c.model == "cartpole":      # the launch shape this call takes (read off sliced_candidate, not found out by running)
+        if c.model == "cartpole":      # the launch shape this call takes (read off the launch plan's rule, not found out by running)
             expect = 1 if (mode == 1 and c.N not in SLICING_ILLEGAL) else 0
             assert mpc.lib.mpcrl_query_time_sliced(mpc._h, sens_flags(True), mpc._stream()) == expect
         r = raw_solve(mpc, c.x0, u0)
@@ -317,3 +320,57 @@ def test_nan_instance_leaves_its_neighbours_alone(oracle_port, model, N, mode):
     assert bool((r.dV_dp[1] == 0.0).all()) and bool((r.dpi_dp[1] == 0.0).all())
     others = torch.arange(c.B, device="cuda") != 1
     same_bits(snapshot(mpc, r), snapshot(clean, rc), rows=others, lagrangian=False)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 6. the query, the launch plan and the launch are one decision
+# ---------------------------------------------------------------------------------------------------------------------------------
+QUERY_B = 8
+QUERY_SLICED = {("cartpole", 20): 1, ("cartpole", 31): 0, ("cartpole", 40): 1, ("linear", 7): 0, ("linear", 8): 0}      # in mode 1; mode -1: never
+
+
+@pytest.mark.parametrize("model,N", sorted(QUERY_SLICED))
+def test_query_is_the_plan_and_the_launch(model, N):
+    """mpcrl_query_time_sliced of a handle = `family == SLICED` of mpcrl_debug_launch_plan (and of its restatement) for the handle's
+    numbers, outside a stream capture and inside one, where the query adds nothing to the graph; the solve after the query returns the
+    bits of the other launch mode's.  Cartpole with the parked instance in LDS (N = 20), without a spare lane (31), on the full tree
+    (40); the linear system either side of its kernel change; cold and warm calls."""
+    from mpc4rl_amd import MPCBatch, _lib
+    ocp = C.problem(model, N)[0]
+    x0, _, step = C.inputs(model)
+    points = {True: x0[:QUERY_B], False: x0[:QUERY_B] + step[:QUERY_B]}
+    n_simd = 4 * torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    spl = 1 if os.environ.get("MPCRL_LINEAR_SPL", "").startswith("1") else 3
+    side, marker = torch.cuda.Stream(), torch.zeros(1, device="cuda")
+    snaps = {}
+    for mode in CARTPOLE_MODES:
+        mpc = MPCBatch(ocp, QUERY_B)
+        mpc.set_launch_mode(mode)
+        for cold in (True, False):
+            flags = sens_flags(cold)
+            args = (N, QUERY_B, n_simd, flags, mode, mpc.lib.mpcrl_query_box_rows(mpc._h), spl, P.TUNE_SLICED)
+            out = (_lib.C.c_int32 * 12)()
+            assert mpc.lib.mpcrl_debug_launch_plan(P.MODELS[model]["id"], *args, out) == 0
+            assert list(out) == P.expected(model, *args)
+            want = int(out[0] == P.SLICED)
+            assert want == (QUERY_SLICED[model, N] if mode == 1 else 0)
+            assert mpc.lib.mpcrl_query_time_sliced(mpc._h, flags, mpc._stream()) == want
+            # inside a capture: the same answer, and a graph that holds the marker's increment alone — replaying it leaves the handle as it was
+            before = [t.clone() for t in mpc.get_iterate()]
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side):
+                captured = mpc.lib.mpcrl_query_time_sliced(mpc._h, flags, mpc._stream())
+                marker.add_(1.0)
+            assert captured == want
+            count = float(marker)
+            g.replay()
+            torch.cuda.synchronize()
+            assert float(marker) == count + 1.0
+            assert all(torch.equal(a, b) for a, b in zip(before, mpc.get_iterate()))
+            r = raw_solve(mpc, points[cold], flags=flags)
+            assert bool((r.status == 0).all())
+            snaps[mode, cold] = snapshot(mpc, r)
+    for cold in (True, False):
+        same_bits(snaps[-1, cold], snaps[1, cold])
+    assert not torch.equal(snaps[1, True][0].V, snaps[1, False][0].V)      # the warm call was another problem than the cold one

@@ -24,7 +24,7 @@ EPS = 2.0 ** -53
 def test_new_symbols_in_header_binding_and_library():
     from mpc4rl_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "mpcrl.h")).read()
-    api = open(os.path.join(ROOT, "mpc4rl_amd", "csrc", "mpcrl_api.hip")).read()
+    api = open(os.path.join(ROOT, "mpc4rl_amd", "csrc", "mpcrl_loops.hip")).read()
     declared = sorted(set(re.findall(r"\b(mpcrl_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))))   # as tests/test_cabi.py reads it
     assert sorted(_lib.EXPORTS) == declared
     for name in NEW:

@@ -21,7 +21,7 @@ NEW = "mpcrl_qlearning_gn_apply_box"
 def test_new_symbol_in_header_and_binding_abi132():
     from mpc4rl_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "mpcrl.h")).read()
-    api = open(os.path.join(ROOT, "mpc4rl_amd", "csrc", "mpcrl_api.hip")).read()
+    api = open(os.path.join(ROOT, "mpc4rl_amd", "csrc", "mpcrl_loops.hip")).read()
     assert re.search(r"\b" + NEW + r"\(", hdr) and re.search(r"\b" + NEW + r"\(", api) and NEW in _lib.EXPORTS
     assert int(re.search(r"#define MPCRL_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 132
     if os.path.exists(_lib.LIB_PATH):

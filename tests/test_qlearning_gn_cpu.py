@@ -21,7 +21,7 @@ EPS = 2.0 ** -53
 def test_new_symbols_in_header_and_binding_abi132():
     from mpc4rl_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "mpcrl.h")).read()
-    api = open(os.path.join(ROOT, "mpc4rl_amd", "csrc", "mpcrl_api.hip")).read()
+    api = open(os.path.join(ROOT, "mpc4rl_amd", "csrc", "mpcrl_loops.hip")).read()
     for name in NEW:
         assert re.search(r"\b" + name + r"\(", hdr), name
         assert re.search(r"\b" + name + r"\(", api), name
