@@ -113,7 +113,8 @@ extern "C" {
  *        compatible linear critic, from the roll-out's own du0/dp); mpcrl_debug_seg_reduce (test probe of the small-model
  *        kernels' segmented reductions); mpcrl_query_box_rows (which form of the cartpole solve kernels the handle's bounds select);
  *        mpcrl_debug_model_jets (test probe of the dynamics jets: the discrete map and its derivatives, point by point);
- *        mpcrl_debug_launch_plan (test probe of the launch plan of the small-model solves: a pure host function) */
+ *        mpcrl_debug_launch_plan (test probe of the launch plan of the small-model solves: a pure host function);
+ *        mpcrl_debug_get_order (test probe of the packing order: the permutation and the order kernel's remembered range) */
 #define MPCRL_ABI_VERSION 132
 
 enum { MPCRL_MODEL_CARTPOLE = 0, MPCRL_MODEL_LINEAR = 1, MPCRL_MODEL_CHAIN = 2 };
@@ -730,6 +731,13 @@ int mpcrl_debug_model_jets(int model, int which, int n, double h, int rk_steps, 
  *   [9] a time-sliced launch is legal   [10] the wave-count rule favours it   [11] 0 (reserved) */
 int mpcrl_debug_launch_plan(int model, int N, int B, int n_simd, int flags, int slice_mode, int box_rows, int linear_spl, int shape,
                             int32_t out[12]);
+
+/* Added under ABI 132.  TEST PROBE of the packing order (mpcrl_set_order, mpcrl_auto_order; csrc/order_kernel.hpp): what the next
+ * mpcrl_solve of the handle would read.  Returns 1 if that solve would use a packing order, 0 if the identity, < 0 on misuse (a null
+ * handle).  perm_out (device, [B] int32, may be NULL): filled with the handle's permutation when the return value is 1, left alone
+ * otherwise.  state_out (device, [3] double, may be NULL): {spread, minimum, coordinate} of the batch mpcrl_auto_order last ordered
+ * from scratch, {-1, 0, 0} before the first such call.  Both copies are asynchronous on `stream`; nothing in the handle changes. */
+int mpcrl_debug_get_order(mpcrl_handle h, int32_t *perm_out, double *state_out, void *stream);
 
 /* Bytes of device memory held by the handle; library version (MPCRL_ABI_VERSION of the header it was built from). */
 int64_t mpcrl_workspace_bytes(mpcrl_handle h);

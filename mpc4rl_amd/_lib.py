@@ -39,7 +39,7 @@ EXPORTS = ["mpcrl_create", "mpcrl_destroy", "mpcrl_set_theta", "mpcrl_set_gamma"
            "mpcrl_ppo_chain_collect", "mpcrl_ppo_surrogate_workspace_bytes_nu", "mpcrl_ppo_surrogate_grad_nu", "mpcrl_ppo_log_std_apply_nu",
            "mpcrl_qlearning_gn_workspace_bytes", "mpcrl_qlearning_td_gn", "mpcrl_qlearning_gn_apply", "mpcrl_qlearning_gn_apply_box",
            "mpcrl_cdpg_record", "mpcrl_cdpg_workspace_bytes", "mpcrl_cdpg_terms", "mpcrl_cdpg_apply",
-           "mpcrl_debug_seg_reduce", "mpcrl_query_box_rows", "mpcrl_debug_model_jets", "mpcrl_debug_launch_plan"]
+           "mpcrl_debug_seg_reduce", "mpcrl_query_box_rows", "mpcrl_debug_model_jets", "mpcrl_debug_launch_plan", "mpcrl_debug_get_order"]
 
 _lib = None
 
@@ -141,6 +141,7 @@ def load():
     lib.mpcrl_debug_seg_reduce.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.mpcrl_debug_model_jets.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.mpcrl_debug_launch_plan.argtypes = [C.c_int] * 9 + [_ip]
+    lib.mpcrl_debug_get_order.argtypes = [vp, vp, vp, vp]
     lib.mpcrl_workspace_bytes.argtypes = [vp]
     lib.mpcrl_workspace_bytes.restype = C.c_int64
     for name in EXPORTS:

@@ -136,6 +136,23 @@ class MPCBatch:
             self._check(self.lib.mpcrl_reset(self._h, _ptr(x0t), self._stream()), "mpcrl_reset")
         self.has_iterate = self.duals_valid = False
 
+    def set_order(self, perm) -> None:
+        """mpcrl_set_order: perm [B], a permutation of 0..B-1 (validity is the caller's contract) — slot i of the next launches works
+        on instance perm[i]; None = identity.  A scheduling hint: no effect on results."""
+        p = None if perm is None else torch.as_tensor(perm, device=self.device).to(torch.int32).reshape(self.B).contiguous()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.mpcrl_set_order(self._h, _ptr(p), self._stream()), "mpcrl_set_order")
+
+    def get_order(self):
+        """(perm [B] int32 or None = identity, state [3] = {spread, minimum, coordinate} of the last from-scratch auto order): what the
+        next solve would read (mpcrl_debug_get_order, a test probe)."""
+        perm = torch.empty((self.B,), dtype=torch.int32, device=self.device)
+        state = torch.empty((3,), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self.lib.mpcrl_debug_get_order(self._h, _ptr(perm), _ptr(state), self._stream())
+        self._check(min(rc, 0), "mpcrl_debug_get_order")
+        return (perm if rc == 1 else None), state
+
     # ------------------------------------------------------------------ the hot path
     def _pack_order(self, x0: torch.Tensor) -> None:
         """Scheduling hint: instances that share a wavefront run in lock-step for the maximum of their iteration counts, so

@@ -456,6 +456,15 @@ int mpcrl_auto_order(mpcrl_handle h, const double *x0, void *stream) {
     return 0;
 }
 
+int mpcrl_debug_get_order(mpcrl_handle h, int32_t *perm_out, double *state_out, void *stream) {
+    if (!h) return MPCRL_E_ARG;
+    ON_DEVICE(h->device);
+    const hipStream_t st = (hipStream_t)stream;
+    if (perm_out && h->have_perm) HIP_OK(hipMemcpyAsync(perm_out, h->perm, (size_t)h->B * sizeof(int), hipMemcpyDeviceToDevice, st));
+    if (state_out) HIP_OK(hipMemcpyAsync(state_out, h->order_state, 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    return h->have_perm ? 1 : 0;
+}
+
 int mpcrl_set_bounds(mpcrl_handle h, int which, const double *lb, const double *ub) {
     if (!h || !lb || !ub || which < MPCRL_BOUNDS_U0 || which > MPCRL_BOUNDS_TERMINAL) return MPCRL_E_ARG;
     const int nw = h->nx + h->nu;

@@ -40,7 +40,7 @@ ACTIVE = 1e-3      # a bound row counts as active when its multiplier is above t
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# device side and comparison (moved here from tests/test_gpu_chain_modes.py, which imports them back)
+# device side and comparison (moved here from tests/test_gpu_chain_modes.py and tests/test_gpu_small_modes.py, which import them back)
 # ---------------------------------------------------------------------------------------------------------------------------------
 def raw_solve(mpc, x0, u0=None, flags=None):
     """mpcrl_solve through ctypes with every output buffer poisoned (NaN / -1) before the call, as
@@ -118,6 +118,26 @@ def bit_equal(ra, rb, rows=None):
             if rows is not None:
                 a, b = a[rows], b[rows]
             assert torch.equal(a, b), f
+
+
+def snapshot(mpc, r):
+    """Everything a call returned and left in the handle."""
+    return r, mpc.get_iterate(), mpc.get_lagrangian()
+
+
+def same_bits(a, b, rows=None, reverse=False, lagrangian=True):
+    """Two snapshots bit for bit (b in reversed batch order if reverse), on the given instances."""
+    from mpc4rl_amd.batch import SolveResult
+    (ra, ia, la), (rb, ib, lb) = a, b
+    if reverse:
+        rb = SolveResult(*[None if t is None else t.flip(0) for t in (rb.u0, rb.V, rb.status, rb.iters, rb.dV_dp, rb.dpi_dp)])
+        ib, lb = [t.flip(0) for t in ib], lb.flip(0)
+    bit_equal(ra, rb, rows)
+    sel = slice(None) if rows is None else rows
+    for name, t1, t2 in zip(("x", "u", "pi", "bnd", "res"), ia, ib):
+        assert torch.equal(t1[sel], t2[sel]), name
+    if lagrangian:
+        assert torch.equal(la[sel], lb[sel]), "lagrangian"
 
 
 def uses_lq_kernel(model, N):

@@ -435,8 +435,13 @@ def test_auto_order_does_not_change_results():
     x0[:, 2] = rng.uniform(0.9 * np.pi, 1.1 * np.pi, B)
     x0[:, 0] = rng.uniform(-0.01, 0.01, B)
     mpc = MPCBatch(ocp, B)
+    mpc.set_launch_mode(-1)      # the plain launch: the one that reads the order (the time-sliced one clears it)
     xt = torch.as_tensor(x0, device="cuda")
     r1 = mpc.solve(xt, sens_v=True, cold=True, reorder=True)
+    perm, _ = mpc.get_order()      # what that solve read: a permutation, and not the identity
+    assert perm is not None
+    perm = perm.cpu().numpy()
+    assert np.array_equal(np.sort(perm), np.arange(B)) and not np.array_equal(perm, np.arange(B))
     mpc.lib.mpcrl_set_order(mpc._h, None, None)
     r2 = mpc.solve(xt, sens_v=True, cold=True, reorder=False)
     assert torch.equal(r1.u0, r2.u0) and torch.equal(r1.V, r2.V) and torch.equal(r1.dV_dp, r2.dV_dp)

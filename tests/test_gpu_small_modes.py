@@ -29,7 +29,7 @@ import torch
 
 import launch_plan_cases as P
 import small_mode_cases as C
-from small_mode_cases import RTOL, bit_equal, compare, outputs, raw_solve, same_statuses
+from small_mode_cases import RTOL, bit_equal, compare, outputs, raw_solve, same_bits, same_statuses, snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -53,26 +53,6 @@ def handle(c, mode, ocp=None):
 def sens_flags(cold):
     from mpc4rl_amd import _lib
     return _lib.SENS_V | _lib.SENS_PI | (_lib.COLD if cold else 0)
-
-
-def snapshot(mpc, r):
-    """Everything a call returned and left in the handle."""
-    return r, mpc.get_iterate(), mpc.get_lagrangian()
-
-
-def same_bits(a, b, rows=None, reverse=False, lagrangian=True):
-    """Two snapshots bit for bit (b in reversed batch order if reverse), on the given instances."""
-    from mpc4rl_amd.batch import SolveResult
-    (ra, ia, la), (rb, ib, lb) = a, b
-    if reverse:
-        rb = SolveResult(*[None if t is None else t.flip(0) for t in (rb.u0, rb.V, rb.status, rb.iters, rb.dV_dp, rb.dpi_dp)])
-        ib, lb = [t.flip(0) for t in ib], lb.flip(0)
-    bit_equal(ra, rb, rows)
-    sel = slice(None) if rows is None else rows
-    for name, t1, t2 in zip(("x", "u", "pi", "bnd", "res"), ia, ib):
-        assert torch.equal(t1[sel], t2[sel]), name
-    if lagrangian:
-        assert torch.equal(la[sel], lb[sel]), "lagrangian"
 
 
 def tag(c, mode, what):
