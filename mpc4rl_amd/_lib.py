@@ -1,19 +1,102 @@
-"""ctypes binding of libmpcrl_hip.so (include/mpcrl.h).  Fails loudly when the library is missing."""
+"""ctypes binding of libmpcrl_hip.so, read from include/mpcrl.h, and the one path the package calls the library through
+(``call``, ``workspace``).  Fails loudly when the library is missing.
+
+The .hip units include the same header, so the compiler holds the implementation to it; the prototypes, constants and error codes here
+are parsed from it, so the binding cannot disagree with either.  ``ProblemSpec`` alone is written by hand (its fields take typed
+pointers) and is compared with the header's struct when the module is imported.
+
+The header is read and parsed when this module is imported, not at ``load()``: the constants below are module attributes that other
+modules and tests read without loading the library.  That needs the standard library only (torch and the library come with ``load()``),
+and it means ``import mpc4rl_amd`` needs include/mpcrl.h beside the package; without it the import fails with a message saying so."""
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
+from typing import Dict, List, NamedTuple, Tuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPCRL_LIB_PATH") or os.path.join(_HERE, "libmpcrl_hip.so")   # the override is for instrumented builds (profiles/microbench)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mpcrl.h")
 
-ABI_VERSION = 132        # MPCRL_ABI_VERSION of include/mpcrl.h this binding was written against
-SENS_V, SENS_PI, RTI, COLD = 1, 2, 4, 8
-COLD_DUAL, NO_BND_STORE, EXACT_QP = 16, 32, 64        # (EXACT_QP: test-only, include/mpcrl.h)
-MODEL_CARTPOLE, MODEL_LINEAR, MODEL_CHAIN = 0, 1, 2
-COST_NLS, COST_EXTERNAL = 0, 1
-NO_BOUND = 1e30
-BOUNDS_U0, BOUNDS_STAGE, BOUNDS_TERMINAL = 0, 1, 2
+# ---------------------------------------------------------------------- the header, parsed (standard library only)
+# parameter kinds: "int", "int64", "double", "handle"; pointers "double*", "float*", "int32*", "int64*", "uint8*", "void*", "spec*", "handle*"
+_SCALAR = {"int": "int", "int64_t": "int64", "double": "double", "mpcrl_handle": "handle"}
+_POINTEE = {"double": "double*", "float": "float*", "int32_t": "int32*", "int64_t": "int64*", "uint8_t": "uint8*", "void": "void*",
+            "MpcrlProblemSpec": "spec*", "mpcrl_handle": "handle*"}
+_RETURN = {"int": "int", "int64_t": "int64"}
+
+
+class Header(NamedTuple):
+    functions: Dict[str, Tuple[str, List[Tuple[str, str]]]]    # export -> (return kind, [(parameter name, kind)]), in header order
+    constants: Dict[str, float]                                 # #defines and enumerators, without the MPCRL_ prefix
+    spec_fields: List[Tuple[str, str]]                          # MpcrlProblemSpec: (field name, "int32" | "double" | "int32*" | "double*")
+
+
+def _parameter(decl: str, where: str) -> Tuple[str, str]:
+    m = re.fullmatch(r"(?:const\s+)?(\w+)(?:\s+|\s*(\*)\s*)(\w+)\s*(\[\s*\d*\s*\])?", decl.strip())
+    if not m or (m.group(2) and m.group(4)):
+        raise ValueError(f"{where}: cannot read the parameter {decl.strip()!r}")
+    base, star, name, array = m.groups()
+    kinds = _POINTEE if star or array else _SCALAR      # (a parameter declared as an array is a pointer)
+    if base not in kinds:
+        raise ValueError(f"{where}: parameter {name!r} has a type this binding does not know: {decl.strip()!r}")
+    return name, kinds[base]
+
+
+def parse_header(text: str) -> Header:
+    """Every ``mpcrl_*`` prototype, ``MPCRL_*`` #define with a value and enumerator, and the fields of MpcrlProblemSpec.  Raises
+    ValueError on a prototype, parameter or enumerator it cannot classify: nothing defaults to a pointer."""
+    text = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", text, flags=re.S))
+    functions = {}
+    for ret, name, params in re.findall(r"\b(\w+)\s+(mpcrl_\w+)\s*\(([^()]*)\)\s*;", text):
+        if ret not in _RETURN:
+            raise ValueError(f"{name}: return type {ret!r} is neither int nor int64_t")
+        params = [] if params.strip() == "void" else [_parameter(p, name) for p in params.split(",")]
+        functions[name] = (_RETURN[ret], params)
+    stray = set(re.findall(r"\b(mpcrl_\w+)\s*\(", text)) - set(functions)
+    if stray:
+        raise ValueError(f"cannot read the prototype of {', '.join(sorted(stray))}")
+    constants = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+MPCRL_(\w+)[ \t]+(\S+)[ \t]*$", text, flags=re.M):
+        constants[name] = float(value) if re.search(r"[.eE]", value) else int(value, 0)
+    for body in re.findall(r"\benum\s*\{([^}]*)\}", text):
+        for item in filter(None, (s.strip() for s in body.split(","))):
+            m = re.fullmatch(r"MPCRL_(\w+)\s*=\s*(-?\d+)", item)
+            if not m:
+                raise ValueError(f"cannot read the enumerator {item!r}")
+            constants[m.group(1)] = int(m.group(2))
+    spec_fields = []
+    m = re.search(r"typedef\s+struct\s*\{([^}]*)\}\s*MpcrlProblemSpec\s*;", text)
+    for decl in filter(None, (s.strip() for s in m.group(1).split(";"))) if m else ():
+        f = re.fullmatch(r"(?:const\s+)?(int32_t|double)\b(.*)", decl, flags=re.S)
+        names = [re.fullmatch(r"\s*(\*?)\s*(\w+)\s*", d) for d in f.group(2).split(",")] if f else [None]
+        if not all(names):
+            raise ValueError(f"MpcrlProblemSpec: cannot read the field {decl!r}")
+        spec_fields += [(n.group(2), f.group(1).replace("_t", "") + n.group(1)) for n in names]
+    return Header(functions, constants, spec_fields)
+
+
+if not os.path.exists(HEADER_PATH):
+    raise ImportError(f"mpc4rl_amd: {HEADER_PATH} not found. The binding is read from the header: keep include/ beside the package "
+                      "(the repository's layout).")
+with open(HEADER_PATH) as _f:
+    HEADER = parse_header(_f.read())
+EXPORTS = list(HEADER.functions)
+
+
+def _constants(names: str):
+    return tuple(HEADER.constants[n] for n in names.split())      # (KeyError: the header no longer has the name)
+
+
+# the header's MPCRL_* #defines and enumerators under their Python names (the prefix dropped)
+ABI_VERSION, NO_BOUND = _constants("ABI_VERSION NO_BOUND")
+SENS_V, SENS_PI, RTI, COLD, COLD_DUAL, NO_BND_STORE, EXACT_QP = _constants("SENS_V SENS_PI RTI COLD COLD_DUAL NO_BND_STORE EXACT_QP")   # (EXACT_QP: test-only)
+MODEL_CARTPOLE, MODEL_LINEAR, MODEL_CHAIN = _constants("MODEL_CARTPOLE MODEL_LINEAR MODEL_CHAIN")
+COST_NLS, COST_EXTERNAL = _constants("COST_NLS COST_EXTERNAL")
+BOUNDS_U0, BOUNDS_STAGE, BOUNDS_TERMINAL = _constants("BOUNDS_U0 BOUNDS_STAGE BOUNDS_TERMINAL")
+E_ARG, E_MODEL, E_HIP, E_NOMEM = _constants("E_ARG E_MODEL E_HIP E_NOMEM")
+_ERRORS = {v: "MPCRL_" + k for k, v in HEADER.constants.items() if k.startswith("E_")}
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
@@ -30,124 +113,92 @@ class ProblemSpec(C.Structure):
     ]
 
 
-EXPORTS = ["mpcrl_create", "mpcrl_destroy", "mpcrl_set_theta", "mpcrl_set_gamma", "mpcrl_set_options", "mpcrl_set_exit_rule", "mpcrl_set_order", "mpcrl_set_bounds", "mpcrl_set_cold_mask", "mpcrl_reset",
-           "mpcrl_solve", "mpcrl_get_iterate", "mpcrl_set_iterate", "mpcrl_get_iterate_rows", "mpcrl_set_iterate_rows", "mpcrl_get_lagrangian", "mpcrl_weighted_grad_sum", "mpcrl_env_cartpole_step", "mpcrl_env_cartpole_reset", "mpcrl_env_linear_step", "mpcrl_policy_action", "mpcrl_critic_workspace_bytes", "mpcrl_critic_td_grad", "mpcrl_critic_dq_da", "mpcrl_replay_sample", "mpcrl_dpg_workspace_bytes", "mpcrl_dpg_grad", "mpcrl_td3_cartpole_collect", "mpcrl_td3_policy_post", "mpcrl_qlearning_cartpole_collect", "mpcrl_qlearning_td_workspace_bytes", "mpcrl_qlearning_td_grad", "mpcrl_qlearning_apply", "mpcrl_auto_order", "mpcrl_query_time_sliced", "mpcrl_set_launch_mode", "mpcrl_get_launch_times", "mpcrl_workspace_bytes", "mpcrl_version",
-           "mpcrl_ppo_cartpole_collect", "mpcrl_ppo_gae", "mpcrl_ppo_surrogate_workspace_bytes", "mpcrl_ppo_surrogate_grad", "mpcrl_ppo_log_std_apply",
-           "mpcrl_value_forward", "mpcrl_value_workspace_bytes", "mpcrl_value_mse_grad",
-           "mpcrl_qlearning_linear_collect", "mpcrl_ppo_linear_collect",
-           "mpcrl_env_chain_step", "mpcrl_qlearning_chain_collect",
-           "mpcrl_ppo_chain_collect", "mpcrl_ppo_surrogate_workspace_bytes_nu", "mpcrl_ppo_surrogate_grad_nu", "mpcrl_ppo_log_std_apply_nu",
-           "mpcrl_qlearning_gn_workspace_bytes", "mpcrl_qlearning_td_gn", "mpcrl_qlearning_gn_apply", "mpcrl_qlearning_gn_apply_box",
-           "mpcrl_cdpg_record", "mpcrl_cdpg_workspace_bytes", "mpcrl_cdpg_terms", "mpcrl_cdpg_apply",
-           "mpcrl_debug_seg_reduce", "mpcrl_query_box_rows", "mpcrl_debug_model_jets", "mpcrl_debug_launch_plan", "mpcrl_debug_get_order"]
+_FIELD = {"int32": C.c_int32, "double": C.c_double, "int32*": _ip, "double*": _dp}
+if ProblemSpec._fields_ != [(n, _FIELD[k]) for n, k in HEADER.spec_fields]:
+    raise ImportError(f"mpc4rl_amd: ProblemSpec no longer matches MpcrlProblemSpec of {HEADER_PATH}")
 
+_CTYPE = {"int": C.c_int, "int64": C.c_int64, "double": C.c_double}      # a handle and every pointer: c_void_p
 _lib = None
+torch = None    # imported by load(): reading the header needs neither torch nor HIP
+_plans = {}     # export -> (function, ((parameter, dtypes) ...) without the stream, takes a stream): what `call` needs, prepared by load()
+
+
+def _ptr(t):
+    """The device address of a tensor for a direct call of the library (tests, profiles/microbench); the package itself uses ``call``."""
+    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def load():
     """Returns the loaded library; raises RuntimeError (never falls back) when it is absent."""
-    global _lib
+    global _lib, torch
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
         raise RuntimeError(
             f"mpc4rl_amd: {LIB_PATH} not found. Build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
+    import torch
     lib = C.CDLL(LIB_PATH)
     lib.mpcrl_version.restype = C.c_int
     if lib.mpcrl_version() != ABI_VERSION and not os.environ.get("MPCRL_SKIP_ABI_CHECK"):   # (the override: A/B runs against older builds) extern "C" links whatever the signatures are: refuse a library built from another header
         raise RuntimeError(f"mpc4rl_amd: {LIB_PATH} reports ABI version {lib.mpcrl_version()}, this binding expects {ABI_VERSION}; rebuild it "
                            "(`python -c 'import __graft_entry__ as g; g.build()'`).")
-    vp = C.c_void_p
-    lib.mpcrl_create.argtypes = [C.POINTER(ProblemSpec), C.c_int, C.c_int, C.POINTER(vp)]
-    lib.mpcrl_destroy.argtypes = [vp]
-    lib.mpcrl_set_theta.argtypes = [vp, vp, C.c_int, C.c_int, vp]
-    lib.mpcrl_set_gamma.argtypes = [vp, C.c_double]
-    lib.mpcrl_set_options.argtypes = [vp, C.c_double, C.c_int]
-    lib.mpcrl_set_exit_rule.argtypes = [vp, C.c_int, C.c_double]
-    lib.mpcrl_set_order.argtypes = [vp, vp, vp]
-    lib.mpcrl_set_bounds.argtypes = [vp, C.c_int, _dp, _dp]
-    lib.mpcrl_set_cold_mask.argtypes = [vp, vp, vp]
-    lib.mpcrl_reset.argtypes = [vp, vp, vp]
-    lib.mpcrl_solve.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp]
-    lib.mpcrl_get_iterate.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    lib.mpcrl_set_iterate.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.mpcrl_get_iterate_rows.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    lib.mpcrl_set_iterate_rows.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    lib.mpcrl_get_lagrangian.argtypes = [vp, vp, vp]
-    lib.mpcrl_auto_order.argtypes = [vp, vp, vp]
-    lib.mpcrl_query_time_sliced.argtypes = [vp, C.c_int, vp]
-    lib.mpcrl_query_box_rows.argtypes = [vp]
-    lib.mpcrl_set_launch_mode.argtypes = [vp, C.c_int]
-    lib.mpcrl_get_launch_times.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    lib.mpcrl_weighted_grad_sum.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp]
-    lib.mpcrl_env_cartpole_step.argtypes = [_dp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
-    lib.mpcrl_env_cartpole_reset.argtypes = [C.c_int, vp, vp, vp, vp, vp, C.c_int, vp]
-    lib.mpcrl_env_linear_step.argtypes = [_dp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp]
-    lib.mpcrl_policy_action.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, vp, vp, vp]
-    lib.mpcrl_critic_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-    lib.mpcrl_critic_workspace_bytes.restype = C.c_int64
-    lib.mpcrl_critic_td_grad.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, vp]
-    lib.mpcrl_critic_dq_da.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
-    lib.mpcrl_replay_sample.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.mpcrl_dpg_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.mpcrl_dpg_workspace_bytes.restype = C.c_int64
-    lib.mpcrl_dpg_grad.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]
-    lib.mpcrl_td3_cartpole_collect.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, C.c_double, vp, vp, vp, C.c_int,
-                                               C.c_double, vp, vp, vp, vp, vp, vp]
-    lib.mpcrl_td3_policy_post.argtypes = [vp, C.c_int, C.c_double, vp, C.c_double, vp, vp, vp, vp, vp, C.c_int, vp]
-    lib.mpcrl_qlearning_cartpole_collect.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp,
-                                                     vp, vp, vp, vp, vp]
-    lib.mpcrl_qlearning_td_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.mpcrl_qlearning_td_workspace_bytes.restype = C.c_int64
-    lib.mpcrl_qlearning_td_grad.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp, vp]
-    lib.mpcrl_qlearning_apply.argtypes = [vp, C.c_int, vp, vp, vp, vp]
-    lib.mpcrl_ppo_cartpole_collect.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double,
-                                               vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.mpcrl_ppo_gae.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, vp, vp, vp]
-    lib.mpcrl_ppo_surrogate_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.mpcrl_ppo_surrogate_workspace_bytes.restype = C.c_int64
-    lib.mpcrl_ppo_surrogate_grad.argtypes = [vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_double, C.c_double, C.c_double,
-                                             C.c_double, C.c_double, C.c_int, vp, vp, vp]
-    lib.mpcrl_ppo_log_std_apply.argtypes = [vp, C.c_int, vp, vp]
-    lib.mpcrl_value_forward.argtypes = [vp, C.c_int64, C.c_int, vp, vp, vp]
-    lib.mpcrl_value_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.mpcrl_value_workspace_bytes.restype = C.c_int64
-    lib.mpcrl_value_mse_grad.argtypes = [vp, vp, vp, C.c_int, C.c_int64, C.c_int, vp, C.c_double, C.c_double, vp, vp, vp]
-    lib.mpcrl_qlearning_linear_collect.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp,
-                                                   vp, vp]
-    lib.mpcrl_ppo_linear_collect.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double,
-                                             C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.mpcrl_env_chain_step.argtypes = [C.c_int, C.c_double, C.c_int, vp, C.c_int64, vp, C.c_int, vp, vp, vp, C.c_double, vp, C.c_int, vp, vp]
-    lib.mpcrl_qlearning_chain_collect.argtypes = [C.c_int, C.c_double, C.c_int, vp, C.c_int64, vp, C.c_double, C.c_int, C.c_int, vp, vp, vp, vp, vp,
-                                                  _dp, _dp, C.c_double, vp, vp, vp, vp, vp, vp, vp]
-    lib.mpcrl_ppo_chain_collect.argtypes = [C.c_int, C.c_double, C.c_int, vp, C.c_int64, vp, C.c_double, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp,
-                                            vp, vp, vp, _dp, _dp, C.c_double, C.c_int64, vp, C.c_double, vp] + [vp] * 12
-    lib.mpcrl_ppo_surrogate_workspace_bytes_nu.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.mpcrl_ppo_surrogate_workspace_bytes_nu.restype = C.c_int64
-    lib.mpcrl_ppo_surrogate_grad_nu.argtypes = [vp, C.c_int, C.c_int64, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, _dp, _dp, C.c_double,
-                                                C.c_double, C.c_double, C.c_int, vp, vp, vp]
-    lib.mpcrl_ppo_log_std_apply_nu.argtypes = [vp, C.c_int, C.c_int, vp, vp]
-    lib.mpcrl_qlearning_gn_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.mpcrl_qlearning_gn_workspace_bytes.restype = C.c_int64
-    lib.mpcrl_qlearning_td_gn.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_double, vp, C.c_int, vp, vp, vp, vp, vp]
-    lib.mpcrl_qlearning_gn_apply.argtypes = [vp, C.c_int, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, vp]
-    lib.mpcrl_qlearning_gn_apply_box.argtypes = [vp, C.c_int, vp, C.c_int, C.c_double, C.c_double, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp]
-    lib.mpcrl_cdpg_record.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-    lib.mpcrl_cdpg_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.mpcrl_cdpg_workspace_bytes.restype = C.c_int64
-    lib.mpcrl_cdpg_terms.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp]
-    lib.mpcrl_cdpg_apply.argtypes = [vp, C.c_int, vp, C.c_int, C.c_double, C.c_double, C.c_int, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]
-    lib.mpcrl_debug_seg_reduce.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
-    lib.mpcrl_debug_model_jets.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp, vp, vp]
-    lib.mpcrl_debug_launch_plan.argtypes = [C.c_int] * 9 + [_ip]
-    lib.mpcrl_debug_get_order.argtypes = [vp, vp, vp, vp]
-    lib.mpcrl_workspace_bytes.argtypes = [vp]
-    lib.mpcrl_workspace_bytes.restype = C.c_int64
-    for name in EXPORTS:
-        if name not in ("mpcrl_workspace_bytes", "mpcrl_critic_workspace_bytes", "mpcrl_dpg_workspace_bytes", "mpcrl_qlearning_td_workspace_bytes",
-                        "mpcrl_ppo_surrogate_workspace_bytes", "mpcrl_value_workspace_bytes", "mpcrl_ppo_surrogate_workspace_bytes_nu",
-                        "mpcrl_qlearning_gn_workspace_bytes", "mpcrl_cdpg_workspace_bytes"):
-            getattr(lib, name).restype = C.c_int
+    # what a tensor handed to a pointer parameter may hold: None = no tensor there, () = any (void *)
+    dtypes = {"double*": (torch.float64,), "float*": (torch.float32,), "int32*": (torch.int32,), "int64*": (torch.int64,),
+              "uint8*": (torch.uint8, torch.bool), "void*": ()}
+    for name, (ret, params) in HEADER.functions.items():
+        fn = getattr(lib, name)
+        fn.restype = _CTYPE[ret]
+        fn.argtypes = [_CTYPE.get(kind, C.c_void_p) for _, kind in params]
+        stream = bool(params) and params[-1] == ("stream", "void*")
+        _plans[name] = (fn, tuple((p, dtypes.get(kind)) for p, kind in (params[:-1] if stream else params)), stream)
     _lib = lib
     return lib
+
+
+def call(name: str, *args, device=None) -> int:
+    """Calls the export ``name`` with ``args`` checked against its prototype in the header, and returns what it returns (>= 0); a
+    negative return raises RuntimeError.  A trailing ``void *stream`` is not given: ``call`` passes the current stream of ``device``
+    (required then; inside a capture that is the capture stream) and runs under ``torch.cuda.device(device)``.  A tensor stands for its
+    device address and must be handed to a pointer parameter of its dtype and live on ``device`` (strides are the caller's contract);
+    None is NULL; anything else (ints, floats, ctypes arrays, byref) goes to ctypes as it is.  A refused argument raises TypeError or
+    ValueError before anything is called."""
+    if _lib is None:
+        load()
+    fn, params, stream = _plans[name]
+    if len(args) != len(params):
+        raise TypeError(f"{name} takes {len(params)} arguments ({', '.join(p for p, _ in params)}{' and the stream' if stream else ''}), "
+                        f"{len(args)} were given")
+    if stream and device is None:
+        raise TypeError(f"{name} launches on a stream: `device` is required")
+    index = None
+    if device is not None:
+        index = device.index if isinstance(device, torch.device) else torch.device(device).index
+        if index is None:       # "cuda": the current device
+            index = torch.cuda.current_device()
+    argv = []
+    for a, (pname, dtypes) in zip(args, params):
+        if isinstance(a, torch.Tensor):
+            if dtypes is None:
+                raise TypeError(f"{name}: parameter {pname} takes no array, a tensor was given")
+            if dtypes and a.dtype not in dtypes:
+                raise TypeError(f"{name}: parameter {pname} points to {dtypes[0]}, the tensor given holds {a.dtype}")
+            if not a.is_cuda or a.device.index != index:
+                raise ValueError(f"{name}: the tensor given for {pname} lives on {a.device}, the call is for "
+                                 f"{'no device' if index is None else f'cuda:{index}'}")
+            a = a.data_ptr()
+        argv.append(a)
+    if stream:
+        with torch.cuda.device(index):
+            rc = fn(*argv, torch.cuda.current_stream(index).cuda_stream)
+    else:
+        rc = fn(*argv)
+    if rc < 0:
+        raise RuntimeError(f"{name} failed with {rc}" + (f" ({_ERRORS[rc]})" if rc in _ERRORS else ""))
+    return rc
+
+
+def workspace(name: str, *dims, device):
+    """A zeroed uint8 tensor on ``device`` of the size the export ``name`` (a ``*_workspace_bytes``) returns for ``dims``."""
+    nbytes = call(name, *dims)      # first: the call is what loads the library (and torch) on a first use
+    return torch.zeros(nbytes, dtype=torch.uint8, device=device)

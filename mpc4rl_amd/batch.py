@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import _ptr      # noqa: F401  (tests and profiles/microbench call the library directly with it)
 from .problems import OcpDescription
 
 
@@ -26,10 +27,6 @@ class SolveResult:
     iters: torch.Tensor              # [B, 2] int32  SQP iterations, interior-point iterations
     dV_dp: Optional[torch.Tensor]    # [B, n_p]
     dpi_dp: Optional[torch.Tensor]   # [B, nu, n_p]
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class MPCBatch:
@@ -48,10 +45,8 @@ class MPCBatch:
         self.nx, self.nu, self.N, self.n_p = ocp.nx, ocp.nu, ocp.N, ocp.n_p
         spec, keep = ocp.c_spec()
         h = C.c_void_p()
-        rc = self.lib.mpcrl_create(C.byref(spec), self.B, self.device.index, C.byref(h))
+        _lib.call("mpcrl_create", C.byref(spec), self.B, self.device.index, C.byref(h))
         del keep
-        if rc != 0:
-            raise RuntimeError(f"mpcrl_create failed with {rc}")
         self._h = h
         self._theta = None
         self.has_iterate = False       # a stored iterate exists (after a solve / set_iterate; cleared by reset)
@@ -62,9 +57,13 @@ class MPCBatch:
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
-            self.lib.mpcrl_destroy(h)
+            self.lib.mpcrl_destroy(h)      # (not through _lib.call: at interpreter exit the module may be gone before the handle)
 
     # ------------------------------------------------------------------ helpers
+    def _call(self, name: str, *args) -> int:
+        return _lib.call(name, self._h, *args, device=self.device)
+
+    # _stream and _check: for direct calls of self.lib (tests, profiles/microbench); the package's own calls go through _call
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
@@ -84,8 +83,7 @@ class MPCBatch:
         if t.shape[-1] != self.n_p or (per and t.shape[0] != self.B):
             raise ValueError(f"theta must be [{self.n_p}] or [{self.B}, {self.n_p}]")
         self._theta = t
-        with torch.cuda.device(self.device):
-            self._check(self.lib.mpcrl_set_theta(self._h, _ptr(t), self.n_p, per, self._stream()), "mpcrl_set_theta")
+        self._call("mpcrl_set_theta", t, self.n_p, per)
 
     def get_theta(self) -> torch.Tensor:
         return self._theta
@@ -93,28 +91,27 @@ class MPCBatch:
     def set_discount_factor(self, gamma: float) -> None:
         """MPC.set_discount_factor (mpc.py:259-285)."""
         self.gamma = float(gamma)
-        self._check(self.lib.mpcrl_set_gamma(self._h, float(gamma)), "mpcrl_set_gamma")
+        self._call("mpcrl_set_gamma", float(gamma))
 
     def set_options(self, tol: float = -1.0, max_iter: int = -1) -> None:
-        self._check(self.lib.mpcrl_set_options(self._h, float(tol), int(max_iter)), "mpcrl_set_options")
+        self._call("mpcrl_set_options", float(tol), int(max_iter))
 
     def set_exit_rule(self, window: int = 10, factor: float = 0.1) -> None:
         """Opt-in divergence exit (include/mpcrl.h mpcrl_set_exit_rule): every ``window`` SQP iterations the best NLP residual of an
         instance must have dropped below ``factor`` x its value at the previous check, else it ends with status 2.  window = 0: off
         (the reference's behaviour: full-step SQP to max_iter)."""
-        self._check(self.lib.mpcrl_set_exit_rule(self._h, int(window), float(factor)), "mpcrl_set_exit_rule")
+        self._call("mpcrl_set_exit_rule", int(window), float(factor))
 
     def set_launch_mode(self, mode: int = 0) -> None:
         """0 = the library times the time-sliced and the plain launch of the solve kernel against each other on this handle's own
         solves and uses the faster (default), 1 = time-sliced whenever legal, -1 = never (include/mpcrl.h mpcrl_set_launch_mode)."""
-        self._check(self.lib.mpcrl_set_launch_mode(self._h, int(mode)), "mpcrl_set_launch_mode")
+        self._call("mpcrl_set_launch_mode", int(mode))
 
     def launch_times(self, warm: bool = False):
         """(time-sliced ms, plain ms, preferred shape) of the launch tuner's last probes on cold (default) or warm calls; -1 = not
         measured yet."""
         a, b = C.c_double(-1.0), C.c_double(-1.0)
-        rc = self.lib.mpcrl_get_launch_times(self._h, int(warm), C.byref(a), C.byref(b))
-        self._check(min(rc, 0), "mpcrl_get_launch_times")
+        rc = self._call("mpcrl_get_launch_times", int(warm), C.byref(a), C.byref(b))
         return a.value, b.value, ("plain" if rc == 1 else "time-sliced")
 
     def set_bounds(self, which: int, lb, ub) -> None:
@@ -125,32 +122,27 @@ class MPCBatch:
         n = {_lib.BOUNDS_U0: self.nu, _lib.BOUNDS_STAGE: self.nu + self.nx, _lib.BOUNDS_TERMINAL: self.nx}[which]
         if lb.shape[0] != n or ub.shape[0] != n:
             raise ValueError(f"bounds of kind {which} have {n} entries")
-        dp = C.POINTER(C.c_double)
-        self._check(self.lib.mpcrl_set_bounds(self._h, int(which), lb.ctypes.data_as(dp), ub.ctypes.data_as(dp)), "mpcrl_set_bounds")
+        self._call("mpcrl_set_bounds", int(which), lb.ctypes.data, ub.ctypes.data)     # (host arrays of float64)
 
     def reset(self, x0=None) -> None:
         """MPC.reset (mpc.py:204-210): the next solve starts from x_k = x0, u = 0, multipliers 0.  With x0 ([B, nx]) the stored
         iterate is set to that cold iterate as well (what get_iterate returns until the next solve)."""
         x0t = None if x0 is None else self._dev(x0, (self.B, self.nx))
-        with torch.cuda.device(self.device):
-            self._check(self.lib.mpcrl_reset(self._h, _ptr(x0t), self._stream()), "mpcrl_reset")
+        self._call("mpcrl_reset", x0t)
         self.has_iterate = self.duals_valid = False
 
     def set_order(self, perm) -> None:
         """mpcrl_set_order: perm [B], a permutation of 0..B-1 (validity is the caller's contract) — slot i of the next launches works
         on instance perm[i]; None = identity.  A scheduling hint: no effect on results."""
         p = None if perm is None else torch.as_tensor(perm, device=self.device).to(torch.int32).reshape(self.B).contiguous()
-        with torch.cuda.device(self.device):
-            self._check(self.lib.mpcrl_set_order(self._h, _ptr(p), self._stream()), "mpcrl_set_order")
+        self._call("mpcrl_set_order", p)
 
     def get_order(self):
         """(perm [B] int32 or None = identity, state [3] = {spread, minimum, coordinate} of the last from-scratch auto order): what the
         next solve would read (mpcrl_debug_get_order, a test probe)."""
         perm = torch.empty((self.B,), dtype=torch.int32, device=self.device)
         state = torch.empty((3,), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.mpcrl_debug_get_order(self._h, _ptr(perm), _ptr(state), self._stream())
-        self._check(min(rc, 0), "mpcrl_debug_get_order")
+        rc = self._call("mpcrl_debug_get_order", perm, state)
         return (perm if rc == 1 else None), state
 
     # ------------------------------------------------------------------ the hot path
@@ -160,14 +152,14 @@ class MPCBatch:
         if self.B < 128:
             return
         if 64 // (self.N + 1) < 2:   # one instance per wavefront (the library also skips the chain at any horizon): no lock step to pack for
-            self._check(self.lib.mpcrl_set_order(self._h, None, self._stream()), "mpcrl_set_order")
+            self._call("mpcrl_set_order", None)
             return
         if self.B <= 8192:   # one small kernel inside the library (csrc/order_kernel.hpp)
-            self._check(self.lib.mpcrl_auto_order(self._h, _ptr(x0), self._stream()), "mpcrl_auto_order")
+            self._call("mpcrl_auto_order", x0)
             return
         dim = torch.argmax(x0.max(0).values - x0.min(0).values).reshape(1)     # stays on the device: no host sync
         perm = torch.argsort(torch.index_select(x0, 1, dim).reshape(-1)).to(torch.int32)
-        self._check(self.lib.mpcrl_set_order(self._h, _ptr(perm), self._stream()), "mpcrl_set_order")
+        self._call("mpcrl_set_order", perm)
 
     def solve(self, x0, u0=None, sens_v: bool = False, sens_pi: bool = False, rti: bool = False, cold: bool = False,
               reorder: bool = True, cold_mask: Optional[torch.Tensor] = None, store_bounds: bool = True,
@@ -179,18 +171,16 @@ class MPCBatch:
         x0 = self._dev(x0, (self.B, self.nx))
         if cold_mask is not None:
             cm = cold_mask.to(device=self.device, dtype=torch.int32).reshape(self.B).contiguous()
-            with torch.cuda.device(self.device):
-                self._check(self.lib.mpcrl_set_cold_mask(self._h, _ptr(cm), self._stream()), "mpcrl_set_cold_mask")
+            self._call("mpcrl_set_cold_mask", cm)
         u0f = None if u0 is None else self._dev(u0, (self.B, self.nu))
         flags = (_lib.SENS_V if sens_v else 0) | (_lib.SENS_PI if sens_pi else 0) | (_lib.RTI if rti else 0) | \
             (_lib.COLD if cold else 0) | (0 if store_bounds else _lib.NO_BND_STORE) | (_lib.EXACT_QP if exact_qp else 0)
         if reorder:
-            if self.lib.mpcrl_query_time_sliced(self._h, flags, self._stream()) == 1:
+            if self._call("mpcrl_query_time_sliced", flags) == 1:
                 # the time-sliced launch deals the batch out in quarters: no packing order needed (and none left over from before)
-                self._check(self.lib.mpcrl_set_order(self._h, None, self._stream()), "mpcrl_set_order")
+                self._call("mpcrl_set_order", None)
             else:
-                with torch.cuda.device(self.device):
-                    self._pack_order(x0)
+                self._pack_order(x0)
         kw = dict(dtype=torch.float64, device=self.device)
         u0_out = torch.empty((self.B, self.nu), **kw)
         V = torch.empty((self.B,), **kw)
@@ -198,10 +188,7 @@ class MPCBatch:
         dpi = torch.empty((self.B, self.nu, self.n_p), **kw) if sens_pi else None
         status = torch.empty((self.B,), dtype=torch.int32, device=self.device)
         iters = torch.empty((self.B, 2), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            rc = self.lib.mpcrl_solve(self._h, _ptr(x0), _ptr(u0f), flags, _ptr(u0_out), _ptr(V), _ptr(dV), _ptr(dpi),
-                                      _ptr(status), _ptr(iters), self._stream())
-        self._check(rc, "mpcrl_solve")
+        self._call("mpcrl_solve", x0, u0f, flags, u0_out, V, dV, dpi, status, iters)
         self.has_iterate, self.duals_valid = True, bool(store_bounds)
         return SolveResult(u0_out, V, status, iters, dV, dpi)
 
@@ -219,9 +206,7 @@ class MPCBatch:
         pi = torch.empty((self.B, self.N, self.nx), **kw)
         bnd = torch.empty((self.B, 10, self.N + 1, nw), **kw)
         res = torch.empty((self.B, 4), **kw)
-        with torch.cuda.device(self.device):
-            self._check(self.lib.mpcrl_get_iterate(self._h, _ptr(x), _ptr(u), _ptr(pi), _ptr(bnd), _ptr(res), self._stream()),
-                        "mpcrl_get_iterate")
+        self._call("mpcrl_get_iterate", x, u, pi, bnd, res)
         return x, u, pi, bnd, res
 
     def set_iterate(self, x, u, pi, bnd=None) -> None:
@@ -232,9 +217,7 @@ class MPCBatch:
         u = self._dev(u, (self.B, self.N, self.nu))
         pi = self._dev(pi, (self.B, self.N, self.nx))
         bnd = None if bnd is None else self._dev(bnd, (self.B, 10, self.N + 1, nw))
-        with torch.cuda.device(self.device):
-            self._check(self.lib.mpcrl_set_iterate(self._h, _ptr(x), _ptr(u), _ptr(pi), _ptr(bnd), self._stream()),
-                        "mpcrl_set_iterate")
+        self._call("mpcrl_set_iterate", x, u, pi, bnd)
         self.has_iterate, self.duals_valid = True, bnd is not None
 
     def _row_tables(self, x, u, pi, bnd, index):
@@ -250,22 +233,19 @@ class MPCBatch:
         """Table row index[i] := stored iterate of instance i (mpcrl_get_iterate_rows; the tables are the caller's, any number of rows,
         rows laid out as get_iterate's; None = skip that array)."""
         self._row_tables(x, u, pi, bnd, index)
-        with torch.cuda.device(self.device):
-            self._check(self.lib.mpcrl_get_iterate_rows(self._h, _ptr(x), _ptr(u), _ptr(pi), _ptr(bnd), _ptr(index), self._stream()), "mpcrl_get_iterate_rows")
+        self._call("mpcrl_get_iterate_rows", x, u, pi, bnd, index)
 
     def set_iterate_rows(self, x, u, pi, bnd, index: Optional[torch.Tensor] = None) -> None:
         """Stored iterate of instance i := table row index[i] (mpcrl_set_iterate_rows); bnd = None as in set_iterate."""
         self._row_tables(x, u, pi, bnd, index)
-        with torch.cuda.device(self.device):
-            self._check(self.lib.mpcrl_set_iterate_rows(self._h, _ptr(x), _ptr(u), _ptr(pi), _ptr(bnd), _ptr(index), self._stream()), "mpcrl_set_iterate_rows")
+        self._call("mpcrl_set_iterate_rows", x, u, pi, bnd, index)
         self.has_iterate, self.duals_valid = True, bnd is not None
 
     def get_lagrangian(self) -> torch.Tensor:
         """[B] Lagrangian of the mirror NLP at the iterate of the last solve (nlp.L, nlp.py:1180,1390)."""
         L = torch.empty((self.B,), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            self._check(self.lib.mpcrl_get_lagrangian(self._h, _ptr(L), self._stream()), "mpcrl_get_lagrangian")
+        self._call("mpcrl_get_lagrangian", L)
         return L
 
     def workspace_bytes(self) -> int:
-        return int(self.lib.mpcrl_workspace_bytes(self._h))
+        return self._call("mpcrl_workspace_bytes")

@@ -37,15 +37,8 @@ def allreduce_weighted_grad(grad: torch.Tensor, weight: torch.Tensor, group: Opt
     buf = torch.empty(n_theta + 2, dtype=torch.float64, device=g.device)
     if g.is_cuda and g.stride(1) == 1 and not deterministic:
         # K5 (csrc/reduce_kernel.hpp): one launch instead of a chain of elementwise / reduction kernels
-        import ctypes as C
         from . import _lib
-        w = w.contiguous()
-        # (the library launches on the device that owns `buf`, whatever device is current here)
-        rc = _lib.load().mpcrl_weighted_grad_sum(C.c_void_p(g.data_ptr()), int(g.stride(0)), C.c_void_p(w.data_ptr()), int(g.shape[0]),
-                                                 int(n_theta), C.c_void_p(buf.data_ptr()),
-                                                 C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"mpcrl_weighted_grad_sum failed with {rc}")
+        _lib.call("mpcrl_weighted_grad_sum", g, int(g.stride(0)), w.contiguous(), int(g.shape[0]), int(n_theta), buf, device=g.device)
     else:   # CPU tensors (gloo tests), and the deterministic path: the reduction kernel combines its per-wave partial sums with
         #         floating-point atomics, whose order varies from run to run; a framework reduction of one shape does not
         buf[:n_theta] = (w[:, None] * g).sum(0)

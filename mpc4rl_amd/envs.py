@@ -20,10 +20,13 @@ exactly [0, 0, pi, 0]; the single-env semantics above are the ones reproduced he
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Optional, Tuple
 
 import torch
+
+from . import _lib
 
 
 class BatchedCartPoleSwingUpEnv:
@@ -69,7 +72,6 @@ class BatchedCartPoleSwingUpEnv:
     def _par(self):
         # rebuilt on every call (nine host scalars): an edit of env.force_mag, max_episode_steps, ... after construction reaches the
         # kernel exactly as it reaches the torch formulation below
-        import ctypes
         self._par_c = (ctypes.c_double * 9)(self.gravity, self.masscart, self.masspole, self.length, self.force_mag, self.tau,
                                             self.x_threshold, self.theta_threshold, float(self.max_episode_steps))
         return self._par_c
@@ -80,14 +82,9 @@ class BatchedCartPoleSwingUpEnv:
         u01 = torch.rand(self.num_envs, generator=self.gen, dtype=torch.float64, device=self.device)
         mask = mask.to(self.device)
         if self._native():
-            from . import _lib
-            from .batch import _ptr
             m8 = mask.to(torch.uint8).contiguous()
             obs = torch.empty(self.num_envs, 4, dtype=self.dtype, device=self.device)
-            rc = _lib.load().mpcrl_env_cartpole_reset(self.num_envs, _ptr(self.state), _ptr(self.steps), _ptr(m8), _ptr(u01), _ptr(obs),
-                                                      self._f32(), torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                raise RuntimeError(f"mpcrl_env_cartpole_reset failed with code {rc}")
+            _lib.call("mpcrl_env_cartpole_reset", self.num_envs, self.state, self.steps, m8, u01, obs, self._f32(), device=self.device)
             return obs
         fresh = torch.zeros_like(self.state)
         fresh[:, 2] = (0.9 + 0.2 * u01) * math.pi
@@ -102,17 +99,12 @@ class BatchedCartPoleSwingUpEnv:
         """action: [B, 1] in [-1, 1] (what CartpoleMPC.get_action returns).  Returns obs, reward, terminated, truncated."""
         a = action.to(torch.float64).reshape(self.num_envs)
         if self._native():
-            from . import _lib
-            from .batch import _ptr
             a = a.to(self.device).contiguous()
             obs = torch.empty(self.num_envs, 4, dtype=self.dtype, device=self.device)
             reward = torch.empty(self.num_envs, dtype=torch.float64, device=self.device)
             flags = torch.empty((2, self.num_envs), dtype=torch.uint8, device=self.device)
-            rc = _lib.load().mpcrl_env_cartpole_step(self._par(), self.num_envs, _ptr(self.state), _ptr(self.steps), _ptr(a), _ptr(obs),
-                                                     self._f32(), _ptr(reward), _ptr(flags[0]), _ptr(flags[1]),
-                                                     torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                raise RuntimeError(f"mpcrl_env_cartpole_step failed with code {rc}")
+            _lib.call("mpcrl_env_cartpole_step", self._par(), self.num_envs, self.state, self.steps, a, obs, self._f32(), reward, flags[0],
+                      flags[1], device=self.device)
             fb = flags.view(torch.bool)
             return obs, reward, fb[0], fb[1]
         x, x_dot, th, th_dot = self.state.unbind(1)
@@ -156,9 +148,6 @@ class BatchedLinearSystemEnv:
     def step(self, action: torch.Tensor):
         a = action.to(torch.float64).reshape(self.num_envs, 1)
         if self.device.type == "cuda":   # one launch through the C ABI (csrc/env_kernel.hpp)
-            import ctypes
-            from . import _lib
-            from .batch import _ptr
             # the parameter block is cached against the identity and in-place version of the tensors it was read from (and the noise
             # bounds), so that a later edit of env.A / env.B / env.low / env.high / the noise bounds is honoured like on the torch path
             # without a device-to-host copy per step
@@ -171,11 +160,8 @@ class BatchedLinearSystemEnv:
             a = a.to(self.device).contiguous()
             obs = torch.empty(self.num_envs, 2, dtype=self.dtype, device=self.device)
             cost = torch.empty(self.num_envs, dtype=torch.float64, device=self.device)
-            rc = _lib.load().mpcrl_env_linear_step(self._par_c, self.num_envs, _ptr(self.state), _ptr(a), _ptr(u01), _ptr(obs),
-                                                   1 if self.dtype == torch.float32 else 0, _ptr(cost),
-                                                   torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                raise RuntimeError(f"mpcrl_env_linear_step failed with code {rc}")
+            _lib.call("mpcrl_env_linear_step", self._par_c, self.num_envs, self.state, a, u01, obs, 1 if self.dtype == torch.float32 else 0,
+                      cost, device=self.device)
             done = torch.zeros(self.num_envs, dtype=torch.bool, device=self.device)
             return obs, cost, done, done.clone()
         noise = torch.zeros(self.num_envs, 2, dtype=torch.float64, device=self.device)
@@ -189,7 +175,6 @@ class BatchedLinearSystemEnv:
 
 def _chain_dims(ocp):
     """(n_mass, Ts, rk_steps) of a chain_mass_ocp(...)."""
-    from . import _lib
     if getattr(ocp, "model", None) != _lib.MODEL_CHAIN or ocp.nu != 3 or ocp.nx % 3 != 0 or (ocp.nx // 3) % 2 != 1:
         raise ValueError("the chain-of-masses OCP is needed (chain_mass_ocp())")
     return (ocp.nx // 3 - 1) // 2 + 2, float(ocp.dT), int(ocp.rk_steps)
@@ -251,18 +236,12 @@ class BatchedChainMassEnv:
         wn = torch.randn(E, 3 * self.M, generator=self.gen, dtype=torch.float64, device=self.device) if self.w_std != 0.0 else None
         done = torch.zeros(E, dtype=torch.bool, device=self.device)
         if self.device.type == "cuda":   # one launch through the C ABI (csrc/chain_env_kernel.hpp)
-            from . import _lib
-            from .batch import _ptr
             if not (self.p.is_contiguous() and self.p.dtype == torch.float64 and self.p.device.type == "cuda"):
                 raise ValueError("env.p must stay a contiguous float64 tensor on the environment's device")
             obs = torch.empty(E, self.nx, dtype=self.dtype, device=self.device)
             cost = torch.empty(E, dtype=torch.float64, device=self.device)
-            rc = _lib.load().mpcrl_env_chain_step(self.n_mass, self.Ts, self.rk_steps, _ptr(self.p), 0 if self.p.dim() == 1 else self.n_p,
-                                                  _ptr(self.x_ss), E, _ptr(self.state), _ptr(a), _ptr(wn), self.w_std, _ptr(obs),
-                                                  1 if self.dtype == torch.float32 else 0, _ptr(cost),
-                                                  torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                raise RuntimeError(f"mpcrl_env_chain_step failed with code {rc}")
+            _lib.call("mpcrl_env_chain_step", self.n_mass, self.Ts, self.rk_steps, self.p, 0 if self.p.dim() == 1 else self.n_p, self.x_ss, E,
+                      self.state, a, wn, self.w_std, obs, 1 if self.dtype == torch.float32 else 0, cost, device=self.device)
             return obs, cost, done, done.clone()
         new, cost = chain_env_step_terms((self.n_mass, self.Ts, self.rk_steps), self.p, self.x_ss, self.state, a, wn, self.w_std)
         self.state.copy_(new)

@@ -28,7 +28,7 @@ from typing import Optional, Sequence, Tuple
 
 import torch
 
-from .batch import _ptr
+from . import _lib
 from .qlearning import GN_KMAX, DeviceQLearning, _gn_chol_solve
 from .qlearning_cartpole import CartpoleQLearning
 from .qlearning_chain import ChainQLearning
@@ -193,13 +193,10 @@ class DevicePolicyGradient(DeviceQLearning):
         if K < 1 or K > GN_KMAX:
             raise ValueError(f"{type(self).__name__} learns between 1 and {GN_KMAX} entries of theta; learn_mask marks {K}")
         T, E, NU, dev = self.T, self.E, self.NU, self.device
-        nb = int(self._lib.mpcrl_cdpg_workspace_bytes(T, E, K))
-        if nb < 0:
-            raise RuntimeError(f"mpcrl_cdpg_workspace_bytes failed with {nb}")
         f64 = dict(dtype=torch.float64, device=dev)
         self.K = K
         self.msg = torch.zeros(cdpg_msg_len(K), **f64)
-        self._ws = torch.zeros(nb, dtype=torch.uint8, device=dev)
+        self._ws = _lib.workspace("mpcrl_cdpg_workspace_bytes", T, E, K, device=dev)
         self.Vt = torch.zeros(T, E, **f64)
         self.U0 = torch.zeros(T, E, NU, **f64)
         self.St = torch.zeros(T, E, dtype=torch.int32, device=dev)
@@ -218,36 +215,22 @@ class DevicePolicyGradient(DeviceQLearning):
     def _rollout_step(self):
         self._gn_setup()
         r = self.rollout_mpc.solve(self.obs, cold_mask=self.cold, sens_pi=True)     # the policy and its Jacobian, one launch
-        with torch.cuda.device(self.device):
-            rc = self._lib.mpcrl_cdpg_record(_ptr(r.V), _ptr(r.u0), _ptr(r.dpi_dp), _ptr(r.status), _ptr(self.row), _ptr(self.learn_idx), self.E,
-                                             self.T, self.NU, self.n_p, self.K, _ptr(self.Vt), _ptr(self.U0), _ptr(self.St), _ptr(self.Jt),
-                                             self._stream())
-            if rc != 0:
-                raise RuntimeError(f"mpcrl_cdpg_record failed with {rc}")
-            rc = self._collect(r)
-        if rc != 0:
-            raise RuntimeError(f"{self._COLLECT} failed with {rc}")
+        self._call("mpcrl_cdpg_record", r.V, r.u0, r.dpi_dp, r.status, self.row, self.learn_idx, self.E, self.T, self.NU, self.n_p, self.K,
+                   self.Vt, self.U0, self.St, self.Jt)
+        self._collect(r)
         return r
 
     def _sweep(self):
         """No sweep: the terms of the episode's own roll-out solves, one launch."""
         self._gn_setup()
-        with torch.cuda.device(self.device):
-            rc = self._lib.mpcrl_cdpg_terms(_ptr(self.Vt), _ptr(self.U0), _ptr(self.Jt), _ptr(self.St), _ptr(self.A), _ptr(self.C), _ptr(self.live),
-                                            self.T, self.E, self.NU, self.K, self.gamma, _ptr(self._ws), _ptr(self.td), _ptr(self.valid),
-                                            _ptr(self.msg), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"mpcrl_cdpg_terms failed with {rc}")
+        self._call("mpcrl_cdpg_terms", self.Vt, self.U0, self.Jt, self.St, self.A, self.C, self.live, self.T, self.E, self.NU, self.K,
+                   self.gamma, self._ws, self.td, self.valid, self.msg)
         return None
 
     def _apply(self) -> None:
         lo, hi, scale = (self.theta_lo, self.theta_hi, self.theta_scale) if self.box else (None, None, None)
-        with torch.cuda.device(self.device):
-            rc = self._lib.mpcrl_cdpg_apply(_ptr(self.msg), self.K, _ptr(self.learn_idx), self.n_p, self.lr, self.damping, int(self.natural),
-                                            _ptr(lo), _ptr(hi), _ptr(scale), self.trust_radius, _ptr(self.theta), _ptr(self.step_out),
-                                            _ptr(self.w), _ptr(self.gn_active), _ptr(self.gn_info), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"mpcrl_cdpg_apply failed with {rc}")
+        self._call("mpcrl_cdpg_apply", self.msg, self.K, self.learn_idx, self.n_p, self.lr, self.damping, int(self.natural), lo, hi, scale,
+                   self.trust_radius, self.theta, self.step_out, self.w, self.gn_active, self.gn_info)
         self._set_theta()
 
 

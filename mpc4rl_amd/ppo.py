@@ -46,7 +46,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .batch import MPCBatch, _ptr
+from .batch import MPCBatch
 from .envs import BatchedCartPoleSwingUpEnv, BatchedChainMassEnv, BatchedLinearSystemEnv, _chain_dims
 from .problems import chain_param_layout
 from .qlearning_chain import chain_env_step_terms
@@ -358,7 +358,6 @@ class MPCActorCriticPolicy:
         if self.value_kernels:
             from .td3 import flatten_parameters
             self.value_flat, self.value_grad_flat = flatten_parameters(self.value_net)
-            self._lib = _lib.load()
         if optimizer_kwargs is None:
             optimizer_kwargs = {}
             if optimizer_class == torch.optim.Adam:
@@ -401,10 +400,7 @@ class MPCActorCriticPolicy:
             return self.value_net(obs.to(torch.float32)).to(torch.float64)
         o = obs.to(device=self.device, dtype=torch.float64).reshape(-1, self.obs_dim).contiguous()
         out = torch.empty(o.shape[0], 1, dtype=torch.float64, device=self.device)
-        rc = self._lib.mpcrl_value_forward(_ptr(o), o.shape[0], self.obs_dim, _ptr(self.value_flat), _ptr(out),
-                                           torch.cuda.current_stream(self.device).cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"mpcrl_value_forward failed with {rc}")
+        _lib.call("mpcrl_value_forward", o, o.shape[0], self.obs_dim, self.value_flat, out, device=self.device)
         return out
 
     def _predict(self, observation: torch.Tensor, deterministic: bool = True) -> torch.Tensor:
@@ -589,18 +585,13 @@ class BatchedPPO:
         self.step_out = torch.zeros(self.n_p, **f64)
         self._stat = torch.zeros(MSG_EXTRA - 1, **f64)              # since the last train(): count, loss, kl, clipped, r, ADV sums
         self._stat_rows = 0
-        self._lib = _lib.load()
-        nb = int(self._lib.mpcrl_ppo_surrogate_workspace_bytes_nu(B, self.n_p, nu) if nu > 1 else self._lib.mpcrl_ppo_surrogate_workspace_bytes(B, self.n_p))
-        if nb < 0:
-            raise RuntimeError(f"mpcrl_ppo_surrogate_workspace_bytes failed with {nb}")
-        self._ws = torch.zeros(nb, dtype=torch.uint8, device=dev)
+        self._ws = (_lib.workspace("mpcrl_ppo_surrogate_workspace_bytes_nu", B, self.n_p, nu, device=dev) if nu > 1 else
+                    _lib.workspace("mpcrl_ppo_surrogate_workspace_bytes", B, self.n_p, device=dev))
         self._vloss = torch.zeros((), dtype=torch.float32, device=dev)      # vf_coef x MSE of the last minibatch (summed over the ranks)
         if self.value_kernels:
-            nb = int(self._lib.mpcrl_value_workspace_bytes(B, ocp.nx))
-            if nb < 0:
-                raise RuntimeError(f"mpcrl_value_workspace_bytes failed with {nb}")
             self.n_value = self.policy.value_flat.numel()
-            self._vws = torch.empty(nb, dtype=torch.uint8, device=dev)      # written in full by every call: no initialisation
+            # written in full by every call: no initialisation (so not _lib.workspace, which zeroes)
+            self._vws = torch.empty(_lib.call("mpcrl_value_workspace_bytes", B, ocp.nx), dtype=torch.uint8, device=dev)
             self.vmsg = torch.zeros(self.n_value + 2, **f64)               # [gradient / world, loss, count]
             self._vloss = self.vmsg[self.n_value]
         # the roll-out handle holds an iterate from here on, so that its first solve is the per-instance cold start of the cold mask
@@ -608,8 +599,8 @@ class BatchedPPO:
         self.iterations = 0
 
     # ------------------------------------------------------------------ pieces
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
+    def _call(self, name: str, *args) -> int:
+        return _lib.call(name, *args, device=self.device)
 
     def _collect_step(self, t: int) -> None:
         env, dev = self.env, self.device
@@ -620,21 +611,13 @@ class BatchedPPO:
             return self._collect_step_chain(t, r, value)
         eps = torch.randn(self.E, dtype=torch.float32, device=dev, generator=self.gen)
         u01 = torch.rand(self.E, generator=env.gen, dtype=torch.float64, device=dev)
-        tables = (_ptr(self.OBS), _ptr(self.ACT), _ptr(self.LOGP), _ptr(self.VAL), _ptr(self.REW), _ptr(self.NEXT), _ptr(self.TERM), _ptr(self.DONE),
-                  _ptr(self.OK), _ptr(self.obs), _ptr(self.ended), self._stream())
-        with torch.cuda.device(dev):
-            if self.linear:      # u01: the environment's noise of this step; truncation at episode_length, restart at the reset state
-                name = "mpcrl_ppo_linear_collect"
-                rc = self._lib.mpcrl_ppo_linear_collect(
-                    self._par_c, self.E, self.T, t, _ptr(env.state), _ptr(self.steps), _ptr(r.u0), _ptr(r.status), _ptr(eps), _ptr(u01), _ptr(value),
-                    _ptr(self.log_std), self.lo, self.hi, self.reward_scale, self.episode_length, self._reset_c, *tables)
-            else:
-                name = "mpcrl_ppo_cartpole_collect"
-                rc = self._lib.mpcrl_ppo_cartpole_collect(
-                    env._par(), self.E, self.T, t, _ptr(env.state), _ptr(env.steps), _ptr(r.u0), _ptr(r.status), _ptr(eps), _ptr(u01), _ptr(value),
-                    _ptr(self.log_std), self.lo, self.hi, self.reward_scale, *tables)
-        if rc != 0:
-            raise RuntimeError(f"{name} failed with {rc}")
+        tables = (self.OBS, self.ACT, self.LOGP, self.VAL, self.REW, self.NEXT, self.TERM, self.DONE, self.OK, self.obs, self.ended)
+        if self.linear:      # u01: the environment's noise of this step; truncation at episode_length, restart at the reset state
+            self._call("mpcrl_ppo_linear_collect", self._par_c, self.E, self.T, t, env.state, self.steps, r.u0, r.status, eps, u01, value,
+                       self.log_std, self.lo, self.hi, self.reward_scale, self.episode_length, self._reset_c, *tables)
+        else:
+            self._call("mpcrl_ppo_cartpole_collect", env._par(), self.E, self.T, t, env.state, env.steps, r.u0, r.status, eps, u01, value,
+                       self.log_std, self.lo, self.hi, self.reward_scale, *tables)
         self.last_collect = (r, eps, u01, value)                              # the step's solve and draws (what the tests re-state it from)
         self.rollout_mpc.get_iterate_rows(*self.iters, index=self._rows[t])
 
@@ -644,15 +627,10 @@ class BatchedPPO:
             raise ValueError("env.p must stay a contiguous float64 tensor on the environment's device")
         eps = torch.randn(self.E, self.nu, dtype=torch.float32, device=dev, generator=self.gen)
         wn, rn = self.wn[t], self.rn[t]                                       # this step's rows of the roll-out's draws
-        with torch.cuda.device(dev):
-            rc = self._lib.mpcrl_ppo_chain_collect(
-                self.n_mass, self.Ts, self.rk_steps, _ptr(env.p), 0 if env.p.dim() == 1 else self.n_p, _ptr(env.x_ss), env.w_std, self.E, self.T, t,
-                _ptr(env.state), _ptr(self.steps), _ptr(r.u0), _ptr(r.status), _ptr(eps), _ptr(wn), _ptr(value), _ptr(self.log_std), self.lo_v,
-                self.hi_v, self.reward_scale, self.episode_length, _ptr(self.x_reset), env.vel_std, _ptr(rn), _ptr(self.OBS), _ptr(self.ACT),
-                _ptr(self.LOGP), _ptr(self.VAL), _ptr(self.REW), _ptr(self.NEXT), _ptr(self.TERM), _ptr(self.DONE), _ptr(self.OK), _ptr(self.obs),
-                _ptr(self.ended), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"mpcrl_ppo_chain_collect failed with {rc}")
+        self._call("mpcrl_ppo_chain_collect", self.n_mass, self.Ts, self.rk_steps, env.p, 0 if env.p.dim() == 1 else self.n_p, env.x_ss,
+                   env.w_std, self.E, self.T, t, env.state, self.steps, r.u0, r.status, eps, wn, value, self.log_std, self.lo_v, self.hi_v,
+                   self.reward_scale, self.episode_length, self.x_reset, env.vel_std, rn, self.OBS, self.ACT, self.LOGP, self.VAL, self.REW,
+                   self.NEXT, self.TERM, self.DONE, self.OK, self.obs, self.ended)
         self.last_collect = (r, eps, wn, value, rn)                           # the step's solve and draws (what the tests re-state it from)
         self.rollout_mpc.get_iterate_rows(*self.iters, index=self._rows[t])
 
@@ -669,11 +647,8 @@ class BatchedPPO:
             self._collect_step(t)
         with torch.no_grad():
             self.VNEXT.copy_(self.policy.predict_values(self.NEXT.reshape(-1, self.nx)).reshape(self.T, self.E))
-        with torch.cuda.device(self.device):
-            rc = self._lib.mpcrl_ppo_gae(_ptr(self.REW), _ptr(self.VAL), _ptr(self.VNEXT), _ptr(self.TERM), _ptr(self.DONE), self.T, self.E,
-                                         self.gamma, self.gae_lambda, _ptr(self.ADV), _ptr(self.RET), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"mpcrl_ppo_gae failed with {rc}")
+        self._call("mpcrl_ppo_gae", self.REW, self.VAL, self.VNEXT, self.TERM, self.DONE, self.T, self.E, self.gamma, self.gae_lambda,
+                   self.ADV, self.RET)
 
     def _world(self) -> int:
         import torch.distributed as dist
@@ -681,37 +656,29 @@ class BatchedPPO:
 
     def _minibatch(self, idx: torch.Tensor) -> None:
         import torch.distributed as dist
-        dev, B = self.device, self.B
+        B = self.B
         obs = self.OBS.reshape(-1, self.nx).index_select(0, idx)
         cold = (self.OK.reshape(-1).index_select(0, idx) == 0).to(torch.int32)     # no accepted roll-out solve: no iterate worth starting from
         self.sample_mpc.set_iterate_rows(*self.iters, index=idx)
         r = self.sample_mpc.solve(obs, sens_pi=True, cold_mask=cold)
-        with torch.cuda.device(dev):
-            if self.nu > 1:
-                rc = self._lib.mpcrl_ppo_surrogate_grad_nu(
-                    _ptr(idx), B, self.T * self.E, _ptr(self.ACT), _ptr(self.LOGP), _ptr(self.ADV), _ptr(self.OK), _ptr(r.u0), _ptr(r.status),
-                    _ptr(r.dpi_dp), self.n_p, self.nu, _ptr(self.log_std), self.lo_v, self.hi_v, self.clip_range, self.ent_coef, self.lr,
-                    int(self.normalize_advantage), _ptr(self._ws), _ptr(self.msg), self._stream())
-            else:
-                rc = self._lib.mpcrl_ppo_surrogate_grad(
-                    _ptr(idx), B, self.T * self.E, _ptr(self.ACT), _ptr(self.LOGP), _ptr(self.ADV), _ptr(self.OK), _ptr(r.u0), _ptr(r.status),
-                    _ptr(r.dpi_dp), self.n_p, _ptr(self.log_std), self.lo, self.hi, self.clip_range, self.ent_coef, self.lr,
-                    int(self.normalize_advantage), _ptr(self._ws), _ptr(self.msg), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"mpcrl_ppo_surrogate_grad failed with {rc}")
+        if self.nu > 1:
+            self._call("mpcrl_ppo_surrogate_grad_nu", idx, B, self.T * self.E, self.ACT, self.LOGP, self.ADV, self.OK, r.u0, r.status, r.dpi_dp,
+                       self.n_p, self.nu, self.log_std, self.lo_v, self.hi_v, self.clip_range, self.ent_coef, self.lr,
+                       int(self.normalize_advantage), self._ws, self.msg)
+        else:
+            self._call("mpcrl_ppo_surrogate_grad", idx, B, self.T * self.E, self.ACT, self.LOGP, self.ADV, self.OK, r.u0, r.status, r.dpi_dp,
+                       self.n_p, self.log_std, self.lo, self.hi, self.clip_range, self.ent_coef, self.lr, int(self.normalize_advantage),
+                       self._ws, self.msg)
         world = self._world()
         if world > 1:
             dist.all_reduce(self.msg, op=dist.ReduceOp.SUM, group=self.group)      # the one collective of the policy step
         self._stat += self.msg[self.n_p + 1: self.n_p + MSG_EXTRA]
         self._stat_rows += B * world
-        with torch.cuda.device(dev):
-            rc = self._lib.mpcrl_qlearning_apply(_ptr(self.msg), self.n_p, _ptr(self.learn_mask), _ptr(self.theta), _ptr(self.step_out), self._stream())
-            if self.nu > 1:
-                rc2 = self._lib.mpcrl_ppo_log_std_apply_nu(_ptr(self.msg), self.n_p, self.nu, _ptr(self.log_std), self._stream())
-            else:
-                rc2 = self._lib.mpcrl_ppo_log_std_apply(_ptr(self.msg), self.n_p, _ptr(self.log_std), self._stream())
-        if rc != 0 or rc2 != 0:
-            raise RuntimeError(f"mpcrl_qlearning_apply / mpcrl_ppo_log_std_apply failed with {rc} / {rc2}")
+        self._call("mpcrl_qlearning_apply", self.msg, self.n_p, self.learn_mask, self.theta, self.step_out)
+        if self.nu > 1:
+            self._call("mpcrl_ppo_log_std_apply_nu", self.msg, self.n_p, self.nu, self.log_std)
+        else:
+            self._call("mpcrl_ppo_log_std_apply", self.msg, self.n_p, self.log_std)
         for m in (self.rollout_mpc, self.sample_mpc):
             m.set_theta(self.theta)
         self._value_step(idx, obs, world)
@@ -719,14 +686,10 @@ class BatchedPPO:
     def _value_step(self, idx: torch.Tensor, obs: torch.Tensor, world: int) -> None:
         """The value network's step on the returns of the minibatch ``idx`` (``obs``: its observations, float64 [B, nx])."""
         import torch.distributed as dist
-        dev, B = self.device, self.B
+        B = self.B
         if self.value_kernels:
-            with torch.cuda.device(dev):
-                rc = self._lib.mpcrl_value_mse_grad(_ptr(self.OBS), _ptr(self.RET), _ptr(idx), B, self.T * self.E, self.ocp.nx,
-                                                    _ptr(self.policy.value_flat), self.vf_coef, 1.0 / world, _ptr(self._vws), _ptr(self.vmsg),
-                                                    self._stream())
-            if rc != 0:
-                raise RuntimeError(f"mpcrl_value_mse_grad failed with {rc}")
+            self._call("mpcrl_value_mse_grad", self.OBS, self.RET, idx, B, self.T * self.E, self.ocp.nx, self.policy.value_flat, self.vf_coef,
+                       1.0 / world, self._vws, self.vmsg)
             if world > 1:
                 dist.all_reduce(self.vmsg, op=dist.ReduceOp.SUM, group=self.group)     # the one collective of the value step
             self.policy.value_grad_flat.copy_(self.vmsg[: self.n_value])

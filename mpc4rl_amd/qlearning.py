@@ -22,7 +22,7 @@ from typing import Callable, Optional, Tuple
 import torch
 
 from . import _lib
-from .batch import MPCBatch, _ptr
+from .batch import MPCBatch
 from .distributed import mean_update
 
 
@@ -296,9 +296,9 @@ class DeviceQLearning:
     largest |p0_c| over the learned entries, and to 1 if those are all 0.  With all three None the plain step runs, bit for bit as before.
     ``EpisodeStats.gn_active`` counts the entries on a bound, ``gn_iterations`` the active-set iterations.
 
-    A plant's class sets ``NX``, ``_COLLECT`` and, with more than one control, ``NU``, checks its OCP and environment, allocates
+    A plant's class sets ``NX`` and, with more than one control, ``NU``, checks its OCP and environment, allocates
     ``live`` [T, E] (and what else its collect kernel needs) after this constructor, and defines ``_collect(r)`` (the collect launch
-    after the roll-out solve r; returns its status), ``_stats()``, where the environment carries more than its state from step to step
+    after the roll-out solve r, through ``self._call``), ``_stats()``, where the environment carries more than its state from step to step
     ``_env_carried()``, and, where the zero state is no state of the plant, ``_initial_obs()``.
 
     ``NU`` = 1: ``A`` and ``eps`` are [T, E] and the control bounds the floats ``lo``, ``hi``.  ``NU`` > 1: ``A`` and ``eps`` are
@@ -306,7 +306,6 @@ class DeviceQLearning:
 
     NX: int = 0             # the state's width
     NU: int = 1             # the number of controls
-    _COLLECT: str = ""      # the library's collect entry point (for error messages)
     _SAMPLE: bool = True    # False: a learner without a learning sweep (policy_gradient.py) builds no ``sample_mpc`` and no TD workspace
 
     def __init__(self, ocp, env, episode_length: int, lr: float, gamma: float, noise_scale: float, seed: int, device, group,
@@ -393,12 +392,8 @@ class DeviceQLearning:
         self.valid = torch.zeros(T - 2, E, dtype=torch.uint8, device=dev)
         self.msg = torch.zeros(self.n_p + 2, **f64)
         self.step_out = torch.zeros(self.n_p, **f64)
-        self._lib = _lib.load()
         if self._SAMPLE:
-            nb = int(self._lib.mpcrl_qlearning_td_workspace_bytes(T, E, self.n_p))
-            if nb < 0:
-                raise RuntimeError(f"mpcrl_qlearning_td_workspace_bytes failed with {nb}")
-            self._td_ws = torch.zeros(nb, dtype=torch.uint8, device=dev)
+            self._td_ws = _lib.workspace("mpcrl_qlearning_td_workspace_bytes", T, E, self.n_p, device=dev)
         # the roll-out handle holds an iterate from here on, so that the first solve of every episode (eager or replayed) is the
         # per-instance cold start of the cold mask, never the handle-wide one of a fresh handle
         x_init = self._initial_obs()
@@ -413,8 +408,8 @@ class DeviceQLearning:
         self.episodes = 0
 
     # ------------------------------------------------------------------ pieces (the same launches eager and captured)
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
+    def _call(self, name: str, *args) -> int:
+        return _lib.call(name, *args, device=self.device)
 
     def _handles(self):
         return (self.rollout_mpc, self.sample_mpc) if self._SAMPLE else (self.rollout_mpc,)
@@ -430,10 +425,7 @@ class DeviceQLearning:
 
     def _rollout_step(self):
         r = self.rollout_mpc.solve(self.obs, cold_mask=self.cold)           # the policy of every environment (mpc.get_action), one launch
-        with torch.cuda.device(self.device):
-            rc = self._collect(r)
-        if rc != 0:
-            raise RuntimeError(f"{self._COLLECT} failed with {rc}")
+        self._collect(r)
         return r
 
     def _gn_setup(self) -> None:
@@ -445,12 +437,9 @@ class DeviceQLearning:
         K = int(idx.numel())
         if K < 1 or K > GN_KMAX:
             raise ValueError(f"method='gauss_newton' learns between 1 and {GN_KMAX} entries of theta; learn_mask marks {K}")
-        nb = int(self._lib.mpcrl_qlearning_gn_workspace_bytes(self.T, self.E, K))
-        if nb < 0:
-            raise RuntimeError(f"mpcrl_qlearning_gn_workspace_bytes failed with {nb}")
         self.K = K
         self.msg = torch.zeros(gn_msg_len(K), dtype=torch.float64, device=self.device)
-        self._gn_ws = torch.zeros(nb, dtype=torch.uint8, device=self.device)
+        self._gn_ws = _lib.workspace("mpcrl_qlearning_gn_workspace_bytes", self.T, self.E, K, device=self.device)
         self.learn_idx = idx.to(torch.int32).contiguous()
         if self.box:
             self._box_setup(idx, K)
@@ -479,20 +468,11 @@ class DeviceQLearning:
         # ... update: V(s_i) from the Q solve's primal iterate, interior point from its default point
         rv = self.sample_mpc.solve(s)
         if self.method == "gauss_newton":
-            with torch.cuda.device(self.device):
-                rc = self._lib.mpcrl_qlearning_td_gn(
-                    _ptr(rq.V), _ptr(rv.V), _ptr(rq.dV_dp), _ptr(rq.status), _ptr(rv.status), _ptr(self.C), _ptr(self.live), self.T, self.E,
-                    self.n_p, self.gamma, _ptr(self.learn_idx), self.K, _ptr(self._gn_ws), _ptr(self.td), _ptr(self.valid), _ptr(self.msg),
-                    self._stream())
-            if rc != 0:
-                raise RuntimeError(f"mpcrl_qlearning_td_gn failed with {rc}")
-            return rq, rv
-        with torch.cuda.device(self.device):
-            rc = self._lib.mpcrl_qlearning_td_grad(
-                _ptr(rq.V), _ptr(rv.V), _ptr(rq.dV_dp), _ptr(rq.status), _ptr(rv.status), _ptr(self.C), _ptr(self.live), self.T, self.E, self.n_p,
-                self.gamma, self.lr, _ptr(self._td_ws), _ptr(self.td), _ptr(self.valid), _ptr(self.msg), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"mpcrl_qlearning_td_grad failed with {rc}")
+            self._call("mpcrl_qlearning_td_gn", rq.V, rv.V, rq.dV_dp, rq.status, rv.status, self.C, self.live, self.T, self.E, self.n_p,
+                       self.gamma, self.learn_idx, self.K, self._gn_ws, self.td, self.valid, self.msg)
+        else:
+            self._call("mpcrl_qlearning_td_grad", rq.V, rv.V, rq.dV_dp, rq.status, rv.status, self.C, self.live, self.T, self.E, self.n_p,
+                       self.gamma, self.lr, self._td_ws, self.td, self.valid, self.msg)
         return rq, rv
 
     def _allreduce(self) -> None:
@@ -502,25 +482,13 @@ class DeviceQLearning:
 
     def _apply(self) -> None:
         if self.method == "gauss_newton" and self.box:
-            with torch.cuda.device(self.device):
-                rc = self._lib.mpcrl_qlearning_gn_apply_box(_ptr(self.msg), self.K, _ptr(self.learn_idx), self.n_p, self.lr, self.damping,
-                                                            _ptr(self.theta_lo), _ptr(self.theta_hi), _ptr(self.theta_scale), self.trust_radius,
-                                                            _ptr(self.theta), _ptr(self.step_out), _ptr(self.gn_active), _ptr(self.gn_info),
-                                                            self._stream())
-            if rc != 0:
-                raise RuntimeError(f"mpcrl_qlearning_gn_apply_box failed with {rc}")
+            self._call("mpcrl_qlearning_gn_apply_box", self.msg, self.K, self.learn_idx, self.n_p, self.lr, self.damping, self.theta_lo,
+                       self.theta_hi, self.theta_scale, self.trust_radius, self.theta, self.step_out, self.gn_active, self.gn_info)
         elif self.method == "gauss_newton":
-            with torch.cuda.device(self.device):
-                rc = self._lib.mpcrl_qlearning_gn_apply(_ptr(self.msg), self.K, _ptr(self.learn_idx), self.n_p, self.lr, self.damping,
-                                                        _ptr(self.theta), _ptr(self.step_out), _ptr(self.gn_info), self._stream())
-            if rc != 0:
-                raise RuntimeError(f"mpcrl_qlearning_gn_apply failed with {rc}")
+            self._call("mpcrl_qlearning_gn_apply", self.msg, self.K, self.learn_idx, self.n_p, self.lr, self.damping, self.theta,
+                       self.step_out, self.gn_info)
         else:
-            with torch.cuda.device(self.device):
-                rc = self._lib.mpcrl_qlearning_apply(_ptr(self.msg), self.n_p, _ptr(self.learn_mask), _ptr(self.theta), _ptr(self.step_out),
-                                                     self._stream())
-            if rc != 0:
-                raise RuntimeError(f"mpcrl_qlearning_apply failed with {rc}")
+            self._call("mpcrl_qlearning_apply", self.msg, self.n_p, self.learn_mask, self.theta, self.step_out)
         self._set_theta()
 
     def _set_theta(self) -> None:

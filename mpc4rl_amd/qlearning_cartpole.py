@@ -35,7 +35,6 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .batch import _ptr
 from .envs import BatchedCartPoleSwingUpEnv
 from .qlearning import DeviceQLearning, EpisodeStats
 
@@ -75,7 +74,6 @@ class CartpoleQLearning(DeviceQLearning):
     Of theta, (M, m, l) are learned."""
 
     NX = 4
-    _COLLECT = "mpcrl_qlearning_cartpole_collect"
 
     def __init__(self, ocp, env, episode_length: int, lr: float = 1e-4, gamma: float = 0.99, noise_scale: float = 0.1, seed: int = 0,
                  device=None, group=None, method: str = "gradient", damping: float = 1e-3, trust_radius: Optional[float] = None,
@@ -93,12 +91,10 @@ class CartpoleQLearning(DeviceQLearning):
         super()._start_episode(x0)
         self.alive.fill_(1)
 
-    def _collect(self, r) -> int:
+    def _collect(self, r) -> None:
         env = self.env
-        return self._lib.mpcrl_qlearning_cartpole_collect(
-            env._par(), self.E, self.T, _ptr(env.state), _ptr(env.steps), _ptr(r.u0), _ptr(r.status), _ptr(self.eps), self.lo, self.hi,
-            self.noise_scale, _ptr(self.obs), _ptr(self.alive), _ptr(self.row), _ptr(self.cold), _ptr(self.S), _ptr(self.A), _ptr(self.C),
-            _ptr(self.live), self._stream())
+        self._call("mpcrl_qlearning_cartpole_collect", env._par(), self.E, self.T, env.state, env.steps, r.u0, r.status, self.eps, self.lo,
+                   self.hi, self.noise_scale, self.obs, self.alive, self.row, self.cold, self.S, self.A, self.C, self.live)
 
     def _env_carried(self):
         return [self.env.state, self.env.steps]

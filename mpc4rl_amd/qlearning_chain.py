@@ -24,7 +24,6 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from .batch import _ptr
 from .envs import BatchedChainMassEnv, _chain_dims
 from .problems import chain_param_layout
 from .qlearning import DeviceQLearning, EpisodeStats
@@ -144,7 +143,6 @@ class ChainQLearning(DeviceQLearning):
     (roll-out handle, sweep handle) as the library reports them."""
 
     NU = 3
-    _COLLECT = "mpcrl_qlearning_chain_collect"
     BLOCKS = ("m", "D", "L", "C", "Q", "R", "w")
 
     def __init__(self, ocp, env, episode_length: int, lr: float = 1e-6, gamma: Optional[float] = None, noise_scale: float = 0.0, seed: int = 0,
@@ -187,12 +185,11 @@ class ChainQLearning(DeviceQLearning):
         super()._start_episode(x0)
         torch.randn(*self.wn.shape, generator=self.env.gen, dtype=torch.float64, device=self.device, out=self.wn)
 
-    def _collect(self, r) -> int:
+    def _collect(self, r) -> None:
         env = self.env
-        return self._lib.mpcrl_qlearning_chain_collect(
-            self.n_mass, self.Ts, self.rk_steps, _ptr(env.p), 0 if env.p.dim() == 1 else self.n_p, _ptr(env.x_ss), env.w_std, self.E, self.T,
-            _ptr(env.state), _ptr(r.u0), _ptr(r.status), _ptr(self.eps), _ptr(self.wn), self.lo_v, self.hi_v, self.noise_scale, _ptr(self.obs),
-            _ptr(self.row), _ptr(self.cold), _ptr(self.S), _ptr(self.A), _ptr(self.C), self._stream())
+        self._call("mpcrl_qlearning_chain_collect", self.n_mass, self.Ts, self.rk_steps, env.p, 0 if env.p.dim() == 1 else self.n_p, env.x_ss,
+                   env.w_std, self.E, self.T, env.state, r.u0, r.status, self.eps, self.wn, self.lo_v, self.hi_v, self.noise_scale, self.obs,
+                   self.row, self.cold, self.S, self.A, self.C)
 
     def _stats(self) -> EpisodeStats:
         nv = float(self.valid.sum().item())

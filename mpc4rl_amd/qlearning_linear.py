@@ -28,7 +28,6 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib
-from .batch import _ptr
 from .envs import BatchedLinearSystemEnv
 from .qlearning import DeviceQLearning, EpisodeStats
 
@@ -81,7 +80,6 @@ class LinearQLearning(DeviceQLearning):
     f) is learned."""
 
     NX = 2
-    _COLLECT = "mpcrl_qlearning_linear_collect"
 
     def __init__(self, ocp, env, episode_length: int, lr: float = 1e-4, gamma: Optional[float] = None, noise_scale: float = 0.0, seed: int = 0,
                  device=None, group=None, method: str = "gradient", damping: float = 1e-3, trust_radius: Optional[float] = None,
@@ -102,10 +100,9 @@ class LinearQLearning(DeviceQLearning):
         super()._start_episode(x0)
         torch.rand(self.T, self.E, generator=self.env.gen, dtype=torch.float64, device=self.device, out=self.u01)
 
-    def _collect(self, r) -> int:
-        return self._lib.mpcrl_qlearning_linear_collect(
-            self._par_c, self.E, self.T, _ptr(self.env.state), _ptr(r.u0), _ptr(r.status), _ptr(self.eps), _ptr(self.u01), self.lo, self.hi,
-            self.noise_scale, _ptr(self.obs), _ptr(self.row), _ptr(self.cold), _ptr(self.S), _ptr(self.A), _ptr(self.C), self._stream())
+    def _collect(self, r) -> None:
+        self._call("mpcrl_qlearning_linear_collect", self._par_c, self.E, self.T, self.env.state, r.u0, r.status, self.eps, self.u01, self.lo,
+                   self.hi, self.noise_scale, self.obs, self.row, self.cold, self.S, self.A, self.C)
 
     def _stats(self) -> EpisodeStats:
         nv = float(self.valid.sum().item())

@@ -8,12 +8,12 @@ grad_a Q from any torch critic.  (No reference behaviour to match for the update
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
 from torch import nn
 
+from . import _lib
 from .batch import MPCBatch
 from .distributed import mean_update
 
@@ -67,34 +67,27 @@ def critic_td_grad(rows, nx: int, nu: int, a_next, ok_u, params, params_target, 
     """mpcrl_critic_td_grad (include/mpcrl.h): TD target, twin-critic loss and its gradient with respect to the flat critic parameters —
     two launches.  rows [B, >= 2 nx + nu + 2] float32 (obs | next obs | action | reward | done), a_next [B, nu] float32, ok_u [B] bool /
     uint8 or None; grad_out: float64 [n_params] (written).  Returns (loss [1] float32, ok [B] bool, workspace)."""
-    from . import _lib
-    lib = _lib.load()
     B = rows.shape[0]
     dev = rows.device
     if not (rows.dtype == torch.float32 and rows.stride(1) == 1 and a_next.dtype == torch.float32 and a_next.is_contiguous()):
         raise ValueError("rows / a_next: float32, unit inner stride")
-    need = lib.mpcrl_critic_workspace_bytes(B, nx, nu, n_critics)
-    if need < 0:
-        raise ValueError("mpcrl_critic_td_grad: nx + nu <= 64, n_critics 1 or 2")
+    try:
+        need = _lib.call("mpcrl_critic_workspace_bytes", B, nx, nu, n_critics)
+    except RuntimeError:
+        raise ValueError("mpcrl_critic_td_grad: nx + nu <= 64, n_critics 1 or 2") from None
     if workspace is None or workspace.numel() * 4 < need:
         workspace = torch.empty(need // 4, dtype=torch.float32, device=dev)
     okb = None if ok_u is None else _as_u8(ok_u)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     ok = torch.empty(B, dtype=torch.uint8, device=dev)
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        rc = lib.mpcrl_critic_td_grad(ptr(rows), rows.stride(0), B, nx, nu, ptr(a_next), ptr(okb), ptr(params), ptr(params_target), n_critics,
-                                      float(gamma), float(out_scale), ptr(workspace), ptr(grad_out), ptr(loss), ptr(ok),
-                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"mpcrl_critic_td_grad failed with code {rc}")
+    _lib.call("mpcrl_critic_td_grad", rows, rows.stride(0), B, nx, nu, a_next, okb, params, params_target, n_critics, float(gamma),
+              float(out_scale), workspace, grad_out, loss, ok, device=dev)
     return loss, ok.view(torch.bool), workspace
 
 
 def critic_dq_da(obs, nx: int, act, ok_u, params):
     """mpcrl_critic_dq_da: dQ_1/da at (obs[:, :nx], act), one launch; 0 where ok_u is 0 or an input is not finite.  Returns (dq_da [B, nu]
     float32, ok [B] bool)."""
-    from . import _lib
     B, nu = act.shape
     dev = act.device
     if not (obs.dtype == torch.float32 and obs.stride(1) == 1 and act.dtype == torch.float32 and act.is_contiguous()):
@@ -102,33 +95,21 @@ def critic_dq_da(obs, nx: int, act, ok_u, params):
     okb = None if ok_u is None else _as_u8(ok_u)
     out = torch.empty((B, nu), dtype=torch.float32, device=dev)
     ok = torch.empty(B, dtype=torch.uint8, device=dev)
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        rc = _lib.load().mpcrl_critic_dq_da(ptr(obs), obs.stride(0), B, nx, nu, ptr(act), ptr(okb), ptr(params), ptr(out), ptr(ok),
-                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"mpcrl_critic_dq_da failed with code {rc}")
+    _lib.call("mpcrl_critic_dq_da", obs, obs.stride(0), B, nx, nu, act, okb, params, out, ok, device=dev)
     return out, ok.view(torch.bool)
 
 
 def dpg_grad(dq_da, ok, dpi_dp, low, high, scale: bool, out, workspace=None):
     """mpcrl_dpg_grad: out[:n_p] = sum_b ok_b sum_u dq_da[b, u] chain_u dpi_dp[b, u, :], out[n_p] = sum_b ok_b — one launch, fixed summation
     order.  out: float64 [n_p + 1] (written; may be a slice of a larger message).  Returns the workspace to pass again."""
-    from . import _lib
-    lib = _lib.load()
     B, nu, n_p = dpi_dp.shape
     dev = dpi_dp.device
     if not (dq_da.dtype == torch.float32 and dq_da.is_contiguous() and dpi_dp.dtype == torch.float64 and dpi_dp.is_contiguous() and out.is_contiguous()):
         raise ValueError("dq_da: contiguous float32 [B, nu]; dpi_dp, out: contiguous float64")
-    need = lib.mpcrl_dpg_workspace_bytes(B, n_p)
+    need = _lib.call("mpcrl_dpg_workspace_bytes", B, n_p)
     if workspace is None or workspace.numel() * 8 < need:
         workspace = torch.zeros((need + 7) // 8, dtype=torch.float64, device=dev)       # (zero once: the kernel leaves its counter zero)
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        rc = lib.mpcrl_dpg_grad(ptr(dq_da), ptr(None if ok is None else _as_u8(ok)), ptr(dpi_dp), B, nu, n_p, ptr(low), ptr(high), int(scale),
-                                ptr(workspace), ptr(out), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"mpcrl_dpg_grad failed with code {rc}")
+    _lib.call("mpcrl_dpg_grad", dq_da, None if ok is None else _as_u8(ok), dpi_dp, B, nu, n_p, low, high, int(scale), workspace, out, device=dev)
     return workspace
 
 
@@ -154,18 +135,13 @@ class MPCActor:
         accept_status2 also 2: the closed loop applies what max_iter left) and u0 is finite, 0 elsewhere — plus
         clip(sigma noise, +-noise_clip), the sum clipped to [-1, 1] when ``noise`` (standard-normal draws, float32) is given.  ONE launch
         (mpcrl_policy_action) for what is ~15 elementwise launches in torch; the same arithmetic in the same order and types."""
-        from . import _lib
         B, nu = r.u0.shape
         a = torch.empty((B, nu), dtype=torch.float32, device=r.u0.device)
         ok = torch.empty((B,), dtype=torch.uint8, device=r.u0.device)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         if noise is not None and not (noise.dtype == torch.float32 and noise.is_contiguous() and noise.shape == (B, nu)):
             raise ValueError("noise: contiguous float32 [B, nu]")
-        with torch.cuda.device(r.u0.device):
-            rc = _lib.load().mpcrl_policy_action(ptr(r.u0), ptr(r.status), ptr(noise), ptr(self.low), ptr(self.high), B, nu, int(self.scale), float(sigma),
-                                                 float(noise_clip), int(accept_status2), ptr(a), ptr(ok), C.c_void_p(torch.cuda.current_stream(r.u0.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"mpcrl_policy_action failed with code {rc}")
+        _lib.call("mpcrl_policy_action", r.u0, r.status, noise, self.low, self.high, B, nu, int(self.scale), float(sigma), float(noise_clip),
+                  int(accept_status2), a, ok, device=r.u0.device)
         return a, ok.view(torch.bool)        # (0 / 1 bytes: a view, not a launch)
 
     def forward(self, obs: torch.Tensor) -> torch.Tensor:        # Actor.forward, td3/policies.py:186-197 — ONE launch
@@ -318,7 +294,6 @@ class DeviceReplayBuffer:
         mpcrl_replay_sample: the same draw (torch.randint on ``gen``), then ONE launch.  Returns (obs, next_obs, act, rew, done) as
         sample() does — views of ``last_rows`` — and sets ``last_x64`` = (obs, next_obs) in float64 and, with iterate tables,
         ``last_starts`` = (rows for obs, cold mask, rows for next_obs, cold mask), masks as int32 (1 = start cold)."""
-        from . import _lib
         steps = self.cap if self.full else self.pos
         if steps == 0:
             raise RuntimeError("DeviceReplayBuffer.sample: the buffer is empty (call collect() / add() first)")
@@ -331,20 +306,13 @@ class DeviceReplayBuffer:
         L, nx, nu = self.data.shape[-1], self._nx, self._nu
         rows = torch.empty((n, L), dtype=torch.float32, device=dev)
         x64 = torch.empty((2, n, nx), dtype=torch.float64, device=dev)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         st = None
         if self.iters is not None:
             r64 = torch.empty((2, n), dtype=torch.int64, device=dev)
             c32 = torch.empty((2, n), dtype=torch.int32, device=dev)
             st = (r64[0], c32[0], r64[1], c32[1])
-        with torch.cuda.device(dev):
-            rc = _lib.load().mpcrl_replay_sample(ptr(self.data), L, nx, self.E, self.cap, steps, ptr(idx), n,
-                                                 ptr(self.pos_t if exclude_pos is None else exclude_pos), int(exclude_pos is not None),
-                                                 ptr(self.iter_ok) if st else None, ptr(rows), ptr(x64[0]), ptr(x64[1]),
-                                                 ptr(st[0]) if st else None, ptr(st[1]) if st else None, ptr(st[2]) if st else None,
-                                                 ptr(st[3]) if st else None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"mpcrl_replay_sample failed with code {rc}")
+        _lib.call("mpcrl_replay_sample", self.data, L, nx, self.E, self.cap, steps, idx, n, self.pos_t if exclude_pos is None else exclude_pos,
+                  int(exclude_pos is not None), self.iter_ok if st else None, rows, x64[0], x64[1], *(st or (None,) * 4), device=dev)
         self.last_idx, self.last_steps, self.last_rows, self.last_x64, self.last_starts = idx, steps, rows, (x64[0], x64[1]), st
         return rows[:, :nx], rows[:, nx: 2 * nx], rows[:, 2 * nx: 2 * nx + nu], rows[:, -2], rows[:, -1]
 
@@ -518,21 +486,14 @@ class BatchedTD3:
         """_collect_step on mpcrl_td3_cartpole_collect: the solve, the two draws (the generators stay torch's), ONE launch for the actor's
         output stage, the environment step, the replay row, the statistics, the resets, the next observation and cold mask — all in
         place, so eager and graph-replayed steps are the same launches — and the move of the iterates into the replay tables."""
-        from . import _lib
-        from .batch import _ptr
         env, buf, dev = self.env, self.buffer, self.device
         r = self.actor.mpc.solve(self.obs, cold_mask=self._ended)
         eps = torch.randn(r.u0.shape, dtype=torch.float32, device=dev, generator=self.gen)
         u01 = torch.rand(self.E, generator=env.gen, dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.load().mpcrl_td3_cartpole_collect(
-                env._par(), self.E, _ptr(env.state), _ptr(env.steps), _ptr(r.u0), _ptr(r.status), _ptr(eps), _ptr(u01), self._lo_hi[0],
-                self._lo_hi[1], int(bool(self.actor.scale)), float(self.action_noise), _ptr(self.obs), _ptr(self._ended), _ptr(buf.data),
-                buf.cap, float(self.reward_scale), _ptr(buf.pos_t), _ptr(buf.iter_ok) if self.replay_iterates else None,
-                _ptr(self._iter_rows) if self.replay_iterates else None, _ptr(self._stats), _ptr(self._collect_ws),
-                torch.cuda.current_stream(dev).cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"mpcrl_td3_cartpole_collect failed with code {rc}")
+        _lib.call("mpcrl_td3_cartpole_collect", env._par(), self.E, env.state, env.steps, r.u0, r.status, eps, u01, self._lo_hi[0], self._lo_hi[1],
+                  int(bool(self.actor.scale)), float(self.action_noise), self.obs, self._ended, buf.data, buf.cap, float(self.reward_scale),
+                  buf.pos_t, buf.iter_ok if self.replay_iterates else None, self._iter_rows if self.replay_iterates else None, self._stats,
+                  self._collect_ws, device=dev)
         if self.replay_iterates:
             self.actor.mpc.get_iterate_rows(*buf.iters, index=self._iter_rows)
         if not static:
@@ -686,15 +647,9 @@ class BatchedTD3:
         self.critic_opt.step()
         step = None
         if do_policy and self._fused_critic:      # the policy step, theta' and the target critics' Polyak update: one launch
-            from . import _lib
-            from .batch import _ptr
             step = torch.empty_like(self.theta)
-            with torch.cuda.device(self.device), torch.no_grad():
-                rc = _lib.load().mpcrl_td3_policy_post(C.c_void_p(flat.data_ptr() + 8 * self.n_crit), n_theta, float(self.lr_actor), _ptr(self.learn_mask),
-                                                       float(self.tau), _ptr(self.theta), _ptr(self.theta_target), _ptr(step), _ptr(self._crit_flat),
-                                                       _ptr(self._crit_target_flat), self.n_crit, torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                raise RuntimeError(f"mpcrl_td3_policy_post failed with code {rc}")
+            _lib.call("mpcrl_td3_policy_post", flat[self.n_crit:], n_theta, float(self.lr_actor), self.learn_mask, float(self.tau), self.theta,
+                      self.theta_target, step, self._crit_flat, self._crit_target_flat, self.n_crit, device=self.device)
             if push_theta:
                 self._push_theta()
         elif do_policy:
