@@ -1,4 +1,4 @@
-"""ctypes binding of libmpcrl_hip.so, read from include/mpcrl.h, and the one path the package calls the library through
+"""ctypes binding of libmpcrl_hip.so, read from include/mpcrl.h (and include/mpcrl_ext.h, a table of its own), and the one path the package calls the library through
 (``call``, ``workspace``).  Fails loudly when the library is missing.
 
 The .hip units include the same header, so the compiler holds the implementation to it; the prototypes, constants and error codes here
@@ -18,6 +18,7 @@ from typing import Dict, List, NamedTuple, Tuple
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MPCRL_LIB_PATH") or os.path.join(_HERE, "libmpcrl_hip.so")   # the override is for instrumented builds (profiles/microbench)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mpcrl.h")
+EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mpcrl_ext.h")   # extensions beyond the reference's MPC surface, versioned on their own
 
 # ---------------------------------------------------------------------- the header, parsed (standard library only)
 # parameter kinds: "int", "int64", "double", "handle"; pointers "double*", "float*", "int32*", "int64*", "uint8*", "void*", "spec*", "handle*"
@@ -83,6 +84,13 @@ if not os.path.exists(HEADER_PATH):
 with open(HEADER_PATH) as _f:
     HEADER = parse_header(_f.read())
 EXPORTS = list(HEADER.functions)
+if not os.path.exists(EXT_HEADER_PATH):
+    raise ImportError(f"mpc4rl_amd: {EXT_HEADER_PATH} not found. The binding is read from the headers: keep include/ beside the package.")
+with open(EXT_HEADER_PATH) as _f:
+    EXT_HEADER = parse_header(_f.read())      # a table of its own: HEADER, EXPORTS and the constants below describe mpcrl.h alone
+EXT_EXPORTS = list(EXT_HEADER.functions)
+EXT_VERSION = EXT_HEADER.constants["EXT_VERSION"]
+STATE_Q_MODE = EXT_HEADER.constants["STATE_Q_MODE"]
 
 
 def _constants(names: str):
@@ -146,7 +154,11 @@ def load():
     # what a tensor handed to a pointer parameter may hold: None = no tensor there, () = any (void *)
     dtypes = {"double*": (torch.float64,), "float*": (torch.float32,), "int32*": (torch.int32,), "int64*": (torch.int64,),
               "uint8*": (torch.uint8, torch.bool), "void*": ()}
-    for name, (ret, params) in HEADER.functions.items():
+    lib.mpcrl_ext_version.restype = C.c_int
+    if lib.mpcrl_ext_version() != EXT_VERSION and not os.environ.get("MPCRL_SKIP_ABI_CHECK"):
+        raise RuntimeError(f"mpc4rl_amd: {LIB_PATH} reports extension version {lib.mpcrl_ext_version()}, this binding expects {EXT_VERSION}; "
+                           "rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`).")
+    for name, (ret, params) in list(HEADER.functions.items()) + list(EXT_HEADER.functions.items()):
         fn = getattr(lib, name)
         fn.restype = _CTYPE[ret]
         fn.argtypes = [_CTYPE.get(kind, C.c_void_p) for _, kind in params]

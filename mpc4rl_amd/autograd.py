@@ -1,0 +1,127 @@
+"""The MPC as a differentiable torch layer: ``u0, V = layer(x0, theta)`` and ``Q = layer.q(x0, u0, theta)`` inside a torch graph.
+
+The forward pass is one solve of the ``MPCBatch`` the layer is built around — with the parameter sensitivities ``theta.requires_grad``
+calls for — and, when ``x0`` (or the pinned ``u0``) needs a gradient, one ``mpcrl_state_sens`` (include/mpcrl_ext.h).  The backward
+pass is plain torch contractions of the stored Jacobians with the incoming gradients (``mpc_backward_terms``):
+
+    g_x0    = g_u' du0*/dx0 + g_V dV/dx0
+    g_theta = g_u' du0*/dp  + g_V dV/dp          summed over the batch for a shared theta [n_p], per instance for theta [B, n_p]
+    g_u0    = g_Q dQ/du0                         (``layer.q``)
+
+Instances whose solve did not end with status 0 contribute zero gradient; ``layer.last_status`` keeps the statuses.  The chain of
+masses has no du0*/dx0 yet: a loss that depends on ``u0`` cannot be back-propagated to ``x0`` there, and asking for it raises.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from .batch import MPCBatch
+
+
+def mpc_backward_terms(g_u: Optional[torch.Tensor], g_V: Optional[torch.Tensor], status: torch.Tensor,
+                       du_dx0: Optional[torch.Tensor], dV_dx0: Optional[torch.Tensor],
+                       du_dp: Optional[torch.Tensor], dV_dp: Optional[torch.Tensor],
+                       shared_theta: bool) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """(g_x0 [B, nx] or None, g_theta [n_p] / [B, n_p] or None) from the incoming gradients g_u [B, nu], g_V [B] (None = the loss does
+    not depend on that output) and the Jacobians du_dx0 [B, nu, nx], dV_dx0 [B, nx], du_dp [B, nu, n_p], dV_dp [B, n_p] (None = that
+    side is not wanted).  Rows of instances with status != 0 are selected out of every Jacobian before it is contracted, so whatever
+    they hold (NaN included) never reaches a gradient.  Tensors only: runs on any device."""
+    good = status == 0
+
+    def rows(J):      # a select, not a product with a mask: 0 * NaN would be NaN
+        return torch.where(good.reshape((-1,) + (1,) * (J.dim() - 1)), J, torch.zeros_like(J))
+
+    def contract(du, dV):
+        g = None
+        if g_u is not None and du is not None:
+            g = torch.einsum("bi,bij->bj", g_u, rows(du))
+        if g_V is not None and dV is not None:
+            t = g_V.reshape(-1, 1) * rows(dV)
+            g = t if g is None else g + t
+        return g
+
+    g_x0 = contract(du_dx0, dV_dx0)
+    g_th = contract(du_dp, dV_dp)
+    if g_th is not None and shared_theta:
+        g_th = g_th.sum(0)
+    return g_x0, g_th
+
+
+class MPCFunction(torch.autograd.Function):
+    """(x0 [B, nx], theta [n_p] | [B, n_p]) -> (u0 [B, nu], V [B]) through ``layer.batch``."""
+
+    @staticmethod
+    def forward(ctx, x0, theta, layer):
+        mpc: MPCBatch = layer.batch
+        need_x, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        mpc.set_theta(theta.detach().to(torch.float64))
+        r = mpc.solve(x0.detach().to(torch.float64), sens_v=need_p, sens_pi=need_p, **layer.solve_args)
+        s = mpc.state_sens(q_mode=False, value=True, policy=layer.has_policy_jacobian) if need_x else None
+        layer.last_status = r.status
+        ctx.set_materialize_grads(False)
+        ctx.shared = theta.dim() == 1
+        ctx.dtypes = (x0.dtype, theta.dtype)
+        ctx.policy = layer.has_policy_jacobian
+        ctx.jac = (r.status, None if s is None else s.dpi_dx0, None if s is None else s.dV_dx0, r.dpi_dp, r.dV_dp)
+        return r.u0.to(x0.dtype), r.V.to(x0.dtype)
+
+    @staticmethod
+    def backward(ctx, g_u, g_V):
+        status, du_dx0, dV_dx0, du_dp, dV_dp = ctx.jac
+        if g_u is not None and ctx.needs_input_grad[0] and not ctx.policy:
+            raise RuntimeError("MPCLayer: the loss depends on u0 and x0 requires a gradient, but du0*/dx0 is not available for the chain "
+                               "of masses (dV/dx0, dQ/dx0 and dQ/du0 are); detach x0 or keep u0 out of the loss.")
+        f64 = [None if g is None else g.to(torch.float64) for g in (g_u, g_V)]
+        g_x0, g_th = mpc_backward_terms(f64[0], f64[1], status, du_dx0, dV_dx0, du_dp, dV_dp, ctx.shared)
+        return (None if g_x0 is None or not ctx.needs_input_grad[0] else g_x0.to(ctx.dtypes[0]),
+                None if g_th is None or not ctx.needs_input_grad[1] else g_th.to(ctx.dtypes[1]), None)
+
+
+class MPCQFunction(torch.autograd.Function):
+    """(x0 [B, nx], u0 [B, nu], theta) -> Q [B]: the solve with u_0 pinned."""
+
+    @staticmethod
+    def forward(ctx, x0, u0, theta, layer):
+        mpc: MPCBatch = layer.batch
+        need_s, need_p = ctx.needs_input_grad[0] or ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        mpc.set_theta(theta.detach().to(torch.float64))
+        r = mpc.solve(x0.detach().to(torch.float64), u0.detach().to(torch.float64), sens_v=need_p, **layer.solve_args)
+        s = mpc.state_sens(q_mode=True, value=True, policy=False) if need_s else None
+        layer.last_status = r.status
+        ctx.set_materialize_grads(False)
+        ctx.shared = theta.dim() == 1
+        ctx.dtypes = (x0.dtype, u0.dtype, theta.dtype)
+        ctx.jac = (r.status, None if s is None else s.dV_dx0, None if s is None else s.dQ_du0, r.dV_dp)
+        return r.V.to(x0.dtype)
+
+    @staticmethod
+    def backward(ctx, g_Q):
+        status, dQ_dx0, dQ_du0, dQ_dp = ctx.jac
+        if g_Q is None:
+            return None, None, None, None
+        g_Q = g_Q.to(torch.float64)
+        g_x0, g_th = mpc_backward_terms(None, g_Q, status, None, dQ_dx0, None, dQ_dp, ctx.shared)
+        g_u0, _ = mpc_backward_terms(None, g_Q, status, None, dQ_du0, None, None, ctx.shared)
+        return tuple(g.to(dt) if need and g is not None else None
+                     for g, need, dt in zip((g_x0, g_u0, g_th), ctx.needs_input_grad[:3], ctx.dtypes)) + (None,)
+
+
+class MPCLayer(torch.nn.Module):
+    """``layer(x0, theta) -> (u0, V)`` and ``layer.q(x0, u0, theta) -> Q`` around one ``MPCBatch`` (its batch size is the layer's).
+    ``solve_args`` go to every ``MPCBatch.solve`` of the layer (e.g. ``cold=True``).  ``last_status`` [B] int32: the statuses of the
+    last forward pass."""
+
+    def __init__(self, batch: MPCBatch, **solve_args):
+        super().__init__()
+        self.batch = batch
+        self.solve_args = solve_args
+        self.has_policy_jacobian = not batch.ocp.name.startswith("chain")      # du0*/dx0: cartpole and linear system
+        self.last_status = None
+
+    def forward(self, x0: torch.Tensor, theta: torch.Tensor):
+        return MPCFunction.apply(x0, theta, self)
+
+    def q(self, x0: torch.Tensor, u0: torch.Tensor, theta: torch.Tensor) -> torch.Tensor:
+        return MPCQFunction.apply(x0, u0, theta, self)

@@ -29,6 +29,13 @@ class SolveResult:
     dpi_dp: Optional[torch.Tensor]   # [B, nu, n_p]
 
 
+@dataclass
+class StateSens:
+    dV_dx0: Optional[torch.Tensor]    # [B, nx]      dV/dx0, or dQ/dx0 when the solve had u0 fixed
+    dQ_du0: Optional[torch.Tensor]    # [B, nu]      Q mode only
+    dpi_dx0: Optional[torch.Tensor]   # [B, nu, nx]  du0*/dx0 (zeros in Q mode); cartpole and linear system
+
+
 class MPCBatch:
     """B independent instances of one OCP on one GPU.  The handle keeps the warm-start iterate of every
     instance (like the reference's solver object keeps its single iterate)."""
@@ -51,6 +58,7 @@ class MPCBatch:
         self._theta = None
         self.has_iterate = False       # a stored iterate exists (after a solve / set_iterate; cleared by reset)
         self.duals_valid = False       # ... and its bound multipliers / slacks come from a solve (not the cold placeholders)
+        self._solve_status = None      # status tensor of the solve that stored the iterate (None: the iterate was set, not solved)
         self.set_theta(torch.as_tensor(ocp.p0, dtype=torch.float64))
         self.gamma = ocp.gamma
 
@@ -130,6 +138,7 @@ class MPCBatch:
         x0t = None if x0 is None else self._dev(x0, (self.B, self.nx))
         self._call("mpcrl_reset", x0t)
         self.has_iterate = self.duals_valid = False
+        self._solve_status = None
 
     def set_order(self, perm) -> None:
         """mpcrl_set_order: perm [B], a permutation of 0..B-1 (validity is the caller's contract) — slot i of the next launches works
@@ -190,7 +199,27 @@ class MPCBatch:
         iters = torch.empty((self.B, 2), dtype=torch.int32, device=self.device)
         self._call("mpcrl_solve", x0, u0f, flags, u0_out, V, dV, dpi, status, iters)
         self.has_iterate, self.duals_valid = True, bool(store_bounds)
+        self._solve_status = status
         return SolveResult(u0_out, V, status, iters, dV, dpi)
+
+    def state_sens(self, q_mode: bool = False, value: bool = True, policy: bool = True) -> StateSens:
+        """Derivatives of the last solve with respect to its initial state and, in Q mode, its pinned first control
+        (include/mpcrl_ext.h mpcrl_state_sens), from the iterate the handle stores.  q_mode: that solve had u0 fixed.  value:
+        dV/dx0 (dQ/dx0 and dQ/du0 in Q mode).  policy: du0*/dx0 (zeros in Q mode; not available for the chain of masses).  Rows of
+        instances whose status is neither 0 nor 2 are zeros."""
+        if not (self.has_iterate and self.duals_valid):
+            raise RuntimeError("state_sens needs the iterate of a solve with its bound multipliers (solve with store_bounds=True first)")
+        kw = dict(dtype=torch.float64, device=self.device)
+        dV = torch.empty((self.B, self.nx), **kw) if value else None
+        dQ = torch.empty((self.B, self.nu), **kw) if value and q_mode else None
+        dpi = torch.empty((self.B, self.nu, self.nx), **kw) if policy else None
+        self._call("mpcrl_state_sens", _lib.STATE_Q_MODE if q_mode else 0, dV, dQ, dpi)
+        st = self._solve_status
+        if st is not None:      # the library sees the stored iterate, not the status word: a failed QP (4) is selected out here
+            good = (st == 0) | (st == 2)
+            dV, dQ, dpi = (None if t is None else torch.where(good.reshape((self.B,) + (1,) * (t.dim() - 1)), t, torch.zeros_like(t))
+                           for t in (dV, dQ, dpi))
+        return StateSens(dV, dQ, dpi)
 
     def get_action(self, x0) -> torch.Tensor:
         """Batched MPC.get_action (mpc.py:27-50)."""
@@ -219,6 +248,7 @@ class MPCBatch:
         bnd = None if bnd is None else self._dev(bnd, (self.B, 10, self.N + 1, nw))
         self._call("mpcrl_set_iterate", x, u, pi, bnd)
         self.has_iterate, self.duals_valid = True, bnd is not None
+        self._solve_status = None
 
     def _row_tables(self, x, u, pi, bnd, index):
         nw = self.nx + self.nu
@@ -240,6 +270,7 @@ class MPCBatch:
         self._row_tables(x, u, pi, bnd, index)
         self._call("mpcrl_set_iterate_rows", x, u, pi, bnd, index)
         self.has_iterate, self.duals_valid = True, bnd is not None
+        self._solve_status = None
 
     def get_lagrangian(self) -> torch.Tensor:
         """[B] Lagrangian of the mirror NLP at the iterate of the last solve (nlp.L, nlp.py:1180,1390)."""

@@ -1,0 +1,86 @@
+// mpcrl_state.hip — include/mpcrl_ext.h: state sensitivities of a solve (dV/dx0, dQ/du0, du0*/dx0) from the iterate the handle
+// stores.  The kernels are state_sens_kernel.hpp; this unit instantiates them for the cartpole, the linear system and every chain
+// size, and launches them.  Nothing here allocates or waits: two launches (or one and a memset) on the caller's stream.
+#include "mpcrl_host.hpp"
+
+#include "../../include/mpcrl_ext.h"
+#include "state_sens_kernel.hpp"
+
+using namespace mpcrl;
+
+namespace {
+
+template <class M>
+int launch_stage0(const MpcrlSolver *h, Stage0Args a, hipStream_t st) {
+    hipLaunchKernelGGL(stage0_grad_kernel<M>, dim3((unsigned)h->B), dim3(64), 0, st, a);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+template <class M>
+int launch_policy(const MpcrlSolver *h, const StateSensArgs &a, hipStream_t st) {
+    constexpr SmallTraits T = small_traits<M>();
+    const int ipw = std::min(64 / (h->N + 1), T.max_ipw);
+    const dim3 grid((unsigned)((h->B + ipw - 1) / ipw)), wave(64);
+    if constexpr (!T.seg_skip) {   // at most 32 lanes per instance: the reductions without the level at distance 32, as launch_small picks
+        if (seg_short(T, h->N)) {
+            hipLaunchKernelGGL((small_state_sens_kernel<M, true>), grid, wave, 0, st, h->small, a);
+            HIP_OK(hipGetLastError());
+            return 0;
+        }
+    }
+    hipLaunchKernelGGL((small_state_sens_kernel<M, false>), grid, wave, 0, st, h->small, a);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mpcrl_ext_version(void) { return MPCRL_EXT_VERSION; }
+
+int mpcrl_state_sens(mpcrl_handle h, int flags, double *dV_dx0, double *dQ_du0, double *dpi_dx0, void *stream) {
+    if (!h || (flags & ~MPCRL_STATE_Q_MODE)) return MPCRL_E_ARG;
+    const bool qmode = (flags & MPCRL_STATE_Q_MODE) != 0;
+    if (!h->have_iterate || h->dual_cold) return MPCRL_E_ARG;
+    if (dQ_du0 && !qmode) return MPCRL_E_ARG;
+    if (dpi_dx0 && h->is_large) return MPCRL_E_MODEL;
+    ON_DEVICE(h->device);
+    const hipStream_t st = (hipStream_t)stream;
+    if (dV_dx0 || dQ_du0) {
+        Stage0Args a;
+        a.B = h->B, a.N = h->N, a.theta_stride = h->theta_stride, a.theta = h->theta;
+        a.rk_steps = h->is_large ? h->large.rk_steps : h->small.rk_steps;
+        a.h = h->is_large ? h->large.h : h->small.h;
+        a.c0 = h->is_large ? h->large.dT : h->small.dT;   // c_0 = dT for both cost kinds
+        a.X = h->X, a.U = h->U, a.PI = h->PI, a.RES = h->RES, a.consts = h->is_large ? h->consts_dev : nullptr;
+        a.dV = dV_dx0, a.dQ = dQ_du0;
+        int rc = MPCRL_E_MODEL;
+        if (h->model == MPCRL_MODEL_CARTPOLE) rc = launch_stage0<CartpoleDev>(h, a, st);
+        else if (h->model == MPCRL_MODEL_LINEAR) rc = launch_stage0<LinearDev>(h, a, st);
+        else
+            switch (h->n_mass) {
+                case 3: rc = launch_stage0<ChainDev<3>>(h, a, st); break;
+                case 4: rc = launch_stage0<ChainDev<4>>(h, a, st); break;
+                case 5: rc = launch_stage0<ChainDev<5>>(h, a, st); break;
+                case 6: rc = launch_stage0<ChainDev<6>>(h, a, st); break;
+                case 7: rc = launch_stage0<ChainDev<7>>(h, a, st); break;
+            }
+        if (rc) return rc;
+    }
+    if (dpi_dx0) {
+        if (qmode)   // u_0 is data: du0/dx0 = 0, as du0/dp is
+            HIP_OK(hipMemsetAsync(dpi_dx0, 0, (size_t)h->B * h->nu * h->nx * sizeof(double), st));
+        else {
+            StateSensArgs a;
+            a.B = h->B, a.theta_stride = h->theta_stride, a.perm = h->have_perm ? h->perm : nullptr, a.theta = h->theta;
+            a.X = h->X, a.U = h->U, a.PI = h->PI, a.BND = h->BND, a.RES = h->RES, a.dpi = dpi_dx0;
+            const int rc = h->model == MPCRL_MODEL_LINEAR ? launch_policy<LinearDev>(h, a, st) : launch_policy<CartpoleDev>(h, a, st);
+            if (rc) return rc;
+        }
+    }
+    return 0;
+}
+
+}  // extern "C"

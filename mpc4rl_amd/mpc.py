@@ -243,6 +243,8 @@ class MPC:
         self._u0 = None
         self._last = None
         self._sens_fresh = False
+        self._state_sens = None
+        self._problem_changed = False          # a parameter, bound or the discount factor was written since the last solve
         # box bounds as the solver currently has them (stage-vector order v = [u; x]); constraints_set / nlp.set edit them
         lb, ub, lbe, ube, _, _, _ = ocp.stage_bounds()
         self._lb0, self._ub0 = lb[: ocp.nu].copy(), ub[: ocp.nu].copy()
@@ -258,6 +260,8 @@ class MPC:
         self._x0, self._u0 = x0[0].copy(), None if u0 is None else u0t[0].copy()
         self._last = r
         self._sens_fresh = sens
+        self._state_sens = None                # dV/dx0, dQ/du0, du0*/dx0 of this solve: computed on demand (_state)
+        self._problem_changed = False
         self.status = int(r.status[0].item())
         return self.status
 
@@ -265,6 +269,7 @@ class MPC:
         self._p = np.asarray(p, float).reshape(-1).copy()
         self._batch.set_theta(torch.as_tensor(self._p))
         self._sens_fresh = False
+        self._problem_changed = True
 
     def _u0_pin(self):
         """lbu_0 == ubu_0 written through constraints_set is the reference's way of pinning u_0 (Q(s, a), mpc.py:71-76)."""
@@ -289,6 +294,7 @@ class MPC:
         value = np.asarray(value, float).reshape(-1)
         lo = field.startswith("l")
         self._sens_fresh = False               # whichever bound changes, the cached sensitivities belong to the old problem
+        self._problem_changed = True
         if field in ("lbx", "ubx") and stage == 0:
             self._x0 = value.copy()
             return
@@ -341,6 +347,34 @@ class MPC:
     def get_dQ_dp(self) -> np.ndarray:                # mpc.py:126-135
         return self.get_dL_dp()
 
+    # derivatives with respect to the initial state and the pinned first control (no counterpart in the reference; include/mpcrl_ext.h)
+    def _state(self):
+        """State sensitivities at the iterate of the last update / q_update.  A parameter, bound or discount factor written since
+        then makes that iterate another problem's: it is solved again first, as get_dL_dp does."""
+        if self._last is None:
+            raise RuntimeError("state sensitivities asked for before any solve")
+        if self._state_sens is None or self._problem_changed:
+            if self._problem_changed or not self._batch.duals_valid:
+                self.update_nlp()
+            policy = not self.ocp.name.startswith("chain")      # du0*/dx0: cartpole and linear system
+            self._state_sens = self._batch.state_sens(q_mode=self._u0 is not None, value=True, policy=policy)
+        return self._state_sens
+
+    def get_dV_dx0(self) -> np.ndarray:               # -> (1, nx); dQ/dx0 after q_update
+        return self._state().dV_dx0.cpu().numpy().reshape(1, -1)
+
+    def get_dQ_du0(self) -> np.ndarray:               # -> (1, nu); after q_update only
+        s = self._state()
+        if s.dQ_du0 is None:
+            raise RuntimeError("get_dQ_du0 needs a q_update (u0 fixed) as the last solve")
+        return s.dQ_du0.cpu().numpy().reshape(1, -1)
+
+    def get_dpi_dx0(self) -> np.ndarray:              # -> (nu, nx); zeros after q_update
+        s = self._state()
+        if s.dpi_dx0 is None:
+            raise NotImplementedError("du0*/dx0 is not available for the chain of masses")
+        return s.dpi_dx0[0].cpu().numpy()
+
     def set_p(self, p: np.ndarray, finite_differences: bool = False) -> None:   # mpc.py:137-154
         self._set_p_internal(p)
 
@@ -391,6 +425,7 @@ class MPC:
         tgt = {"x": x, "u": u, "pi": pi}[field]
         tgt[0, stage] = torch.as_tensor(np.asarray(value, float).reshape(-1), device=tgt.device)
         self._batch.set_iterate(x, u, pi, bnd if duals else None)
+        self._state_sens = None
 
     def set_parameter(self, value_, api="new"):       # mpc.py:233-257
         self._set_p_internal(value_)
@@ -399,6 +434,7 @@ class MPC:
         self.discount_factor = discount_factor_
         self._batch.set_discount_factor(discount_factor_)
         self._sens_fresh = False
+        self._problem_changed = True
 
     def get(self, stage, field):                      # mpc.py:287-288
         x, u, pi, bnd, _ = self._batch.get_iterate()
