@@ -10,7 +10,8 @@
  *     dQ/du0   = grad_u l0(x0, u0)           (Q mode: the multiplier of the pin lbu_0 = ubu_0 = u0; no bound term enters)
  *     du0* / dx0                             (V mode: rows u_0 of -(dR/dz)^-1 dR/dx0 of the exact-Hessian barrier KKT system — the
  *                                             system the du0* / dp pass solves, same stiffness cap, another right-hand side)
- * du0* / dx0 exists for the cartpole and the linear system; the chain of masses has dV/dx0, dQ/dx0 and dQ/du0 only.
+ * Here du0* / dx0 exists for the cartpole and the linear system; the chain of masses has dV/dx0, dQ/dx0 and dQ/du0 from this call and
+ * its du0* / dx0 from mpcrl_chain_policy_state_sens (mpcrl_chain_ext.h).
  */
 #ifndef MPCRL_EXT_H
 #define MPCRL_EXT_H

@@ -8,8 +8,11 @@ pass is plain torch contractions of the stored Jacobians with the incoming gradi
     g_theta = g_u' du0*/dp  + g_V dV/dp          summed over the batch for a shared theta [n_p], per instance for theta [B, n_p]
     g_u0    = g_Q dQ/du0                         (``layer.q``)
 
-Instances whose solve did not end with status 0 contribute zero gradient; ``layer.last_status`` keeps the statuses.  The chain of
-masses has no du0*/dx0 yet: a loss that depends on ``u0`` cannot be back-propagated to ``x0`` there, and asking for it raises.
+Instances whose solve did not end with status 0 contribute zero gradient; ``layer.last_status`` keeps the statuses.  On the chain of
+masses du0*/dx0 is opt-in (``MPCLayer(..., policy_jacobian=True)``; include/mpcrl_chain_ext.h): the layer computes the state
+sensitivities in ``forward``, before it knows whether ``g_u`` will arrive, and there that is three more launches per forward pass
+whenever the solve itself did not run the du0*/dp pass.  Without it a loss that depends on ``u0`` cannot be back-propagated to ``x0``
+on a chain, and asking for it raises.
 """
 from __future__ import annotations
 
@@ -63,7 +66,7 @@ class MPCFunction(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         ctx.shared = theta.dim() == 1
         ctx.dtypes = (x0.dtype, theta.dtype)
-        ctx.policy = layer.has_policy_jacobian
+        ctx.policy, ctx.chain = layer.has_policy_jacobian, layer.batch.ocp.name.startswith("chain")
         ctx.jac = (r.status, None if s is None else s.dpi_dx0, None if s is None else s.dV_dx0, r.dpi_dp, r.dV_dp)
         return r.u0.to(x0.dtype), r.V.to(x0.dtype)
 
@@ -71,8 +74,12 @@ class MPCFunction(torch.autograd.Function):
     def backward(ctx, g_u, g_V):
         status, du_dx0, dV_dx0, du_dp, dV_dp = ctx.jac
         if g_u is not None and ctx.needs_input_grad[0] and not ctx.policy:
+            if not ctx.chain:
+                raise RuntimeError("MPCLayer: the loss depends on u0 and x0 requires a gradient, but the layer was built with "
+                                   "policy_jacobian=False; detach x0 or keep u0 out of the loss.")
             raise RuntimeError("MPCLayer: the loss depends on u0 and x0 requires a gradient, but du0*/dx0 is not available for the chain "
-                               "of masses (dV/dx0, dQ/dx0 and dQ/du0 are); detach x0 or keep u0 out of the loss.")
+                               "of masses (dV/dx0, dQ/dx0 and dQ/du0 are) unless the layer is built with policy_jacobian=True; detach "
+                               "x0 or keep u0 out of the loss.")
         f64 = [None if g is None else g.to(torch.float64) for g in (g_u, g_V)]
         g_x0, g_th = mpc_backward_terms(f64[0], f64[1], status, du_dx0, dV_dx0, du_dp, dV_dp, ctx.shared)
         return (None if g_x0 is None or not ctx.needs_input_grad[0] else g_x0.to(ctx.dtypes[0]),
@@ -110,14 +117,16 @@ class MPCQFunction(torch.autograd.Function):
 
 class MPCLayer(torch.nn.Module):
     """``layer(x0, theta) -> (u0, V)`` and ``layer.q(x0, u0, theta) -> Q`` around one ``MPCBatch`` (its batch size is the layer's).
-    ``solve_args`` go to every ``MPCBatch.solve`` of the layer (e.g. ``cold=True``).  ``last_status`` [B] int32: the statuses of the
-    last forward pass."""
+    ``policy_jacobian``: whether ``forward`` computes du0*/dx0 when ``x0`` needs a gradient — None = on for the cartpole and the linear
+    system, off for the chain of masses (where it costs up to three more launches per forward pass); True / False = on / off on any
+    model.  ``solve_args`` go to every ``MPCBatch.solve`` of the layer (e.g. ``cold=True``).  ``last_status`` [B] int32: the statuses
+    of the last forward pass."""
 
-    def __init__(self, batch: MPCBatch, **solve_args):
+    def __init__(self, batch: MPCBatch, policy_jacobian: Optional[bool] = None, **solve_args):
         super().__init__()
         self.batch = batch
         self.solve_args = solve_args
-        self.has_policy_jacobian = not batch.ocp.name.startswith("chain")      # du0*/dx0: cartpole and linear system
+        self.has_policy_jacobian = (not batch.ocp.name.startswith("chain")) if policy_jacobian is None else bool(policy_jacobian)
         self.last_status = None
 
     def forward(self, x0: torch.Tensor, theta: torch.Tensor):

@@ -33,7 +33,7 @@ class SolveResult:
 class StateSens:
     dV_dx0: Optional[torch.Tensor]    # [B, nx]      dV/dx0, or dQ/dx0 when the solve had u0 fixed
     dQ_du0: Optional[torch.Tensor]    # [B, nu]      Q mode only
-    dpi_dx0: Optional[torch.Tensor]   # [B, nu, nx]  du0*/dx0 (zeros in Q mode); cartpole and linear system
+    dpi_dx0: Optional[torch.Tensor]   # [B, nu, nx]  du0*/dx0 (zeros in Q mode)
 
 
 class MPCBatch:
@@ -59,6 +59,9 @@ class MPCBatch:
         self.has_iterate = False       # a stored iterate exists (after a solve / set_iterate; cleared by reset)
         self.duals_valid = False       # ... and its bound multipliers / slacks come from a solve (not the cold placeholders)
         self._solve_status = None      # status tensor of the solve that stored the iterate (None: the iterate was set, not solved)
+        self._is_chain = ocp.name.startswith("chain")
+        # chain: the handle's workspace still describes the last solve (include/mpcrl_chain_ext.h; the library keeps the same flag)
+        self._chain_ws_current = False
         self.set_theta(torch.as_tensor(ocp.p0, dtype=torch.float64))
         self.gamma = ocp.gamma
 
@@ -66,6 +69,12 @@ class MPCBatch:
         h, self._h = getattr(self, "_h", None), None
         if h:
             self.lib.mpcrl_destroy(h)      # (not through _lib.call: at interpreter exit the module may be gone before the handle)
+
+    @property
+    def chain_workspace_current(self) -> bool:
+        """Chain of masses: the handle's workspace still describes the last solve, which is what ``state_sens(policy=True)`` reads
+        there (include/mpcrl_chain_ext.h).  False on the other models, before a solve and after anything else touched the handle."""
+        return self._chain_ws_current
 
     # ------------------------------------------------------------------ helpers
     def _call(self, name: str, *args) -> int:
@@ -92,6 +101,7 @@ class MPCBatch:
             raise ValueError(f"theta must be [{self.n_p}] or [{self.B}, {self.n_p}]")
         self._theta = t
         self._call("mpcrl_set_theta", t, self.n_p, per)
+        self._chain_ws_current = False
 
     def get_theta(self) -> torch.Tensor:
         return self._theta
@@ -100,6 +110,7 @@ class MPCBatch:
         """MPC.set_discount_factor (mpc.py:259-285)."""
         self.gamma = float(gamma)
         self._call("mpcrl_set_gamma", float(gamma))
+        self._chain_ws_current = False
 
     def set_options(self, tol: float = -1.0, max_iter: int = -1) -> None:
         self._call("mpcrl_set_options", float(tol), int(max_iter))
@@ -131,6 +142,7 @@ class MPCBatch:
         if lb.shape[0] != n or ub.shape[0] != n:
             raise ValueError(f"bounds of kind {which} have {n} entries")
         self._call("mpcrl_set_bounds", int(which), lb.ctypes.data, ub.ctypes.data)     # (host arrays of float64)
+        self._chain_ws_current = False
 
     def reset(self, x0=None) -> None:
         """MPC.reset (mpc.py:204-210): the next solve starts from x_k = x0, u = 0, multipliers 0.  With x0 ([B, nx]) the stored
@@ -139,6 +151,7 @@ class MPCBatch:
         self._call("mpcrl_reset", x0t)
         self.has_iterate = self.duals_valid = False
         self._solve_status = None
+        self._chain_ws_current = False
 
     def set_order(self, perm) -> None:
         """mpcrl_set_order: perm [B], a permutation of 0..B-1 (validity is the caller's contract) — slot i of the next launches works
@@ -200,20 +213,32 @@ class MPCBatch:
         self._call("mpcrl_solve", x0, u0f, flags, u0_out, V, dV, dpi, status, iters)
         self.has_iterate, self.duals_valid = True, bool(store_bounds)
         self._solve_status = status
+        self._chain_ws_current = self._is_chain
         return SolveResult(u0_out, V, status, iters, dV, dpi)
 
     def state_sens(self, q_mode: bool = False, value: bool = True, policy: bool = True) -> StateSens:
         """Derivatives of the last solve with respect to its initial state and, in Q mode, its pinned first control
         (include/mpcrl_ext.h mpcrl_state_sens), from the iterate the handle stores.  q_mode: that solve had u0 fixed.  value:
-        dV/dx0 (dQ/dx0 and dQ/du0 in Q mode).  policy: du0*/dx0 (zeros in Q mode; not available for the chain of masses).  Rows of
-        instances whose status is neither 0 nor 2 are zeros."""
+        dV/dx0 (dQ/dx0 and dQ/du0 in Q mode).  policy: du0*/dx0 (zeros in Q mode).  On the chain of masses the policy part comes
+        from the workspace of the last solve (include/mpcrl_chain_ext.h mpcrl_chain_policy_state_sens: one launch after a solve with
+        sens_pi, four otherwise) and needs that solve to be the last thing that touched the handle: a set_theta, set_bounds,
+        set_discount_factor, reset or set_iterate in between raises.  Rows of instances whose status is neither 0 nor 2 are zeros."""
         if not (self.has_iterate and self.duals_valid):
             raise RuntimeError("state_sens needs the iterate of a solve with its bound multipliers (solve with store_bounds=True first)")
         kw = dict(dtype=torch.float64, device=self.device)
         dV = torch.empty((self.B, self.nx), **kw) if value else None
         dQ = torch.empty((self.B, self.nu), **kw) if value and q_mode else None
         dpi = torch.empty((self.B, self.nu, self.nx), **kw) if policy else None
-        self._call("mpcrl_state_sens", _lib.STATE_Q_MODE if q_mode else 0, dV, dQ, dpi)
+        flags = _lib.STATE_Q_MODE if q_mode else 0
+        if self._is_chain and policy:
+            if not self._chain_ws_current or self._solve_status is None:
+                raise RuntimeError("state_sens(policy=True) on the chain of masses reads the workspace of the last solve, and the handle "
+                                   "was changed since (set_theta, set_bounds, set_discount_factor, reset or set_iterate): solve again first")
+            if value:
+                self._call("mpcrl_state_sens", flags, dV, dQ, None)
+            self._call("mpcrl_chain_policy_state_sens", flags, self._solve_status, dpi)
+        else:
+            self._call("mpcrl_state_sens", flags, dV, dQ, dpi)
         st = self._solve_status
         if st is not None:      # the library sees the stored iterate, not the status word: a failed QP (4) is selected out here
             good = (st == 0) | (st == 2)
@@ -249,6 +274,7 @@ class MPCBatch:
         self._call("mpcrl_set_iterate", x, u, pi, bnd)
         self.has_iterate, self.duals_valid = True, bnd is not None
         self._solve_status = None
+        self._chain_ws_current = False
 
     def _row_tables(self, x, u, pi, bnd, index):
         nw = self.nx + self.nu
@@ -271,6 +297,7 @@ class MPCBatch:
         self._call("mpcrl_set_iterate_rows", x, u, pi, bnd, index)
         self.has_iterate, self.duals_valid = True, bnd is not None
         self._solve_status = None
+        self._chain_ws_current = False
 
     def get_lagrangian(self) -> torch.Tensor:
         """[B] Lagrangian of the mirror NLP at the iterate of the last solve (nlp.L, nlp.py:1180,1390)."""

@@ -56,6 +56,30 @@ int launch_large(MpcrlSolver *h, LargeArgs a, hipStream_t st) {
     return 0;
 }
 
+// du0*/dx0 of the handle's last solve (include/mpcrl_chain_ext.h).  With the exact Hessians and the adjoint solutions of that solve
+// in the workspace: the contraction alone.  Otherwise the adjoint pipeline first, launched as launch_large launches it on the stored
+// iterate, without the parameter terms (chain_sens_th2, chain_sens_mix2 and chain_sens_out do not run).
+template <class M>
+int launch_policy_state_sens(MpcrlSolver *h, const int32_t *status, double *dpi_dx0, bool adjoint_current, hipStream_t st) {
+    const int B = h->B, N = h->N;
+    const LargeLds<M> lds(N);
+    if (!lds.fits()) return MPCRL_E_ARG;   // (mpcrl_create has checked: not reached)
+    LargeArgs a{};
+    a.B = B, a.theta_stride = h->theta_stride, a.theta = h->theta;
+    a.X = h->X, a.U = h->U, a.PI = h->PI, a.BND = h->BND, a.RES = h->RES, a.LAG = h->LAG;
+    a.ws = h->ws, a.ws_stride = h->ws_stride, a.status = const_cast<int32_t *>(status);
+    // what chain_sens_riccati_kernel's guard asks for: the policy pass in V mode.  It writes nothing through a.dpi (chain_sens_out does)
+    a.flags = MPCRL_SENS_PI, a.dpi = dpi_dx0, a.u0fix = nullptr;
+    if (!adjoint_current) {
+        hipLaunchKernelGGL((chain_point_kernel<M, true>), dim3((unsigned)B), dim3(64), lds.point, st, h->large, a);
+        hipLaunchKernelGGL(chain_sens_ad_kernel<M>, dim3((unsigned)(B * HexCfg<M>::groups(N))), dim3(64), 0, st, h->large, a);
+        hipLaunchKernelGGL(chain_sens_riccati_kernel<M>, dim3(B), dim3(64), lds.sqp, st, h->large, a);
+    }
+    hipLaunchKernelGGL(chain_state_sens_kernel<M>, dim3((unsigned)B), dim3(64), 0, st, h->large, a, dpi_dx0);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 size_t ws_doubles(int N) { return LargeLayout<Model>(N).total; }
 bool lds_fits(int N) { return LargeLds<Model>(N).fits(); }
 
@@ -78,6 +102,7 @@ constexpr int (*debug_phases)(unsigned long long *, int) = nullptr;
 #define MPCRL_CAT_(a, b) a##b
 #define MPCRL_CAT(a, b) MPCRL_CAT_(a, b)
 const MpcrlChainEntry *MPCRL_CAT(mpcrl_chain_entry_, MPCRL_CHAIN_NMASS)() {
-    static const MpcrlChainEntry e = {MPCRL_CHAIN_NMASS, (long)Model::NP, ws_doubles, lds_fits, launch_large<Model>, debug_phases};
+    static const MpcrlChainEntry e = {MPCRL_CHAIN_NMASS, (long)Model::NP, ws_doubles, lds_fits, launch_large<Model>, debug_phases,
+                                     launch_policy_state_sens<Model>};
     return &e;
 }

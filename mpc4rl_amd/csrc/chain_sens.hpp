@@ -280,6 +280,8 @@ __global__ void __launch_bounds__(64, 1) chain_sens_riccati_kernel(const LargeSp
     const int ne = (N + 1) * NW;
     const double *th = S.th, *xs = sp.consts;
     const WsArr Hex{(char *)w, (unsigned)lay.Hex};
+    // (launch_policy_state_sens, chain_inst.hip, passes this guard with a.dpi = its [B, nu, nx] output as a non-null token: neither this
+    // kernel nor the two in front of it may ever write through a.dpi — only chain_sens_out does, and that launcher does not run it)
     if (!((a.flags & 2) && a.dpi) || S.qmode) return;
     for (int e = lane; e < NW * NW; e += NT) Hex[N * NW * NW + e] = S.ck(N) * M::hess(true, e / NW, e % NW, th);
     // barrier diagonal from the final (lam, t) of the bound rows (slacks are constants of the mirror, quirk q1), capped as in the small
@@ -520,6 +522,57 @@ __global__ void __launch_bounds__(1024) chain_sens_out_kernel(const LargeSpec sp
         else
             a.dpi[((size_t)inst * NU + iu) * NP + pidx] = sens_ok ? -acc : NAN;
     }
+}
+
+// du0*/dx0 (include/mpcrl_chain_ext.h) from what chain_sens_riccati_kernel left in the workspace: with x_0 eliminated, x0 enters the
+// KKT system through the control rows of stage 0 (Hex_0[u, x] x_0) and through dynamics row 0 (A_0 x_0), so with the adjoint solution
+// (y_u, y_nu) of right-hand side e_iu as forward2_sens stores it
+//     du0*/dx0 [iu][j] = -( sum_c Ydu[iu][0 NU + c] Hex_0[u_c, x_j] + sum_r Ydnu[iu][1 NX + r] A_0[r, j] )
+// — the contraction chain_sens_mix2 / chain_sens_out do for a parameter, with x0 in its place (Ydnu[(k + 1) NX + .] is the adjoint of
+// dynamics row k).  No state row of stage 0 carries a barrier term (x_0 is data); the stiffness cap sits in the factorisation.
+// ONE WAVEFRONT PER INSTANCE, lane j = state column: the NU + NX operand rows (the x columns of rows u of Hex_0 and of [B A]_0) are
+// read coalesced, the NU (NU + NX) adjoint entries are staged in LDS and read as broadcasts; every sum runs in one fixed order (the
+// rows in sequence on one lane), so the same workspace gives the same bits.  Every row of the output is written by every call: the
+// values for status 0 / 2, zeros otherwise, NaN where the factorisation was not positive definite (as chain_sens_out does for dpi_dp).
+template <class M>
+__global__ void __launch_bounds__(64) chain_state_sens_kernel(const LargeSpec sp, const LargeArgs a, double *__restrict__ out) {
+    constexpr int NX = M::NX, NU = M::NU, NW = NX + NU, NY = NU + NX;
+    static_assert(NX <= 64, "one state column per lane");
+    __shared__ double y[NU * NY];
+    const int N = sp.N, inst = blockIdx.x, lane = threadIdx.x;
+    double *o = out + (size_t)inst * NU * NX;
+    const int status = a.status[inst];
+    if (!(status == 0 || status == 2)) {
+        for (int e = lane; e < NU * NX; e += 64) o[e] = 0.0;
+        return;
+    }
+    const LargeLayout<M> lay(N);
+    const double *w = a.ws + (size_t)inst * a.ws_stride;
+    const double *Ydu = w + lay.Ydu, *Ydnu = w + lay.Ydnu + NX, *Hex0 = w + lay.Hex, *BA0 = w + lay.BA;
+    for (int e = lane; e < NU * NY; e += 64) {
+        const int iu = e / NY, c = e - iu * NY;
+        y[e] = c < NU ? Ydu[(size_t)iu * N * NU + c] : Ydnu[(size_t)iu * (N + 1) * NX + (c - NU)];
+    }
+    const bool sens_ok = w[lay.state + ST_STATUS] == 0.0;
+    wave_sync();
+    if (lane >= NX) return;
+    double acc[NU];
+#pragma unroll
+    for (int iu = 0; iu < NU; ++iu) acc[iu] = 0.0;
+#pragma unroll
+    for (int c = 0; c < NU; ++c) {
+        const double hv = Hex0[c * NW + NU + lane];
+#pragma unroll
+        for (int iu = 0; iu < NU; ++iu) acc[iu] = fma(y[iu * NY + c], hv, acc[iu]);
+    }
+#pragma unroll
+    for (int r = 0; r < NX; ++r) {      // (unrolled: the NX row loads are in flight together)
+        const double av = BA0[r * NW + NU + lane];
+#pragma unroll
+        for (int iu = 0; iu < NU; ++iu) acc[iu] = fma(y[iu * NY + NU + r], av, acc[iu]);
+    }
+#pragma unroll
+    for (int iu = 0; iu < NU; ++iu) o[iu * NX + lane] = sens_ok ? -acc[iu] : NAN;
 }
 
 }  // namespace mpcrl

@@ -70,18 +70,6 @@ int fill_large_spec(const MpcrlProblemSpec &s, LargeSpec &d) {
     return 0;
 }
 
-// n_mass (3 .. 7, a free integer in the reference: rlmpc/mpc/chain_mass/ocp_utils.py:344-350) -> the translation unit of that chain size
-const MpcrlChainEntry *chain_entry(int n_mass) {
-    switch (n_mass) {
-        case 3: return mpcrl_chain_entry_3();
-        case 4: return mpcrl_chain_entry_4();
-        case 5: return mpcrl_chain_entry_5();
-        case 6: return mpcrl_chain_entry_6();
-        case 7: return mpcrl_chain_entry_7();
-        default: return nullptr;
-    }
-}
-
 inline void tuner_harvest(MpcrlSolver::Tuner &t) {   // probes that have finished since the last look (never waits)
     for (int m = 0; m < 2; ++m)
         if (t.pending[m] && hipEventQuery(t.ev[m][1]) == hipSuccess) {
@@ -370,12 +358,14 @@ int mpcrl_set_theta(mpcrl_handle h, const double *theta, int n_theta, int per_in
     ON_DEVICE(h->device);
     const size_t n = (size_t)h->np * (per_instance ? h->B : 1);
     HIP_OK(hipMemcpyAsync(h->theta, theta, n * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    h->chain_ws_current = h->chain_adjoint_current = false;   // (mpcrl_chain_ext.h: the workspace no longer describes the handle's state)
     h->theta_stride = per_instance ? h->np : 0;
     return 0;
 }
 
 int mpcrl_set_gamma(mpcrl_handle h, double gamma) {
     if (!h) return MPCRL_E_ARG;
+    h->chain_ws_current = h->chain_adjoint_current = false;   // (mpcrl_chain_ext.h: the workspace no longer describes the handle's state)
     h->small.gamma = gamma, h->large.gamma = gamma;
     return 0;
 }
@@ -481,6 +471,7 @@ int mpcrl_set_bounds(mpcrl_handle h, int which, const double *lb, const double *
     if (which == MPCRL_BOUNDS_STAGE && !h->is_large)   // a soft bound must stay a two-sided bound (its slack rows exist for both sides)
         for (int i = 0; i < n; ++i)
             if (h->small.soft[i] && (lb[i] <= -MPCRL_NO_BOUND * 0.1 || ub[i] >= MPCRL_NO_BOUND * 0.1)) return MPCRL_E_ARG;
+    h->chain_ws_current = h->chain_adjoint_current = false;   // (mpcrl_chain_ext.h: the workspace no longer describes the handle's state)
     for (int i = 0; i < n; ++i) dl[i] = lb[i], du[i] = ub[i];
     refresh_box_rows(h);
     return 0;
@@ -497,6 +488,7 @@ int mpcrl_reset(mpcrl_handle h, const double *x0, void *stream) {
     // the next solve builds the cold iterate itself from ITS x0 (MPCRL_COLD); the stored arrays are set to the same state so
     // that get_iterate / set_iterate after a reset see the cold iterate and not the previous solution
     int rc = fill_cold_iterate(h, x0, true, (hipStream_t)stream);
+    h->chain_ws_current = h->chain_adjoint_current = false;   // (mpcrl_chain_ext.h: the workspace no longer describes the handle's state)
     h->have_iterate = false, h->dual_cold = false;
     return rc;
 }
@@ -535,6 +527,7 @@ int mpcrl_solve(mpcrl_handle h, const double *x0, const double *u0_fixed, int fl
         rc = launch_small(h, a, st);   // (mpcrl_create admits no other model: cartpole or the linear system)
     // (a solve that left the bound planes alone: the next one must not start its interior point from them)
     if (!rc) h->have_iterate = true, h->dual_cold = (flags & MPCRL_NO_BND_STORE) != 0;
+    if (!rc && h->is_large) h->chain_ws_current = true, h->chain_adjoint_current = a.dpi && !a.u0fix;
     return rc;
 }
 
@@ -572,6 +565,7 @@ int mpcrl_set_iterate(mpcrl_handle h, const double *x, const double *u, const do
         int rc = fill_cold_iterate(h, nullptr, false, st);
         if (rc) return rc;
     }
+    h->chain_ws_current = h->chain_adjoint_current = false;   // (mpcrl_chain_ext.h: the workspace no longer describes the handle's state)
     h->have_iterate = true, h->dual_cold = bnd == nullptr;
     return 0;
 }
@@ -598,6 +592,7 @@ int mpcrl_set_iterate_rows(mpcrl_handle h, const double *x, const double *u, con
     hipLaunchKernelGGL(iterate_rows_kernel<true>, dim3((unsigned)h->B), dim3(256), 0, st, h->X, h->U, h->PI, h->BND, (double *)x, (double *)u, (double *)pi,
                        (double *)bnd, (const long *)index, (N + 1) * nx, N * nu, N * nx, 10 * (N + 1) * nw);
     HIP_OK(hipGetLastError());
+    h->chain_ws_current = h->chain_adjoint_current = false;   // (mpcrl_chain_ext.h: the workspace no longer describes the handle's state)
     h->have_iterate = true, h->dual_cold = bnd == nullptr;
     return 0;
 }

@@ -47,6 +47,9 @@ struct MpcrlSolver {
     int planned = -1;           // what mpcrl_query_time_sliced promised for the next solve (-1: nothing promised)
     bool have_iterate = false;
     bool dual_cold = false;   // the stored bound multipliers are placeholders (set_iterate without bnd): next solve = MPCRL_COLD_DUAL
+    // chain (include/mpcrl_chain_ext.h): the workspace still describes the last solve (its linearisation, multipliers and bound rows
+    // at the stored iterate) / and also holds that solve's exact Hessians and adjoint solutions (V mode with MPCRL_SENS_PI)
+    bool chain_ws_current = false, chain_adjoint_current = false;
 };
 
 #define HIP_OK(expr)                                                                          \
@@ -66,8 +69,22 @@ struct MpcrlChainEntry {
     bool (*fits)(int N);                                            // every dynamic-LDS request of the kernels fits one workgroup
     int (*launch)(MpcrlSolver *h, LargeArgs a, hipStream_t st);     // init + SQP (+ sensitivity) launches of one mpcrl_solve
     int (*debug_phases)(unsigned long long *out16, int reset);      // -DMPCRL_PROFILE_PHASES builds: the unit's phase ticks (else null)
+    // du0*/dx0 of the last solve (mpcrl_chain_policy_state_sens): the contraction alone, or the adjoint pipeline in front of it
+    int (*policy_state_sens)(MpcrlSolver *h, const int32_t *status, double *dpi_dx0, bool adjoint_current, hipStream_t st);
 };
 const MpcrlChainEntry *mpcrl_chain_entry_3(), *mpcrl_chain_entry_4(), *mpcrl_chain_entry_5(), *mpcrl_chain_entry_6(), *mpcrl_chain_entry_7();
+// n_mass (3 .. 7, a free integer in the reference: rlmpc/mpc/chain_mass/ocp_utils.py:344-350) -> the translation unit of that chain size
+// (the one table: mpcrl_api.hip and mpcrl_state.hip both go through it)
+inline const MpcrlChainEntry *chain_entry(int n_mass) {
+    switch (n_mass) {
+        case 3: return mpcrl_chain_entry_3();
+        case 4: return mpcrl_chain_entry_4();
+        case 5: return mpcrl_chain_entry_5();
+        case 6: return mpcrl_chain_entry_6();
+        case 7: return mpcrl_chain_entry_7();
+        default: return nullptr;
+    }
+}
 
 // switches to the handle's device for the duration of a call and restores the caller's device afterwards
 struct DeviceGuard {

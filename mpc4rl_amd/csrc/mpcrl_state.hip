@@ -1,9 +1,10 @@
 // mpcrl_state.hip — include/mpcrl_ext.h: state sensitivities of a solve (dV/dx0, dQ/du0, du0*/dx0) from the iterate the handle
-// stores.  The kernels are state_sens_kernel.hpp; this unit instantiates them for the cartpole, the linear system and every chain
+// stores; include/mpcrl_chain_ext.h: du0*/dx0 of the chain, from the workspace of its last solve (kernels and launches: chain_sens.hpp,
+// chain_inst.hip).  The kernels are state_sens_kernel.hpp; this unit instantiates them for the cartpole, the linear system and every chain
 // size, and launches them.  Nothing here allocates or waits: two launches (or one and a memset) on the caller's stream.
 #include "mpcrl_host.hpp"
 
-#include "../../include/mpcrl_ext.h"
+#include "../../include/mpcrl_chain_ext.h"
 #include "state_sens_kernel.hpp"
 
 using namespace mpcrl;
@@ -81,6 +82,23 @@ int mpcrl_state_sens(mpcrl_handle h, int flags, double *dV_dx0, double *dQ_du0, 
         }
     }
     return 0;
+}
+
+int mpcrl_chain_ext_version(void) { return MPCRL_CHAIN_EXT_VERSION; }
+
+int mpcrl_chain_policy_state_sens(mpcrl_handle h, int flags, const int32_t *status, double *dpi_dx0, void *stream) {
+    if (!h || (flags & ~MPCRL_STATE_Q_MODE) || !status || !dpi_dx0) return MPCRL_E_ARG;
+    if (!h->is_large) return MPCRL_E_MODEL;
+    if (!h->chain_ws_current) return MPCRL_E_ARG;
+    const MpcrlChainEntry *e = chain_entry(h->n_mass);
+    if (!e) return MPCRL_E_MODEL;
+    ON_DEVICE(h->device);
+    const hipStream_t st = (hipStream_t)stream;
+    if (flags & MPCRL_STATE_Q_MODE) {   // u_0 is data: du0/dx0 = 0, as du0/dp is
+        HIP_OK(hipMemsetAsync(dpi_dx0, 0, (size_t)h->B * h->nu * h->nx * sizeof(double), st));
+        return 0;
+    }
+    return e->policy_state_sens(h, status, dpi_dx0, h->chain_adjoint_current, st);
 }
 
 }  // extern "C"

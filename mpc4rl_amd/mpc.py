@@ -244,6 +244,7 @@ class MPC:
         self._last = None
         self._sens_fresh = False
         self._state_sens = None
+        self._chain_dpi_dx0 = None
         self._problem_changed = False          # a parameter, bound or the discount factor was written since the last solve
         # box bounds as the solver currently has them (stage-vector order v = [u; x]); constraints_set / nlp.set edit them
         lb, ub, lbe, ube, _, _, _ = ocp.stage_bounds()
@@ -261,6 +262,7 @@ class MPC:
         self._last = r
         self._sens_fresh = sens
         self._state_sens = None                # dV/dx0, dQ/du0, du0*/dx0 of this solve: computed on demand (_state)
+        self._chain_dpi_dx0 = None             # chain: du0*/dx0 of this solve, computed on demand (get_dpi_dx0)
         self._problem_changed = False
         self.status = int(r.status[0].item())
         return self.status
@@ -356,7 +358,7 @@ class MPC:
         if self._state_sens is None or self._problem_changed:
             if self._problem_changed or not self._batch.duals_valid:
                 self.update_nlp()
-            policy = not self.ocp.name.startswith("chain")      # du0*/dx0: cartpole and linear system
+            policy = not self.ocp.name.startswith("chain")      # du0*/dx0 of the chain: get_dpi_dx0 alone fetches it (its own launches)
             self._state_sens = self._batch.state_sens(q_mode=self._u0 is not None, value=True, policy=policy)
         return self._state_sens
 
@@ -370,10 +372,20 @@ class MPC:
         return s.dQ_du0.cpu().numpy().reshape(1, -1)
 
     def get_dpi_dx0(self) -> np.ndarray:              # -> (nu, nx); zeros after q_update
-        s = self._state()
-        if s.dpi_dx0 is None:
-            raise NotImplementedError("du0*/dx0 is not available for the chain of masses")
-        return s.dpi_dx0[0].cpu().numpy()
+        if not self.ocp.name.startswith("chain"):
+            return self._state().dpi_dx0[0].cpu().numpy()
+        # chain of masses (include/mpcrl_chain_ext.h): from the workspace of the last solve, fetched here alone and cached on its own,
+        # so that get_dV_dx0 / get_dQ_du0 stay the one launch they were
+        if self._last is None:
+            raise RuntimeError("state sensitivities asked for before any solve")
+        if self._chain_dpi_dx0 is None or self._problem_changed:
+            if self._problem_changed or not self._batch.duals_valid:
+                self.update_nlp()
+            if not self._batch.chain_workspace_current:
+                raise RuntimeError("get_dpi_dx0 on the chain of masses reads the workspace of the last solve, and the stored iterate was "
+                                   "edited since (set): call update / q_update again first")
+            self._chain_dpi_dx0 = self._batch.state_sens(q_mode=self._u0 is not None, value=False, policy=True).dpi_dx0
+        return self._chain_dpi_dx0[0].cpu().numpy()
 
     def set_p(self, p: np.ndarray, finite_differences: bool = False) -> None:   # mpc.py:137-154
         self._set_p_internal(p)
@@ -426,6 +438,7 @@ class MPC:
         tgt[0, stage] = torch.as_tensor(np.asarray(value, float).reshape(-1), device=tgt.device)
         self._batch.set_iterate(x, u, pi, bnd if duals else None)
         self._state_sens = None
+        self._chain_dpi_dx0 = None
 
     def set_parameter(self, value_, api="new"):       # mpc.py:233-257
         self._set_p_internal(value_)
