@@ -9,7 +9,7 @@ classes without ``libmpcrl_hip.so`` raises.
 """
 from .problems import OcpDescription, cartpole_ocp, chain_mass_ocp, linear_system_ocp  # noqa: F401
 from .batch import MPCBatch, SolveResult, StateSens  # noqa: F401
-from .autograd import MPCFunction, MPCLayer, MPCQFunction, mpc_backward_terms  # noqa: F401
+from .autograd import MPCFunction, MPCLayer, MPCQFunction, MPCTrajectoryFunction, mpc_backward_terms  # noqa: F401
 from .envs import BatchedCartPoleSwingUpEnv, BatchedChainMassEnv, BatchedLinearSystemEnv  # noqa: F401
 from .qlearning import BatchedQLearning, qlearning_gn_box_step, qlearning_gn_step, qlearning_gn_terms  # noqa: F401
 from .qlearning_cartpole import CartpoleEpisodeStats, CartpoleQLearning, qlearning_td_terms  # noqa: F401

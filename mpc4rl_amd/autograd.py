@@ -13,6 +13,14 @@ masses du0*/dx0 is opt-in (``MPCLayer(..., policy_jacobian=True)``; include/mpcr
 sensitivities in ``forward``, before it knows whether ``g_u`` will arrive, and there that is three more launches per forward pass
 whenever the solve itself did not run the du0*/dp pass.  Without it a loss that depends on ``u0`` cannot be back-propagated to ``x0``
 on a chain, and asking for it raises.
+
+``X, U = layer.trajectory(x0, theta)`` returns the whole plan X* [B, N+1, nx], U* [B, N, nu] (cartpole and linear system).  Its forward
+pass is one plain solve — no sensitivity pass — and its backward pass one ``mpcrl_traj_vjp`` (include/mpcrl_traj_ext.h) with the incoming
+(g_X, g_U): one adjoint solve per instance whatever the horizon.  That call reads the iterate the handle stores, so the iterate must
+still be that forward pass's: every ``forward``, ``q`` and ``trajectory`` of a layer increments the layer's pass counter, and
+``backward`` raises a RuntimeError when the counter is no longer the one its forward pass recorded ("one backward per forward, before
+the layer runs again").  Setters called on the batch directly (``set_theta``, ``set_iterate``, ``reset``, ``solve`` ...) between the
+forward and the backward pass are the caller's responsibility: the layer does not see them.
 """
 from __future__ import annotations
 
@@ -115,8 +123,43 @@ class MPCQFunction(torch.autograd.Function):
                      for g, need, dt in zip((g_x0, g_u0, g_th), ctx.needs_input_grad[:3], ctx.dtypes)) + (None,)
 
 
+class MPCTrajectoryFunction(torch.autograd.Function):
+    """(x0 [B, nx], theta [n_p] | [B, n_p]) -> (X [B, N+1, nx], U [B, N, nu]) through ``layer.batch``; ``backward`` is one
+    ``MPCBatch.trajectory_vjp`` on the iterate that forward pass left in the handle (the layer's pass counter guards it)."""
+
+    @staticmethod
+    def forward(ctx, x0, theta, layer):
+        mpc = layer.batch
+        mpc.set_theta(theta.detach().to(torch.float64))
+        r = mpc.solve(x0.detach().to(torch.float64), **layer.solve_args)
+        X, U = mpc.get_iterate()[:2]
+        layer.last_status = r.status
+        ctx.set_materialize_grads(False)
+        ctx.layer, ctx.pass_id = layer, layer.pass_counter
+        ctx.shared = theta.dim() == 1
+        ctx.dtypes = (x0.dtype, theta.dtype)
+        return X.to(x0.dtype), U.to(x0.dtype)
+
+    @staticmethod
+    def backward(ctx, g_X, g_U):
+        need_x, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if (g_X is None and g_U is None) or not (need_x or need_p):
+            return None, None, None
+        if ctx.layer.pass_counter != ctx.pass_id:
+            raise RuntimeError("MPCLayer.trajectory: the backward pass reads the iterate its forward pass stored in the handle, and the "
+                               "layer has run another forward, q or trajectory since (pass counter "
+                               f"{ctx.layer.pass_counter}, recorded {ctx.pass_id}): one backward per forward, before the layer runs again.")
+        g_x0, g_th = ctx.layer.batch.trajectory_vjp(None if g_X is None else g_X.to(torch.float64),
+                                                    None if g_U is None else g_U.to(torch.float64), x0=need_x, theta=need_p)
+        if g_th is not None and ctx.shared:
+            g_th = g_th.sum(0)
+        return (None if g_x0 is None else g_x0.to(ctx.dtypes[0]), None if g_th is None else g_th.to(ctx.dtypes[1]), None)
+
+
 class MPCLayer(torch.nn.Module):
-    """``layer(x0, theta) -> (u0, V)`` and ``layer.q(x0, u0, theta) -> Q`` around one ``MPCBatch`` (its batch size is the layer's).
+    """``layer(x0, theta) -> (u0, V)``, ``layer.q(x0, u0, theta) -> Q`` and ``layer.trajectory(x0, theta) -> (X, U)`` around one
+    ``MPCBatch`` (its batch size is the layer's).  ``pass_counter``: incremented by each of the three (the staleness rule of
+    ``trajectory``'s backward pass, see the module's docstring).
     ``policy_jacobian``: whether ``forward`` computes du0*/dx0 when ``x0`` needs a gradient — None = on for the cartpole and the linear
     system, off for the chain of masses (where it costs up to three more launches per forward pass); True / False = on / off on any
     model.  ``solve_args`` go to every ``MPCBatch.solve`` of the layer (e.g. ``cold=True``).  ``last_status`` [B] int32: the statuses
@@ -128,9 +171,16 @@ class MPCLayer(torch.nn.Module):
         self.solve_args = solve_args
         self.has_policy_jacobian = (not batch.ocp.name.startswith("chain")) if policy_jacobian is None else bool(policy_jacobian)
         self.last_status = None
+        self.pass_counter = 0
 
     def forward(self, x0: torch.Tensor, theta: torch.Tensor):
+        self.pass_counter += 1
         return MPCFunction.apply(x0, theta, self)
 
     def q(self, x0: torch.Tensor, u0: torch.Tensor, theta: torch.Tensor) -> torch.Tensor:
+        self.pass_counter += 1
         return MPCQFunction.apply(x0, u0, theta, self)
+
+    def trajectory(self, x0: torch.Tensor, theta: torch.Tensor):
+        self.pass_counter += 1
+        return MPCTrajectoryFunction.apply(x0, theta, self)

@@ -59,6 +59,7 @@ class MPCBatch:
         self.has_iterate = False       # a stored iterate exists (after a solve / set_iterate; cleared by reset)
         self.duals_valid = False       # ... and its bound multipliers / slacks come from a solve (not the cold placeholders)
         self._solve_status = None      # status tensor of the solve that stored the iterate (None: the iterate was set, not solved)
+        self._solve_q_mode = False     # ... and whether that solve had u0 fixed
         self._is_chain = ocp.name.startswith("chain")
         # chain: the handle's workspace still describes the last solve (include/mpcrl_chain_ext.h; the library keeps the same flag)
         self._chain_ws_current = False
@@ -213,6 +214,7 @@ class MPCBatch:
         self._call("mpcrl_solve", x0, u0f, flags, u0_out, V, dV, dpi, status, iters)
         self.has_iterate, self.duals_valid = True, bool(store_bounds)
         self._solve_status = status
+        self._solve_q_mode = u0f is not None
         self._chain_ws_current = self._is_chain
         return SolveResult(u0_out, V, status, iters, dV, dpi)
 
@@ -245,6 +247,34 @@ class MPCBatch:
             dV, dQ, dpi = (None if t is None else torch.where(good.reshape((self.B,) + (1,) * (t.dim() - 1)), t, torch.zeros_like(t))
                            for t in (dV, dQ, dpi))
         return StateSens(dV, dQ, dpi)
+
+    def trajectory_vjp(self, gX=None, gU=None, x0: bool = True, theta: bool = True):
+        """(g_x0 [B, nx] or None, g_theta [B, n_p] or None): the cotangents gX [B, N+1, nx] on X* and gU [B, N, nu] on U* of the last
+        solve (None = zeros, not both) pulled back to its initial state and its parameters by one adjoint solve per instance
+        (include/mpcrl_traj_ext.h mpcrl_traj_vjp), from the iterate the handle stores.  g_theta is zero at the entries of theta the
+        sensitivity pass does not differentiate (the cartpole's cost block).  Rows of instances whose status is not 0 are zeros.
+        Cartpole and linear system, after a solve without u0."""
+        if self._is_chain:
+            raise RuntimeError("trajectory_vjp is not available for the chain of masses")
+        if not (self.has_iterate and self.duals_valid):
+            raise RuntimeError("trajectory_vjp needs the iterate of a solve with its bound multipliers (solve with store_bounds=True first)")
+        if self._solve_status is not None and self._solve_q_mode:
+            raise RuntimeError("trajectory_vjp after a solve with u0 fixed (Q mode) is not available")
+        if gX is None and gU is None:
+            raise ValueError("trajectory_vjp needs a cotangent: gX, gU or both")
+        if not (x0 or theta):
+            raise ValueError("trajectory_vjp needs an output: x0, theta or both")
+        gX = None if gX is None else self._dev(gX, (self.B, self.N + 1, self.nx))
+        gU = None if gU is None else self._dev(gU, (self.B, self.N, self.nu))
+        kw = dict(dtype=torch.float64, device=self.device)
+        g_x0 = torch.empty((self.B, self.nx), **kw) if x0 else None
+        g_th = torch.empty((self.B, self.n_p), **kw) if theta else None
+        self._call("mpcrl_traj_vjp", 0, gX, gU, g_x0, g_th)
+        st = self._solve_status
+        if st is not None:      # as in state_sens: the library sees the stored iterate, not the status word
+            good = (st == 0).reshape(self.B, 1)
+            g_x0, g_th = (None if t is None else torch.where(good, t, torch.zeros_like(t)) for t in (g_x0, g_th))
+        return g_x0, g_th
 
     def get_action(self, x0) -> torch.Tensor:
         """Batched MPC.get_action (mpc.py:27-50)."""

@@ -5,7 +5,9 @@
 #include "mpcrl_host.hpp"
 
 #include "../../include/mpcrl_chain_ext.h"
+#include "../../include/mpcrl_traj_ext.h"
 #include "state_sens_kernel.hpp"
+#include "traj_vjp_kernel.hpp"
 
 using namespace mpcrl;
 
@@ -31,6 +33,23 @@ int launch_policy(const MpcrlSolver *h, const StateSensArgs &a, hipStream_t st) 
         }
     }
     hipLaunchKernelGGL((small_state_sens_kernel<M, false>), grid, wave, 0, st, h->small, a);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+template <class M>
+int launch_traj_vjp(const MpcrlSolver *h, const TrajVjpArgs &a, hipStream_t st) {   // the dispatch of launch_policy
+    constexpr SmallTraits T = small_traits<M>();
+    const int ipw = std::min(64 / (h->N + 1), T.max_ipw);
+    const dim3 grid((unsigned)((h->B + ipw - 1) / ipw)), wave(64);
+    if constexpr (!T.seg_skip) {
+        if (seg_short(T, h->N)) {
+            hipLaunchKernelGGL((small_traj_vjp_kernel<M, true>), grid, wave, 0, st, h->small, a);
+            HIP_OK(hipGetLastError());
+            return 0;
+        }
+    }
+    hipLaunchKernelGGL((small_traj_vjp_kernel<M, false>), grid, wave, 0, st, h->small, a);
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -82,6 +101,22 @@ int mpcrl_state_sens(mpcrl_handle h, int flags, double *dV_dx0, double *dQ_du0, 
         }
     }
     return 0;
+}
+
+int mpcrl_traj_ext_version(void) { return MPCRL_TRAJ_EXT_VERSION; }
+
+int mpcrl_traj_vjp(mpcrl_handle h, int flags, const double *gX, const double *gU, double *g_x0, double *g_theta, void *stream) {
+    if (!h || flags) return MPCRL_E_ARG;   // (MPCRL_STATE_Q_MODE included: with u_0 pinned the system has other unknowns)
+    if (h->is_large) return MPCRL_E_MODEL;
+    if (!h->have_iterate || h->dual_cold) return MPCRL_E_ARG;
+    if ((!gX && !gU) || (!g_x0 && !g_theta)) return MPCRL_E_ARG;
+    ON_DEVICE(h->device);
+    TrajVjpArgs a;
+    a.B = h->B, a.theta_stride = h->theta_stride, a.perm = h->have_perm ? h->perm : nullptr, a.theta = h->theta;
+    a.X = h->X, a.U = h->U, a.PI = h->PI, a.BND = h->BND, a.RES = h->RES;
+    a.gX = gX, a.gU = gU, a.g_x0 = g_x0, a.g_theta = g_theta;
+    return h->model == MPCRL_MODEL_LINEAR ? launch_traj_vjp<LinearDev>(h, a, (hipStream_t)stream)
+                                          : launch_traj_vjp<CartpoleDev>(h, a, (hipStream_t)stream);
 }
 
 int mpcrl_chain_ext_version(void) { return MPCRL_CHAIN_EXT_VERSION; }
