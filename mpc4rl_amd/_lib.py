@@ -1,4 +1,4 @@
-"""ctypes binding of libmpcrl_hip.so, read from include/mpcrl.h (and include/mpcrl_ext.h, include/mpcrl_chain_ext.h and include/mpcrl_traj_ext.h, a table of its own each), and the one path the package calls the library through
+"""ctypes binding of libmpcrl_hip.so, read from include/mpcrl.h (and include/mpcrl_ext.h, include/mpcrl_chain_ext.h, include/mpcrl_traj_ext.h and include/mpcrl_chain_traj_ext.h, a table of its own each), and the one path the package calls the library through
 (``call``, ``workspace``).  Fails loudly when the library is missing.
 
 The .hip units include the same header, so the compiler holds the implementation to it; the prototypes, constants and error codes here
@@ -105,6 +105,13 @@ with open(TRAJ_EXT_HEADER_PATH) as _f:
     TRAJ_EXT_HEADER = parse_header(_f.read())      # a fourth table (the #include of mpcrl_ext.h is not followed)
 TRAJ_EXT_EXPORTS = list(TRAJ_EXT_HEADER.functions)
 TRAJ_EXT_VERSION = TRAJ_EXT_HEADER.constants["TRAJ_EXT_VERSION"]
+CHAIN_TRAJ_EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mpcrl_chain_traj_ext.h")   # the trajectory VJP of the chain of masses, versioned on its own
+if not os.path.exists(CHAIN_TRAJ_EXT_HEADER_PATH):
+    raise ImportError(f"mpc4rl_amd: {CHAIN_TRAJ_EXT_HEADER_PATH} not found. The binding is read from the headers: keep include/ beside the package.")
+with open(CHAIN_TRAJ_EXT_HEADER_PATH) as _f:
+    CHAIN_TRAJ_EXT_HEADER = parse_header(_f.read())      # a fifth table (the #include of mpcrl_ext.h is not followed)
+CHAIN_TRAJ_EXT_EXPORTS = list(CHAIN_TRAJ_EXT_HEADER.functions)
+CHAIN_TRAJ_EXT_VERSION = CHAIN_TRAJ_EXT_HEADER.constants["CHAIN_TRAJ_EXT_VERSION"]
 
 
 def _constants(names: str):
@@ -180,8 +187,12 @@ def load():
     if lib.mpcrl_traj_ext_version() != TRAJ_EXT_VERSION and not os.environ.get("MPCRL_SKIP_ABI_CHECK"):
         raise RuntimeError(f"mpc4rl_amd: {LIB_PATH} reports trajectory extension version {lib.mpcrl_traj_ext_version()}, this binding expects "
                            f"{TRAJ_EXT_VERSION}; rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`).")
+    lib.mpcrl_chain_traj_ext_version.restype = C.c_int
+    if lib.mpcrl_chain_traj_ext_version() != CHAIN_TRAJ_EXT_VERSION and not os.environ.get("MPCRL_SKIP_ABI_CHECK"):
+        raise RuntimeError(f"mpc4rl_amd: {LIB_PATH} reports chain trajectory extension version {lib.mpcrl_chain_traj_ext_version()}, this "
+                           f"binding expects {CHAIN_TRAJ_EXT_VERSION}; rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`).")
     for name, (ret, params) in (list(HEADER.functions.items()) + list(EXT_HEADER.functions.items()) + list(CHAIN_EXT_HEADER.functions.items())
-                                + list(TRAJ_EXT_HEADER.functions.items())):
+                                + list(TRAJ_EXT_HEADER.functions.items()) + list(CHAIN_TRAJ_EXT_HEADER.functions.items())):
         fn = getattr(lib, name)
         fn.restype = _CTYPE[ret]
         fn.argtypes = [_CTYPE.get(kind, C.c_void_p) for _, kind in params]

@@ -14,8 +14,9 @@ sensitivities in ``forward``, before it knows whether ``g_u`` will arrive, and t
 whenever the solve itself did not run the du0*/dp pass.  Without it a loss that depends on ``u0`` cannot be back-propagated to ``x0``
 on a chain, and asking for it raises.
 
-``X, U = layer.trajectory(x0, theta)`` returns the whole plan X* [B, N+1, nx], U* [B, N, nu] (cartpole and linear system).  Its forward
-pass is one plain solve — no sensitivity pass — and its backward pass one ``mpcrl_traj_vjp`` (include/mpcrl_traj_ext.h) with the incoming
+``X, U = layer.trajectory(x0, theta)`` returns the whole plan X* [B, N+1, nx], U* [B, N, nu] (every model).  Its forward
+pass is one plain solve — no sensitivity pass — and its backward pass one ``mpcrl_traj_vjp`` (include/mpcrl_traj_ext.h; on the chain of
+masses ``mpcrl_chain_traj_vjp``, include/mpcrl_chain_traj_ext.h, through ``MPCBatch.chain_trajectory_vjp``: no opt-in) with the incoming
 (g_X, g_U): one adjoint solve per instance whatever the horizon.  That call reads the iterate the handle stores, so the iterate must
 still be that forward pass's: every ``forward``, ``q`` and ``trajectory`` of a layer increments the layer's pass counter, and
 ``backward`` raises a RuntimeError when the counter is no longer the one its forward pass recorded ("one backward per forward, before
@@ -125,7 +126,8 @@ class MPCQFunction(torch.autograd.Function):
 
 class MPCTrajectoryFunction(torch.autograd.Function):
     """(x0 [B, nx], theta [n_p] | [B, n_p]) -> (X [B, N+1, nx], U [B, N, nu]) through ``layer.batch``; ``backward`` is one
-    ``MPCBatch.trajectory_vjp`` on the iterate that forward pass left in the handle (the layer's pass counter guards it)."""
+    ``MPCBatch.trajectory_vjp`` (``chain_trajectory_vjp`` when the batch's OCP is a chain of masses) on the iterate that forward pass
+    left in the handle (the layer's pass counter guards it)."""
 
     @staticmethod
     def forward(ctx, x0, theta, layer):
@@ -149,8 +151,10 @@ class MPCTrajectoryFunction(torch.autograd.Function):
             raise RuntimeError("MPCLayer.trajectory: the backward pass reads the iterate its forward pass stored in the handle, and the "
                                "layer has run another forward, q or trajectory since (pass counter "
                                f"{ctx.layer.pass_counter}, recorded {ctx.pass_id}): one backward per forward, before the layer runs again.")
-        g_x0, g_th = ctx.layer.batch.trajectory_vjp(None if g_X is None else g_X.to(torch.float64),
-                                                    None if g_U is None else g_U.to(torch.float64), x0=need_x, theta=need_p)
+        batch = ctx.layer.batch
+        vjp = batch.chain_trajectory_vjp if batch.ocp.name.startswith("chain") else batch.trajectory_vjp
+        g_x0, g_th = vjp(None if g_X is None else g_X.to(torch.float64), None if g_U is None else g_U.to(torch.float64),
+                         x0=need_x, theta=need_p)
         if g_th is not None and ctx.shared:
             g_th = g_th.sum(0)
         return (None if g_x0 is None else g_x0.to(ctx.dtypes[0]), None if g_th is None else g_th.to(ctx.dtypes[1]), None)

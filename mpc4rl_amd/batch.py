@@ -276,6 +276,34 @@ class MPCBatch:
             g_x0, g_th = (None if t is None else torch.where(good, t, torch.zeros_like(t)) for t in (g_x0, g_th))
         return g_x0, g_th
 
+    def chain_trajectory_vjp(self, gX=None, gU=None, x0: bool = True, theta: bool = True):
+        """``trajectory_vjp`` for the chain of masses (include/mpcrl_chain_traj_ext.h mpcrl_chain_traj_vjp): (g_x0 [B, nx] or None,
+        g_theta [B, n_p] or None) for the cotangents gX [B, N+1, nx] on X* and gU [B, N, nu] on U* of the last solve (None = zeros, not
+        both), by one adjoint Riccati solve per instance on the workspace of that solve — three launches after a solve with sens_pi,
+        five otherwise.  Like ``state_sens(policy=True)`` it needs that solve to be the last thing that touched the handle: a
+        set_theta, set_bounds, set_discount_factor, reset or set_iterate in between raises.  After a solve without u0.  Rows of
+        instances whose status is neither 0 nor 2 are zeros."""
+        if not self._is_chain:
+            raise RuntimeError("chain_trajectory_vjp is for the chain of masses; the cartpole and the linear system have trajectory_vjp")
+        if not (self.has_iterate and self.duals_valid):
+            raise RuntimeError("chain_trajectory_vjp needs the iterate of a solve with its bound multipliers (solve with store_bounds=True first)")
+        if self._solve_status is not None and self._solve_q_mode:
+            raise RuntimeError("chain_trajectory_vjp after a solve with u0 fixed (Q mode) is not available")
+        if not self._chain_ws_current or self._solve_status is None:
+            raise RuntimeError("chain_trajectory_vjp reads the workspace of the last solve, and the handle was changed since (set_theta, "
+                               "set_bounds, set_discount_factor, reset or set_iterate): solve again first")
+        if gX is None and gU is None:
+            raise ValueError("chain_trajectory_vjp needs a cotangent: gX, gU or both")
+        if not (x0 or theta):
+            raise ValueError("chain_trajectory_vjp needs an output: x0, theta or both")
+        gX = None if gX is None else self._dev(gX, (self.B, self.N + 1, self.nx))
+        gU = None if gU is None else self._dev(gU, (self.B, self.N, self.nu))
+        kw = dict(dtype=torch.float64, device=self.device)
+        g_x0 = torch.empty((self.B, self.nx), **kw) if x0 else None
+        g_th = torch.empty((self.B, self.n_p), **kw) if theta else None
+        self._call("mpcrl_chain_traj_vjp", 0, self._solve_status, gX, gU, g_x0, g_th)
+        return g_x0, g_th
+
     def get_action(self, x0) -> torch.Tensor:
         """Batched MPC.get_action (mpc.py:27-50)."""
         return self.solve(x0).u0

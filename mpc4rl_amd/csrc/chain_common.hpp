@@ -116,7 +116,7 @@ struct LargeLayout {
     // pattern for the vector sweeps, which multiply with [A B] and K instead of a stored closed-loop matrix
     static constexpr int BAS = NW * NW;
     size_t BA, r, q, dx, du, nuq, Dx, Du, rg, rb, rt, Dg, lamw, tw, aff, p, kff, Hex, term, ynu, state, Ydx, Ydu, Ydnu,
-        term2, ptab, gtab, qvtab, G2, P2, hb2, minv2, mvu2, total;
+        term2, ptab, gtab, qvtab, G2, P2, hb2, minv2, mvu2, Tdx, Tdu, Tdnu, tterm, total;
     __host__ __device__ explicit LargeLayout(int N) {
         size_t o = 0;
         auto take = [&](size_t n) { size_t s = o; o += (n + 1) & ~(size_t)1; return s; };   // every array 16-byte aligned
@@ -137,11 +137,15 @@ struct LargeLayout {
         // the sweeps' streams: closed-loop blocks G_k, cost-to-go P_k of the adjoint factorisation (Omega register layout), hb_k = P_{k+1} b_k, R_k^-1, mv_u of the corrector
         G2 = take((size_t)N * OmCfg<M>::GSZ), P2 = take((size_t)(N + 1) * OmCfg<M>::GSZ + 64);
         hb2 = take((size_t)N * OmCfg<M>::HBS), minv2 = take((size_t)N * 16), mvu2 = take((size_t)N * 4);
+        // the trajectory VJP (include/mpcrl_chain_traj_ext.h): its ONE adjoint solution and per-stage parameter terms, a region of their
+        // own behind everything else — Ydx / Ydu / Ydnu / term2 stay the du0*/dp pass's, which mpcrl_chain_policy_state_sens reads
+        Tdx = take((size_t)(N + 1) * NX + 2), Tdu = take((size_t)N * NU + 2), Tdnu = take((size_t)(N + 1) * NX + 2), tterm = take((size_t)N * NTD);
         total = (o + 7) & ~(size_t)7;
     }
 };
 
-enum { ST_ACTIVE = 0, ST_IT = 1, ST_NIPM = 2, ST_TIGHT = 3, ST_STEPN = 4, ST_COST = 5, ST_RES = 6, ST_STATUS = 10 };
+enum { ST_ACTIVE = 0, ST_IT = 1, ST_NIPM = 2, ST_TIGHT = 3, ST_STEPN = 4, ST_COST = 5, ST_RES = 6, ST_STATUS = 10,
+       ST_TRAJ = 11 };   // ST_STATUS: the du0*/dp factorisation was positive definite (0) or not (4); ST_TRAJ: the same of the trajectory VJP's own
 
 template <class M, bool SECOND, bool TH_LDS>
 __device__ __forceinline__ void chain_point_body(const double *X, const double *U, const double *th, double *w, int N, int k, double h, int steps, double *lacc);

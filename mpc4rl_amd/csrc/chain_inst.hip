@@ -80,6 +80,34 @@ int launch_policy_state_sens(MpcrlSolver *h, const int32_t *status, double *dpi_
     return 0;
 }
 
+// The trajectory VJP of the handle's last solve (include/mpcrl_chain_traj_ext.h).  The exact Hessians and the point tables are in the
+// workspace after a solve that ran MPCRL_SENS_PI in V mode; otherwise the second-order point pass and chain_sens_ad first, as above.
+// Then the adjoint solve for the cotangent, the mixed term of its one solution (only g_theta reads it) and the outputs.  Every
+// dynamic-LDS request is at most the du0*/dp pass's (LargeLds: one solution staged instead of 1 + NU).
+template <class M>
+int launch_traj_vjp(MpcrlSolver *h, const int32_t *status, const double *gX, const double *gU, double *g_x0, double *g_theta,
+                    bool adjoint_current, hipStream_t st) {
+    const int B = h->B, N = h->N;
+    const LargeLds<M> lds(N);
+    if (!lds.fits()) return MPCRL_E_ARG;   // (mpcrl_create has checked: not reached)
+    LargeArgs a{};
+    a.B = B, a.theta_stride = h->theta_stride, a.theta = h->theta;
+    a.X = h->X, a.U = h->U, a.PI = h->PI, a.BND = h->BND, a.RES = h->RES, a.LAG = h->LAG;
+    a.ws = h->ws, a.ws_stride = h->ws_stride, a.status = const_cast<int32_t *>(status);
+    a.flags = MPCRL_SENS_PI, a.u0fix = nullptr;      // (as launch_policy_state_sens; a.dpi stays null: nothing here reads or writes it)
+    if (!adjoint_current) {
+        hipLaunchKernelGGL((chain_point_kernel<M, true>), dim3((unsigned)B), dim3(64), lds.point, st, h->large, a);
+        hipLaunchKernelGGL(chain_sens_ad_kernel<M>, dim3((unsigned)(B * HexCfg<M>::groups(N))), dim3(64), 0, st, h->large, a);
+    }
+    hipLaunchKernelGGL(chain_traj_riccati_kernel<M>, dim3(B), dim3(64), lds.sqp, st, h->large, a, gX, gU);
+    if (g_theta)
+        hipLaunchKernelGGL((chain_sens_mix2_kernel<M, 1>), dim3((unsigned)(((long)B * N + 63) / 64)), dim3(64), lds.mix2, st, h->large, a);
+    const unsigned lds_out = (unsigned)((64 + 2 * ((N + 1) * M::NX + N * M::NU)) * sizeof(double));
+    hipLaunchKernelGGL(chain_traj_out_kernel<M>, dim3((unsigned)B), dim3(1024), lds_out, st, h->large, a, gX, g_x0, g_theta);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 size_t ws_doubles(int N) { return LargeLayout<Model>(N).total; }
 bool lds_fits(int N) { return LargeLds<Model>(N).fits(); }
 
@@ -103,6 +131,6 @@ constexpr int (*debug_phases)(unsigned long long *, int) = nullptr;
 #define MPCRL_CAT(a, b) MPCRL_CAT_(a, b)
 const MpcrlChainEntry *MPCRL_CAT(mpcrl_chain_entry_, MPCRL_CHAIN_NMASS)() {
     static const MpcrlChainEntry e = {MPCRL_CHAIN_NMASS, (long)Model::NP, ws_doubles, lds_fits, launch_large<Model>, debug_phases,
-                                     launch_policy_state_sens<Model>};
+                                     launch_policy_state_sens<Model>, launch_traj_vjp<Model>};
     return &e;
 }

@@ -7,6 +7,11 @@
 //   chain_sens_riccati        wavefront per instance: factorisation with the exact Hessian + barrier diagonal, nu adjoint solves
 //   chain_sens_mix2           lane per (instance, stage, control): the mixed term y_v' d/dv (nu' dF/dtheta) + y_nu' dF/dtheta
 //   chain_sens_out            workgroup per instance: the output reductions
+// and, on the workspace such a solve leaves, the calls of include/mpcrl_chain_ext.h and include/mpcrl_chain_traj_ext.h (chain_inst.hip):
+//   chain_state_sens          wavefront per instance: du0*/dx0, the stage-0 contraction of the nu adjoint solutions
+//   chain_traj_riccati        wavefront per instance: the same factorisation, ONE adjoint solve for a cotangent on the whole plan
+//   chain_sens_mix2<M, 1>     lane per (instance, stage): the mixed term of that one solution
+//   chain_traj_out            workgroup per instance: g_theta and g_x0
 // They re-use [B A], lam, t, nu left in the workspace by the last SQP round (its linearisation is at the final iterate).
 #pragma once
 #include "chain_linearise.hpp"
@@ -307,6 +312,62 @@ __global__ void __launch_bounds__(64, 1) chain_sens_riccati_kernel(const LargeSp
     if (lane == 0) S.state[ST_STATUS] = okall ? 0.0 : 4.0;   // read by sens_out: NaN sensitivities when the exact-Hessian KKT matrix is not pd
 }
 
+// The adjoint solve of the trajectory VJP (include/mpcrl_chain_traj_ext.h): K y = [G; 0] with K the exact-Hessian barrier KKT matrix
+// chain_sens_riccati_kernel factors (same guards on the status, same capped barrier diagonal, same terminal Hessian, rb = 0) and
+// G = (gU, gX) the cotangent on the plan.  The right-hand side of the recursion is -G in stage-vector order [u_k; x_k] — the sign of
+// the -e_iu above, so that the unit cotangent reproduces Ydx / Ydu / Ydnu — with the state part of stage 0 zero (x_0 is eliminated:
+// gX[0] enters g_x0 through the identity alone, chain_traj_out_kernel) and gX[N] at the terminal stage.  One factor sweep (its vector
+// column leaves p_k, kff_k), one forward sweep (forward2_adj).  The solution goes to a region of its own (Tdx / Tdu / Tdnu) and the
+// verdict of the factorisation to a word of its own (ST_TRAJ): what the du0*/dp pass left for mpcrl_chain_policy_state_sens stays.
+template <class M>
+__global__ void __launch_bounds__(64, 1) chain_traj_riccati_kernel(const LargeSpec sp, const LargeArgs a, const double *__restrict__ gX,
+                                                                   const double *__restrict__ gU) {
+    using Cfg = ChainCfg<M>;
+    constexpr int NX = M::NX, NU = M::NU, NW = NX + NU, NT = 64;
+    extern __shared__ __attribute__((aligned(16))) double lds[];      // Cfg::lds_doubles(N) doubles (launch_traj_vjp)
+    __shared__ int sidx[196];
+    const int lane = threadIdx.x, inst = blockIdx.x, N = sp.N;
+    const int status = a.status[inst];
+    if (!(status == 0 || status == 2)) return;
+    ChainSolver<M> S(sp, lane);
+    S.th = a.theta + (size_t)inst * a.theta_stride;
+    S.qmode = false;      // u_0 is free (after a Q-mode solve: at the pinned value)
+    const LargeLayout<M> lay(N);
+    double *w = a.ws + (size_t)inst * a.ws_stride;
+    S.bind_workspace(w, lay);
+    S.setup(lds, sidx);
+    S.X = a.X + (size_t)inst * (N + 1) * NX, S.U = a.U + (size_t)inst * N * NU;
+    const int ne = (N + 1) * NW;
+    const double *th = S.th;
+    const WsArr Hex{(char *)w, (unsigned)lay.Hex};
+    for (int e = lane; e < NW * NW; e += NT) Hex[N * NW * NW + e] = S.ck(N) * M::hess(true, e / NW, e % NW, th);
+    for (int e = lane; e < ne; e += NT) {      // the capped barrier diagonal of chain_sens_riccati_kernel
+        const int k = e / NW, i = e - k * NW;
+        double d = 0.0;
+        if (!S.skipc(k, i))
+            for (int sd = 0; sd < 2; ++sd)
+                if (S.has(sd, k, i)) d += fmin(S.LAM(sd, e) / S.TT(sd, e), SENS_W_MAX);
+        S.Dg[e] = d;
+    }
+    wave_sync();
+    for (int e = lane; e < N * NX; e += NT) S.rb[e] = 0.0;
+    const double *gx = gX ? gX + (size_t)inst * (N + 1) * NX : nullptr, *gu = gU ? gU + (size_t)inst * N * NU : nullptr;
+    for (int e = lane; e < ne; e += NT) {
+        const int k = e / NW, i = e - k * NW;
+        double v = 0.0;
+        if (i < NU) {
+            if (gu && k < N) v = gu[k * NU + i];
+        } else if (gx && k > 0)
+            v = gx[k * NX + (i - NU)];
+        S.rt[e] = -v;
+    }
+    wave_sync();
+    const WsArr Tdx{(char *)w, (unsigned)lay.Tdx}, Tdu{(char *)w, (unsigned)lay.Tdu}, Tdnu{(char *)w, (unsigned)lay.Tdnu};
+    const bool okall = ChainSolver<M>::template factor_call<HessGlobal<M>>(S.ctx(), Hex.off, S.rt.off, S.rb.off);
+    ChainSolver<M>::forward_adj_call(S.ctx(), Tdx.off, Tdu.off, Tdnu.off);
+    if (lane == 0) S.state[ST_TRAJ] = okall ? 0.0 : 4.0;   // read by chain_traj_out_kernel: NaN where the exact-Hessian KKT matrix is not pd
+}
+
 // ---- the mixed term on the POINT TABLES (round 4; until then a forward-over-reverse jet sweep of the whole
 // RK4 map that kept four stage states, four adjoint vectors and the parameter adjoint live as jets: 1 076 spilled registers and 3.3 KB of
 // scratch per lane at n_mass 5, 1 696 / 6 KB at n_mass 7 — 0.43 / 1.85 ms for 12 k flops per lane).  Per (instance, stage, control)
@@ -319,9 +380,13 @@ __global__ void __launch_bounds__(64, 1) chain_sens_riccati_kernel(const LargeSp
 //      (d dist / dx)' G_{e,i} d dist_{e,i} at every evaluation point;
 //   3. at every (e, i) the tangent of the parameter adjoint of ode_adj_p, written out in the table quantities.
 // ~170 doubles of live state, no jets, no scratch.
-template <class M>
+// NS = NU (the default): the NU solutions of the du0*/dp pass (Ydx / Ydu / Ydnu -> term2), a lane per (instance, stage, control).
+// NS = 1: the ONE solution of the trajectory VJP (Tdx / Tdu / Tdnu -> tterm, chain_traj_riccati_kernel), a lane per (instance, stage).
+template <class M, int NS = M::NU>
 __global__ void __launch_bounds__(64) chain_sens_mix2_kernel(const LargeSpec sp, const LargeArgs a) {
     constexpr int NX = M::NX, NU = M::NU, NTD = M::NTD, NL = M::NL, TAB2 = M::TAB2, MM = M::M;
+    constexpr bool TRAJ = NS != NU;
+    static_assert(NS == NU || NS == 1, "the du0*/dp pass or the trajectory VJP");
     // per lane in LDS ([index][lane]: conflict-free): the NTD accumulators of the parameter-adjoint tangent and the start state of
     // the second RK4 step — with the evaluation states recomputed where they are used, what stays in registers is one evaluation
     // state, one ODE tangent and the four adjoint vectors
@@ -329,7 +394,7 @@ __global__ void __launch_bounds__(64) chain_sens_mix2_kernel(const LargeSpec sp,
     const int N = sp.N, lane = threadIdx.x;
     double *thd = sm + lane, *dx1 = sm + NTD * 64 + lane;
     const long gid = (long)blockIdx.x * 64 + threadIdx.x;
-    const int per = N * NU;
+    const int per = N * NS;
     const int inst = (int)(gid / per);
     if (inst >= a.B) return;
     const int status = a.status[inst];
@@ -337,13 +402,13 @@ __global__ void __launch_bounds__(64) chain_sens_mix2_kernel(const LargeSpec sp,
     // (the control index runs fastest: the NU lanes of a stage read the SAME table entries — every table access of this kernel is a gather,
     // one cache line per lane, and the kernel runs on the rate of those requests; with the stage index fastest all 64 lanes of a load
     // went to different lines)
-    const int it = (int)(gid - (long)inst * per), k = it / NU, iu = it - k * NU;
+    const int it = (int)(gid - (long)inst * per), k = it / NS, iu = it - k * NS;
     const LargeLayout<M> lay(N);
     double *w = a.ws + (size_t)inst * a.ws_stride;
     const double *th = a.theta + (size_t)inst * a.theta_stride;
     const double *tab = w + lay.ptab + (size_t)k * 8 * NL * TAB2, *Gt = w + lay.gtab + (size_t)k * 8 * NL * 6, *qv = w + lay.qvtab + (size_t)k * 8 * NL * 6;
-    const double *Ydx = w + lay.Ydx + (size_t)iu * (N + 1) * NX + (size_t)k * NX, *Ydu = w + lay.Ydu + (size_t)iu * N * NU,
-                 *Ydnu = w + lay.Ydnu + (size_t)iu * (N + 1) * NX;
+    const double *Ydx = w + (TRAJ ? lay.Tdx : lay.Ydx) + (size_t)iu * (N + 1) * NX + (size_t)k * NX,
+                 *Ydu = w + (TRAJ ? lay.Tdu : lay.Ydu) + (size_t)iu * N * NU, *Ydnu = w + (TRAJ ? lay.Tdnu : lay.Ydnu) + (size_t)iu * (N + 1) * NX;
     const double h = sp.h;
     const int steps = sp.rk_steps;
     const double *mp = th, *Dp = th + NL, *Lp = th + 4 * NL;
@@ -447,7 +512,7 @@ __global__ void __launch_bounds__(64) chain_sens_mix2_kernel(const LargeSpec sp,
 #pragma unroll
         for (int i = 0; i < NX; ++i) lbd[i] = accd[i];
     }
-    double *term2 = w + lay.term2 + ((size_t)iu * N + k) * NTD;
+    double *term2 = w + (TRAJ ? lay.tterm : lay.term2) + ((size_t)iu * N + k) * NTD;
 #pragma unroll
     for (int d = 0; d < NTD; ++d) term2[d] = thd[d * 64];
 }
@@ -573,6 +638,74 @@ __global__ void __launch_bounds__(64) chain_state_sens_kernel(const LargeSpec sp
     }
 #pragma unroll
     for (int iu = 0; iu < NU; ++iu) o[iu * NX + lane] = sens_ok ? -acc[iu] : NAN;
+}
+
+// The outputs of the trajectory VJP from the ONE solution y of chain_traj_riccati_kernel: what chain_sens_out_kernel (a slot >= 1) and
+// chain_state_sens_kernel contract, with that solution in place of the NU of the du0*/dp pass,
+//     g_theta = -y' dR/dtheta     the per-stage terms of chain_sens_mix2_kernel<M, 1> summed over the stages, the closed forms for Q and R
+//     g_x0    = -y' dR/dx0 + gX[0]     stage 0: Hex_0[u, x] and A_0
+// One workgroup of 1024 lanes per instance, the trajectories staged in LDS; every sum runs over the stages (the rows) in sequence on
+// one lane, so the same workspace gives the same bits.  Every requested row is written in full by every call: the values for status
+// 0 / 2, zeros otherwise, NaN where the factorisation was not positive definite.
+template <class M>
+__global__ void __launch_bounds__(1024) chain_traj_out_kernel(const LargeSpec sp, const LargeArgs a, const double *__restrict__ gX,
+                                                              double *__restrict__ g_x0, double *__restrict__ g_theta) {
+    constexpr int NX = M::NX, NU = M::NU, NW = NX + NU, NTD = M::NTD, NP = M::NP;
+    constexpr int NE = NTD + NX * NX + NU * NU;   // dynamics parameters, Q (column-major), R
+    static_assert(NE == NP && NX <= 1024, "every entry of theta is an output element; one state column per lane");
+    const int N = sp.N;
+    extern __shared__ double sm[];
+    double *cks = sm, *lX = sm + 64, *lU = lX + (N + 1) * NX, *Dx = lU + N * NU, *Du = Dx + (N + 1) * NX;
+    const int inst = blockIdx.x, tid = threadIdx.x;
+    double *gx = g_x0 ? g_x0 + (size_t)inst * NX : nullptr, *gt = g_theta ? g_theta + (size_t)inst * NP : nullptr;
+    const int status = a.status[inst];
+    if (!(status == 0 || status == 2)) {
+        if (gt)
+            for (int e = tid; e < NP; e += 1024) gt[e] = 0.0;
+        if (gx && tid < NX) gx[tid] = 0.0;
+        return;
+    }
+    const LargeLayout<M> lay(N);
+    const double *w = a.ws + (size_t)inst * a.ws_stride;
+    const double *X = a.X + (size_t)inst * (N + 1) * NX, *U = a.U + (size_t)inst * N * NU, *xs = sp.consts;
+    for (int k = tid; k <= N; k += 1024) {
+        double c = k == N ? 1.0 : sp.dT;
+        if (sp.cost_kind != 0) c = k == 0 ? sp.dT : (k == N ? pow(sp.gamma, (double)N) : pow(sp.gamma, (double)k) * sp.dT);
+        cks[k] = c;
+    }
+    for (int e = tid; e < (N + 1) * NX; e += 1024) lX[e] = X[e] - xs[e % NX], Dx[e] = w[lay.Tdx + e];
+    for (int e = tid; e < N * NU; e += 1024) lU[e] = U[e], Du[e] = w[lay.Tdu + e];
+    __syncthreads();
+    const bool sens_ok = w[lay.state + ST_TRAJ] == 0.0;
+    if (gt)
+        for (int e0 = tid; e0 < NE; e0 += 1024) {
+            double acc = 0.0;
+            int pidx;
+            if (e0 < NTD) {
+                const double *tm = w + lay.tterm;
+                for (int k = 0; k < N; ++k) acc += tm[k * NTD + e0];
+                pidx = M::td_index(e0);
+            } else if (e0 < NTD + NX * NX) {      // y' d2 l / dv dQ_ij = 1/2 (y_i e_j + y_j e_i)
+                const int e = e0 - NTD, j = e / NX, i = e - j * NX;
+                for (int k = 0; k <= N; ++k) acc += 0.5 * cks[k] * (Dx[k * NX + i] * lX[k * NX + j] + Dx[k * NX + j] * lX[k * NX + i]);
+                pidx = M::OFF_Q + e;
+            } else {
+                const int ee = e0 - NTD - NX * NX, j = ee / NU, i = ee - j * NU;
+                for (int k = 0; k < N; ++k) acc += 0.5 * cks[k] * (Du[k * NU + i] * lU[k * NU + j] + Du[k * NU + j] * lU[k * NU + i]);
+                pidx = M::OFF_R + ee;
+            }
+            gt[pidx] = sens_ok ? -acc : NAN;
+        }
+    if (gx && tid < NX) {      // lane = state column, the operand rows read coalesced (chain_state_sens_kernel)
+        const double *Tdnu = w + lay.Tdnu + NX, *Hex0 = w + lay.Hex, *BA0 = w + lay.BA;
+        double acc = 0.0;
+#pragma unroll
+        for (int c = 0; c < NU; ++c) acc = fma(Du[c], Hex0[c * NW + NU + tid], acc);
+#pragma unroll 4
+        for (int r = 0; r < NX; ++r) acc = fma(Tdnu[r], BA0[r * NW + NU + tid], acc);
+        const double g0 = gX ? gX[(size_t)inst * (N + 1) * NX + tid] : 0.0;
+        gx[tid] = sens_ok ? g0 - acc : NAN;
+    }
 }
 
 }  // namespace mpcrl

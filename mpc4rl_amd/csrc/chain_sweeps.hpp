@@ -1147,6 +1147,130 @@ struct ChainSolver {
         wave_sync();
     }
 
+    // ---- the forward sweep of ONE adjoint solve whose right-hand side is non-zero at every stage (the trajectory VJP,
+    // chain_traj_riccati_kernel): the factor sweep's vector column has left p_k and kff_k of that right-hand side, and
+    //     [dx_{k+1}; du_k] = [0; -kff_k] + G_k [dx_k; -kff_k]         dnu_k = P_k dx_k + p_k   (k = 1 .. N)
+    // on the G2 / P2 streams as forward2_sens loads them (same prefetch depth: two blocks per stage in flight).  kff_k and p_k of the
+    // whole horizon are staged in LDS first (kff compactly, four slots per stage; p in Omega order), so the streams are all that is in
+    // the global-memory queue.  One column: the 16 columns of the B operand carry identical copies, the lanes of column 0 store.  The
+    // P product takes the operand with EMPTY control slots — the control columns of the stored P_k are R - R R^-1 R, rounding noise
+    // that forward2_sens never meets (its control slots are zero past stage 0).  Out: Zdx / Zdu / Zdnu as ONE solution of forward2_sens.
+    MPCRL_DI void forward2_adj(const WsArr Zdx, const WsArr Zdu, const WsArr Zdnu) {
+        using O = OmCfg<M>;
+        constexpr int RG = O::RG, NTR = O::NTR, GQ = O::GQ, TV = O::TV, LV = O::LV, D = NTR <= 2 ? 3 : 1;
+        constexpr bool RAGGED = 4 * RG > NW;
+        const int lr = lane >> 4, lc = lane & 15;
+        const bool padl = lr < NU, col = lc == 0;
+        const int sx = (N + 1) * NX;
+        double *const lk = lds + Cfg::oBig, *const lp = lk + 4 * N;
+        for (int e = lane; e < 4 * N; e += NT) lk[e] = (e & 3) < NU ? kff[(e >> 2) * NU + ((e & 3) < NU ? (e & 3) : 0)] : 0.0;
+        stage_vec_lds<true>(lp, p, N);
+        unsigned tfull[NTR], tcomp[NTR], poffs[NTR];
+#pragma unroll
+        for (int ti = 0; ti < NTR; ++ti) {
+            const int a_ = 16 * ti + lc, a = a_ < 4 * RG ? a_ : 4 * RG - 1;
+            tfull[ti] = (unsigned)((a >> 2) * TV * 64 + (a & 3) * 16 + lr);
+            tcomp[ti] = (unsigned)(RG * TV * 64 + (a >> 2) * O::CT + (a & 3) * LV + lr);
+            poffs[ti] = O::goff(0, ti, lr, lc);
+        }
+        if (lane < NX) Zdx[lane] = 0.0, Zdnu[lane] = 0.0;      // x_0 is eliminated
+        wave_sync();
+        double w[RG];
+#pragma unroll
+        for (int rg = 0; rg < RG; ++rg) w[rg] = 0.0;
+        double nGt[D][NTR][RG], nP[D][RG][NTR];
+        staged_loop<D>(
+            N,
+            [&](int k, auto sl) {
+                constexpr int d = decltype(sl)::value;
+#pragma unroll
+                for (int ti = 0; ti < NTR; ++ti)
+#pragma unroll
+                    for (int ks = 0; ks < RG; ++ks)
+                        nGt[d][ti][ks] = G2[k * O::GSZ + (ks / 4 < TV ? tfull[ti] + (ks / 4) * 64 : tcomp[ti]) + 4 * (ks % 4)];
+                static_for<RG>([&](auto rg_) {
+                    constexpr int rg = decltype(rg_)::value;
+#pragma unroll
+                    for (int ti = 0; ti < NTR; ++ti) nP[d][rg][ti] = P2[k * O::GSZ + poffs[ti] + rg * (ti < TV ? TV * 64 : O::CT)];
+                });
+            },
+            [&](int k, auto sl, auto refill) {
+                constexpr int d = decltype(sl)::value;
+                d4_t acc[NTR], acc2[NTR];
+                static_for<NTR>([&](auto ti_) {
+                    static_for<4>([&](auto r_) {
+                        constexpr int ti = decltype(ti_)::value, r = decltype(r_)::value, rg = 4 * ti + r;
+                        double c = 0.0;
+                        if constexpr (rg < RG) c = lp[k * O::HBS + 4 * rg + lr];      // p_k (zero in the control and pad slots)
+                        acc[ti][r] = 0.0, acc2[ti][r] = c;
+                    });
+                });
+                const double nk = padl ? -lk[4 * k + lr] : 0.0;       // -kff_k in the control slots
+                acc[GQ / 4][GQ % 4] = nk;
+                const double wx = padl ? 0.0 : w[GQ];                 // the operand of the P product: dx_k alone
+                w[GQ] = padl ? nk : w[GQ];
+                double Gk[NTR][RG], Pk[RG][NTR];
+#pragma unroll
+                for (int ti = 0; ti < NTR; ++ti)
+#pragma unroll
+                    for (int ks = 0; ks < RG; ++ks) Gk[ti][ks] = nGt[d][ti][ks];
+#pragma unroll
+                for (int rg = 0; rg < RG; ++rg)
+#pragma unroll
+                    for (int ti = 0; ti < NTR; ++ti) Pk[rg][ti] = nP[d][rg][ti];
+                refill();
+#pragma unroll
+                for (int ks = 0; ks < RG; ++ks)
+#pragma unroll
+                    for (int ti = 0; ti < NTR; ++ti) {
+                        acc[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(Gk[ti][ks], w[ks], acc[ti], 0, 0, 0);
+                        acc2[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(Pk[ks][ti], ks == GQ ? wx : w[ks], acc2[ti], 0, 0, 0);
+                    }
+                if (col)
+                    static_for<RG>([&](auto rg_) {
+                        constexpr int rg = decltype(rg_)::value;
+                        const double v = acc[rg / 4][rg % 4];
+                        const bool rok = (rg != GQ || !padl) && (!RAGGED || rg < RG - 1 || 4 * rg + lr < NW);
+                        if constexpr (rg == GQ)
+                            Zdx[padl ? (int)(Zdu.off - Zdx.off) + k * NU + lr : (k + 1) * NX + om_xr<rg>(lr)] = v;      // du_k / dx_{k+1}
+                        else
+                            Zdx[rok ? (k + 1) * NX + om_xr<rg>(lr) : sx] = v;
+                        Zdnu[(rok && k > 0) ? k * NX + om_xr<rg>(lr) : sx] = acc2[rg / 4][rg % 4];
+                    });
+#pragma unroll
+                for (int rg = 0; rg < RG; ++rg) w[rg] = acc[rg / 4][rg % 4];
+            });
+        {   // terminal multiplier step: dnu_N = P_N dx_N + p_N
+            d4_t acc2[NTR];
+            double Pk[RG][NTR];
+            static_for<RG>([&](auto rg_) {
+                constexpr int rg = decltype(rg_)::value;
+#pragma unroll
+                for (int ti = 0; ti < NTR; ++ti) Pk[rg][ti] = P2[N * O::GSZ + poffs[ti] + rg * (ti < TV ? TV * 64 : O::CT)];
+            });
+            static_for<NTR>([&](auto ti_) {
+                static_for<4>([&](auto r_) {
+                    constexpr int ti = decltype(ti_)::value, r = decltype(r_)::value, rg = 4 * ti + r;
+                    double c = 0.0;
+                    if constexpr (rg < RG) c = lp[N * O::HBS + 4 * rg + lr];
+                    acc2[ti][r] = c;
+                });
+            });
+            w[GQ] = padl ? 0.0 : w[GQ];
+#pragma unroll
+            for (int ks = 0; ks < RG; ++ks)
+#pragma unroll
+                for (int ti = 0; ti < NTR; ++ti) acc2[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(Pk[ks][ti], w[ks], acc2[ti], 0, 0, 0);
+            if (col)
+                static_for<RG>([&](auto rg_) {
+                    constexpr int rg = decltype(rg_)::value;
+                    const bool rok = (rg != GQ || !padl) && (!RAGGED || rg < RG - 1 || 4 * rg + lr < NW);
+                    Zdnu[rok ? N * NX + om_xr<rg>(lr) : sx] = acc2[rg / 4][rg % 4];
+                });
+        }
+        wave_sync();
+    }
+
     // ---- multipliers of the dynamics at the end of a QP, by ONE costate sweep instead of Dnu_k = p_k + P_k Dx_k in every
     // interior-point iteration (which made the factor sweep stream P_k out and the corrector's forward sweep stream it back in: 9 KB
     // of the 32 KB a stage moved per iteration at n_mass 5).  No step of the iteration uses nuq — the Riccati direction gives Dx, Du,
@@ -1722,6 +1846,10 @@ struct ChainSolver {
     __device__ MPCRL_PHASE_FN static void forward_sens_call(Ctx c, unsigned ydx, unsigned ydu, unsigned ydnu) {
         ChainSolver S = from_ctx(c);
         S.forward2_sens(S.arr(ydx), S.arr(ydu), S.arr(ydnu));
+    }
+    __device__ MPCRL_PHASE_FN static void forward_adj_call(Ctx c, unsigned zdx, unsigned zdu, unsigned zdnu) {
+        ChainSolver S = from_ctx(c);
+        S.forward2_adj(S.arr(zdx), S.arr(zdu), S.arr(zdnu));
     }
     __device__ MPCRL_PHASE_FN static void costate_call(Ctx c) {
         ChainSolver S = from_ctx(c);

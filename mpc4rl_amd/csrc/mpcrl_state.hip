@@ -1,10 +1,11 @@
 // mpcrl_state.hip — include/mpcrl_ext.h: state sensitivities of a solve (dV/dx0, dQ/du0, du0*/dx0) from the iterate the handle
-// stores; include/mpcrl_chain_ext.h: du0*/dx0 of the chain, from the workspace of its last solve (kernels and launches: chain_sens.hpp,
-// chain_inst.hip).  The kernels are state_sens_kernel.hpp; this unit instantiates them for the cartpole, the linear system and every chain
+// stores; include/mpcrl_chain_ext.h and include/mpcrl_chain_traj_ext.h: du0*/dx0 and the trajectory VJP of the chain, from the workspace
+// of its last solve (kernels and launches: chain_sens.hpp, chain_inst.hip).  The kernels are state_sens_kernel.hpp; this unit instantiates them for the cartpole, the linear system and every chain
 // size, and launches them.  Nothing here allocates or waits: two launches (or one and a memset) on the caller's stream.
 #include "mpcrl_host.hpp"
 
 #include "../../include/mpcrl_chain_ext.h"
+#include "../../include/mpcrl_chain_traj_ext.h"
 #include "../../include/mpcrl_traj_ext.h"
 #include "state_sens_kernel.hpp"
 #include "traj_vjp_kernel.hpp"
@@ -134,6 +135,21 @@ int mpcrl_chain_policy_state_sens(mpcrl_handle h, int flags, const int32_t *stat
         return 0;
     }
     return e->policy_state_sens(h, status, dpi_dx0, h->chain_adjoint_current, st);
+}
+
+int mpcrl_chain_traj_ext_version(void) { return MPCRL_CHAIN_TRAJ_EXT_VERSION; }
+
+int mpcrl_chain_traj_vjp(mpcrl_handle h, int flags, const int32_t *status, const double *gX, const double *gU, double *g_x0,
+                         double *g_theta, void *stream) {
+    if (!h || flags) return MPCRL_E_ARG;   // (MPCRL_STATE_Q_MODE included: with u_0 pinned the system has other unknowns)
+    if (!h->is_large) return MPCRL_E_MODEL;
+    if (!status || (!gX && !gU) || (!g_x0 && !g_theta)) return MPCRL_E_ARG;
+    if (!h->chain_ws_current) return MPCRL_E_ARG;
+    const MpcrlChainEntry *e = chain_entry(h->n_mass);
+    if (!e) return MPCRL_E_MODEL;
+    ON_DEVICE(h->device);
+    // the solution and its parameter terms have a region of their own in the workspace: chain_adjoint_current stays as it is
+    return e->traj_vjp(h, status, gX, gU, g_x0, g_theta, h->chain_adjoint_current, (hipStream_t)stream);
 }
 
 }  // extern "C"
