@@ -1,4 +1,4 @@
-"""ctypes binding of libmpcrl_hip.so, read from include/mpcrl.h (and include/mpcrl_ext.h, include/mpcrl_chain_ext.h, include/mpcrl_traj_ext.h and include/mpcrl_chain_traj_ext.h, a table of its own each), and the one path the package calls the library through
+"""ctypes binding of libmpcrl_hip.so, read from include/mpcrl.h (and include/mpcrl_ext.h, include/mpcrl_chain_ext.h, include/mpcrl_traj_ext.h, include/mpcrl_chain_traj_ext.h and include/mpcrl_bound_ext.h, a table of its own each), and the one path the package calls the library through
 (``call``, ``workspace``).  Fails loudly when the library is missing.
 
 The .hip units include the same header, so the compiler holds the implementation to it; the prototypes, constants and error codes here
@@ -112,6 +112,13 @@ with open(CHAIN_TRAJ_EXT_HEADER_PATH) as _f:
     CHAIN_TRAJ_EXT_HEADER = parse_header(_f.read())      # a fifth table (the #include of mpcrl_ext.h is not followed)
 CHAIN_TRAJ_EXT_EXPORTS = list(CHAIN_TRAJ_EXT_HEADER.functions)
 CHAIN_TRAJ_EXT_VERSION = CHAIN_TRAJ_EXT_HEADER.constants["CHAIN_TRAJ_EXT_VERSION"]
+BOUND_EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mpcrl_bound_ext.h")   # the derivatives with respect to the box bounds, versioned on their own
+if not os.path.exists(BOUND_EXT_HEADER_PATH):
+    raise ImportError(f"mpc4rl_amd: {BOUND_EXT_HEADER_PATH} not found. The binding is read from the headers: keep include/ beside the package.")
+with open(BOUND_EXT_HEADER_PATH) as _f:
+    BOUND_EXT_HEADER = parse_header(_f.read())      # a sixth table (the #include of mpcrl_ext.h is not followed)
+BOUND_EXT_EXPORTS = list(BOUND_EXT_HEADER.functions)
+BOUND_EXT_VERSION = BOUND_EXT_HEADER.constants["BOUND_EXT_VERSION"]
 
 
 def _constants(names: str):
@@ -191,8 +198,17 @@ def load():
     if lib.mpcrl_chain_traj_ext_version() != CHAIN_TRAJ_EXT_VERSION and not os.environ.get("MPCRL_SKIP_ABI_CHECK"):
         raise RuntimeError(f"mpc4rl_amd: {LIB_PATH} reports chain trajectory extension version {lib.mpcrl_chain_traj_ext_version()}, this "
                            f"binding expects {CHAIN_TRAJ_EXT_VERSION}; rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`).")
+    older = bool(os.environ.get("MPCRL_SKIP_ABI_CHECK"))      # an A/B run against an older build: what it lacks is left unbound
+    if not (older and not hasattr(lib, "mpcrl_bound_ext_version")):
+        lib.mpcrl_bound_ext_version.restype = C.c_int
+    if not older and lib.mpcrl_bound_ext_version() != BOUND_EXT_VERSION:
+        raise RuntimeError(f"mpc4rl_amd: {LIB_PATH} reports bound extension version {lib.mpcrl_bound_ext_version()}, this binding expects "
+                           f"{BOUND_EXT_VERSION}; rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`).")
     for name, (ret, params) in (list(HEADER.functions.items()) + list(EXT_HEADER.functions.items()) + list(CHAIN_EXT_HEADER.functions.items())
-                                + list(TRAJ_EXT_HEADER.functions.items()) + list(CHAIN_TRAJ_EXT_HEADER.functions.items())):
+                                + list(TRAJ_EXT_HEADER.functions.items()) + list(CHAIN_TRAJ_EXT_HEADER.functions.items())
+                                + list(BOUND_EXT_HEADER.functions.items())):
+        if older and name in BOUND_EXT_HEADER.functions and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.restype = _CTYPE[ret]
         fn.argtypes = [_CTYPE.get(kind, C.c_void_p) for _, kind in params]

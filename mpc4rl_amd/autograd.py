@@ -22,6 +22,17 @@ still be that forward pass's: every ``forward``, ``q`` and ``trajectory`` of a l
 ``backward`` raises a RuntimeError when the counter is no longer the one its forward pass recorded ("one backward per forward, before
 the layer runs again").  Setters called on the batch directly (``set_theta``, ``set_iterate``, ``reset``, ``solve`` ...) between the
 forward and the backward pass are the caller's responsibility: the layer does not see them.
+
+``layer(x0, theta, bounds)`` and ``layer.trajectory(x0, theta, bounds)`` with ``bounds`` a ``BoxBounds`` of six tensors (the three
+groups of ``MPCBatch.set_bounds``, shared by the batch) also differentiate with respect to the box bounds (include/mpcrl_bound_ext.h):
+learned constraint back-offs.  The forward pass copies the six tensors to the host and calls ``set_bounds`` for the three groups — a
+HOST SYNCHRONISATION per forward pass, and the bounds stay set on the batch afterwards — then solves as above.  The backward pass of
+``trajectory`` is ONE ``MPCBatch.bound_vjp`` for everything that requires a gradient (x0, theta and the bounds: the same adjoint solve
+serves them all), the per-stage rows folded onto the groups (``fold_bound_grad``) and summed over the batch; that of ``forward`` adds,
+for the bounds, one ``bound_vjp`` with g_u as the cotangent on stage 0 of U* plus g_V dV/db (``bound_value_grad``: lam_l, -lam_u).
+Members of ``bounds`` that do not require a gradient get none; instances excluded from the theta gradient (status != 0) contribute
+zero; both backward passes read the stored iterate, so the pass-counter rule above covers them.  With ``bounds=None`` nothing changes:
+the layer makes the calls it made before.  ``layer.q`` takes no bounds.
 """
 from __future__ import annotations
 
@@ -29,7 +40,8 @@ from typing import Optional, Tuple
 
 import torch
 
-from .batch import MPCBatch
+from . import _lib
+from .batch import BoxBounds, MPCBatch
 
 
 def mpc_backward_terms(g_u: Optional[torch.Tensor], g_V: Optional[torch.Tensor], status: torch.Tensor,
@@ -160,6 +172,115 @@ class MPCTrajectoryFunction(torch.autograd.Function):
         return (None if g_x0 is None else g_x0.to(ctx.dtypes[0]), None if g_th is None else g_th.to(ctx.dtypes[1]), None)
 
 
+def _apply_bounds(mpc, bounds) -> None:
+    """The six tensors of a BoxBounds to the host and into the handle (three ``set_bounds``): a host synchronisation."""
+    host = [b.detach().to(torch.float64).cpu().numpy() for b in bounds]
+    mpc.set_bounds(_lib.BOUNDS_U0, host[0], host[1])
+    mpc.set_bounds(_lib.BOUNDS_STAGE, host[2], host[3])
+    mpc.set_bounds(_lib.BOUNDS_TERMINAL, host[4], host[5])
+
+
+def _bound_grads(mpc, g_lb, g_ub, good, needs, like):
+    """Per-stage bound gradients g_lb, g_ub [B, N+1, nu+nx] -> the six gradients of a BoxBounds (None where not needed): rows of
+    instances outside ``good`` selected out, folded onto the groups of ``set_bounds`` and summed over the batch; ``like``: the
+    (device, dtype) of each member (the bounds may live on the host)."""
+    out = []
+    for g in (g_lb, g_ub):
+        g = torch.where(good.reshape(-1, 1, 1), g, torch.zeros_like(g))
+        out.append([t.sum(0) for t in mpc.fold_bound_grad(g)])
+    six = (out[0][0], out[1][0], out[0][1], out[1][1], out[0][2], out[1][2])      # lb0, ub0, lb, ub, lbe, ube
+    return tuple(g.to(device=dev, dtype=dt) if need else None for g, need, (dev, dt) in zip(six, needs, like))
+
+
+def _stale(ctx, what: str):
+    if ctx.layer.pass_counter != ctx.pass_id:
+        raise RuntimeError(f"MPCLayer.{what}: the backward pass reads the iterate its forward pass stored in the handle, and the "
+                           "layer has run another forward, q or trajectory since (pass counter "
+                           f"{ctx.layer.pass_counter}, recorded {ctx.pass_id}): one backward per forward, before the layer runs again.")
+
+
+class MPCBoundedFunction(torch.autograd.Function):
+    """``MPCFunction`` with the box bounds as inputs: (x0, theta, lb0, ub0, lb, ub, lbe, ube) -> (u0, V).  The x0 and theta sides
+    are ``MPCFunction``'s; the bounds' gradient is one ``MPCBatch.bound_vjp`` (g_u on stage 0 of U*) plus g_V dV/db."""
+
+    @staticmethod
+    def forward(ctx, x0, theta, lb0, ub0, lb, ub, lbe, ube, layer):
+        mpc: MPCBatch = layer.batch
+        need_x, need_p, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2:8]
+        _apply_bounds(mpc, (lb0, ub0, lb, ub, lbe, ube))
+        mpc.set_theta(theta.detach().to(torch.float64))
+        r = mpc.solve(x0.detach().to(torch.float64), sens_v=need_p, sens_pi=need_p, **layer.solve_args)
+        s = mpc.state_sens(q_mode=False, value=True, policy=layer.has_policy_jacobian) if need_x else None
+        layer.last_status = r.status
+        ctx.set_materialize_grads(False)
+        ctx.layer, ctx.pass_id = layer, layer.pass_counter
+        ctx.shared = theta.dim() == 1
+        ctx.dtypes, ctx.like = (x0.dtype, theta.dtype), tuple((b.device, b.dtype) for b in (lb0, ub0, lb, ub, lbe, ube))
+        ctx.policy, ctx.chain = layer.has_policy_jacobian, layer.batch.ocp.name.startswith("chain")
+        ctx.jac = (r.status, None if s is None else s.dpi_dx0, None if s is None else s.dV_dx0, r.dpi_dp, r.dV_dp)
+        ctx.dV_db = mpc.bound_value_grad(q_mode=False) if any(need_b) else None
+        return r.u0.to(x0.dtype), r.V.to(x0.dtype)
+
+    @staticmethod
+    def backward(ctx, g_u, g_V):
+        status, du_dx0, dV_dx0, du_dp, dV_dp = ctx.jac
+        need_b = ctx.needs_input_grad[2:8]
+        if g_u is not None and ctx.needs_input_grad[0] and not ctx.policy:
+            raise RuntimeError("MPCLayer: the loss depends on u0 and x0 requires a gradient, but du0*/dx0 is not available: build the layer "
+                               "with policy_jacobian=True, detach x0 or keep u0 out of the loss.")
+        f64 = [None if g is None else g.to(torch.float64) for g in (g_u, g_V)]
+        g_x0, g_th = mpc_backward_terms(f64[0], f64[1], status, du_dx0, dV_dx0, du_dp, dV_dp, ctx.shared)
+        g_b = (None,) * 6
+        if any(need_b) and (g_u is not None or g_V is not None):
+            mpc = ctx.layer.batch
+            g_lb = g_ub = None
+            if g_u is not None:
+                _stale(ctx, "forward")
+                gU = torch.zeros((mpc.B, mpc.N, mpc.nu), dtype=torch.float64, device=f64[0].device)
+                gU[:, 0] = f64[0]
+                g_lb, g_ub = mpc.bound_vjp(None, gU, x0=False, theta=False, bounds=True)[2:]
+            if g_V is not None:
+                dlb, dub = (f64[1].reshape(-1, 1, 1) * d for d in ctx.dV_db)
+                g_lb, g_ub = (dlb, dub) if g_lb is None else (g_lb + dlb, g_ub + dub)
+            g_b = _bound_grads(mpc, g_lb, g_ub, status == 0, need_b, ctx.like)
+        return (None if g_x0 is None or not ctx.needs_input_grad[0] else g_x0.to(ctx.dtypes[0]),
+                None if g_th is None or not ctx.needs_input_grad[1] else g_th.to(ctx.dtypes[1])) + g_b + (None,)
+
+
+class MPCBoundedTrajectoryFunction(torch.autograd.Function):
+    """``MPCTrajectoryFunction`` with the box bounds as inputs: (x0, theta, lb0, ub0, lb, ub, lbe, ube) -> (X, U); ``backward`` is one
+    ``MPCBatch.bound_vjp`` for everything that requires a gradient."""
+
+    @staticmethod
+    def forward(ctx, x0, theta, lb0, ub0, lb, ub, lbe, ube, layer):
+        mpc = layer.batch
+        _apply_bounds(mpc, (lb0, ub0, lb, ub, lbe, ube))
+        mpc.set_theta(theta.detach().to(torch.float64))
+        r = mpc.solve(x0.detach().to(torch.float64), **layer.solve_args)
+        X, U = mpc.get_iterate()[:2]
+        layer.last_status = r.status
+        ctx.set_materialize_grads(False)
+        ctx.layer, ctx.pass_id, ctx.status = layer, layer.pass_counter, r.status
+        ctx.shared = theta.dim() == 1
+        ctx.dtypes, ctx.like = (x0.dtype, theta.dtype), tuple((b.device, b.dtype) for b in (lb0, ub0, lb, ub, lbe, ube))
+        return X.to(x0.dtype), U.to(x0.dtype)
+
+    @staticmethod
+    def backward(ctx, g_X, g_U):
+        need_x, need_p, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2:8]
+        if (g_X is None and g_U is None) or not (need_x or need_p or any(need_b)):
+            return (None,) * 9
+        _stale(ctx, "trajectory")
+        mpc = ctx.layer.batch
+        g_x0, g_th, g_lb, g_ub = mpc.bound_vjp(None if g_X is None else g_X.to(torch.float64), None if g_U is None else g_U.to(torch.float64),
+                                               x0=need_x, theta=need_p, bounds=any(need_b))
+        if g_th is not None and ctx.shared:
+            g_th = g_th.sum(0)
+        # the rows bound_vjp keeps are those its model's trajectory VJP keeps (the chain: statuses 0 and 2): the bounds take the same
+        g_b = _bound_grads(mpc, g_lb, g_ub, torch.ones_like(ctx.status, dtype=torch.bool), need_b, ctx.like) if any(need_b) else (None,) * 6
+        return (None if g_x0 is None else g_x0.to(ctx.dtypes[0]), None if g_th is None else g_th.to(ctx.dtypes[1])) + g_b + (None,)
+
+
 class MPCLayer(torch.nn.Module):
     """``layer(x0, theta) -> (u0, V)``, ``layer.q(x0, u0, theta) -> Q`` and ``layer.trajectory(x0, theta) -> (X, U)`` around one
     ``MPCBatch`` (its batch size is the layer's).  ``pass_counter``: incremented by each of the three (the staleness rule of
@@ -177,14 +298,21 @@ class MPCLayer(torch.nn.Module):
         self.last_status = None
         self.pass_counter = 0
 
-    def forward(self, x0: torch.Tensor, theta: torch.Tensor):
+    def forward(self, x0: torch.Tensor, theta: torch.Tensor, bounds: Optional[BoxBounds] = None):
+        """``bounds``: a BoxBounds whose members may require a gradient (a host synchronisation per call, see the module's docstring);
+        None = the bounds the batch has, as constants."""
         self.pass_counter += 1
-        return MPCFunction.apply(x0, theta, self)
+        if bounds is None:
+            return MPCFunction.apply(x0, theta, self)
+        return MPCBoundedFunction.apply(x0, theta, *BoxBounds(*bounds), self)
 
     def q(self, x0: torch.Tensor, u0: torch.Tensor, theta: torch.Tensor) -> torch.Tensor:
         self.pass_counter += 1
         return MPCQFunction.apply(x0, u0, theta, self)
 
-    def trajectory(self, x0: torch.Tensor, theta: torch.Tensor):
+    def trajectory(self, x0: torch.Tensor, theta: torch.Tensor, bounds: Optional[BoxBounds] = None):
+        """``bounds``: as in ``forward``."""
         self.pass_counter += 1
-        return MPCTrajectoryFunction.apply(x0, theta, self)
+        if bounds is None:
+            return MPCTrajectoryFunction.apply(x0, theta, self)
+        return MPCBoundedTrajectoryFunction.apply(x0, theta, *BoxBounds(*bounds), self)

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -34,6 +34,17 @@ class StateSens:
     dV_dx0: Optional[torch.Tensor]    # [B, nx]      dV/dx0, or dQ/dx0 when the solve had u0 fixed
     dQ_du0: Optional[torch.Tensor]    # [B, nu]      Q mode only
     dpi_dx0: Optional[torch.Tensor]   # [B, nu, nx]  du0*/dx0 (zeros in Q mode)
+
+
+class BoxBounds(NamedTuple):
+    """The box bounds of an OCP as tensors, the three groups of ``MPCBatch.set_bounds`` (shared by the batch, as the handle's bounds
+    are): stage-0 controls, stages 1 .. N-1 in stage-vector order v = [u; x], terminal states.  |bound| >= 1e29 = absent."""
+    lb0: torch.Tensor     # [nu]
+    ub0: torch.Tensor     # [nu]
+    lb: torch.Tensor      # [nu + nx]
+    ub: torch.Tensor      # [nu + nx]
+    lbe: torch.Tensor     # [nx]
+    ube: torch.Tensor     # [nx]
 
 
 class MPCBatch:
@@ -303,6 +314,69 @@ class MPCBatch:
         g_th = torch.empty((self.B, self.n_p), **kw) if theta else None
         self._call("mpcrl_chain_traj_vjp", 0, self._solve_status, gX, gU, g_x0, g_th)
         return g_x0, g_th
+
+    def bound_value_grad(self, q_mode: bool = False):
+        """(dV_dlb, dV_dub), each [B, N+1, nu+nx] in stage-vector order v = [u; x] (the layout of one plane of ``get_iterate``'s bnd):
+        the derivative of the last solve's value (of Q after a solve with u0 fixed: q_mode) with respect to the lower / upper bound of
+        every stage and coordinate, lam_l and -lam_u (include/mpcrl_bound_ext.h mpcrl_bound_value_grad).  One entry per stage: sum
+        them onto the groups of ``set_bounds`` with ``fold_bound_grad``.  Exactly zero where no bound row exists (absent bounds,
+        stage-0 states, terminal controls, in Q mode the stage-0 controls).  Every model.  Rows of instances whose status is neither
+        0 nor 2 are zeros."""
+        if not (self.has_iterate and self.duals_valid):
+            raise RuntimeError("bound_value_grad needs the iterate of a solve with its bound multipliers (solve with store_bounds=True first)")
+        kw = dict(dtype=torch.float64, device=self.device)
+        shape = (self.B, self.N + 1, self.nu + self.nx)
+        dlb, dub = torch.empty(shape, **kw), torch.empty(shape, **kw)
+        self._call("mpcrl_bound_value_grad", _lib.STATE_Q_MODE if q_mode else 0, dlb, dub)
+        st = self._solve_status
+        if st is not None:      # as in state_sens: the library sees the stored iterate, not the status word
+            good = ((st == 0) | (st == 2)).reshape(self.B, 1, 1)
+            dlb, dub = (torch.where(good, t, torch.zeros_like(t)) for t in (dlb, dub))
+        return dlb, dub
+
+    def bound_vjp(self, gX=None, gU=None, x0: bool = True, theta: bool = True, bounds: bool = True):
+        """(g_x0 [B, nx], g_theta [B, n_p], g_lb, g_ub [B, N+1, nu+nx]; None where not asked for): ``trajectory_vjp`` /
+        ``chain_trajectory_vjp`` — whichever the model has — with the cotangents also pulled back to the box bounds, every stage and
+        coordinate of v = [u; x] on its own (include/mpcrl_bound_ext.h mpcrl_bound_vjp / mpcrl_chain_bound_vjp): the same ONE adjoint
+        solve per instance serves all four.  g_lb / g_ub are exactly zero where no bound row exists; ``fold_bound_grad`` sums them
+        onto the groups of ``set_bounds``.  The conditions and the rows that are zeros are those of the model's trajectory VJP."""
+        name = "chain_trajectory_vjp" if self._is_chain else "trajectory_vjp"
+        if not (self.has_iterate and self.duals_valid):
+            raise RuntimeError(f"{name} needs the iterate of a solve with its bound multipliers (solve with store_bounds=True first)")
+        if self._solve_status is not None and self._solve_q_mode:
+            raise RuntimeError(f"{name} after a solve with u0 fixed (Q mode) is not available")
+        if self._is_chain and (not self._chain_ws_current or self._solve_status is None):
+            raise RuntimeError("chain_trajectory_vjp reads the workspace of the last solve, and the handle was changed since (set_theta, "
+                               "set_bounds, set_discount_factor, reset or set_iterate): solve again first")
+        if gX is None and gU is None:
+            raise ValueError(f"{name} needs a cotangent: gX, gU or both")
+        if not (x0 or theta or bounds):
+            raise ValueError("bound_vjp needs an output: x0, theta, bounds or any of them")
+        gX = None if gX is None else self._dev(gX, (self.B, self.N + 1, self.nx))
+        gU = None if gU is None else self._dev(gU, (self.B, self.N, self.nu))
+        kw = dict(dtype=torch.float64, device=self.device)
+        g_x0 = torch.empty((self.B, self.nx), **kw) if x0 else None
+        g_th = torch.empty((self.B, self.n_p), **kw) if theta else None
+        g_lb = torch.empty((self.B, self.N + 1, self.nu + self.nx), **kw) if bounds else None
+        g_ub = torch.empty((self.B, self.N + 1, self.nu + self.nx), **kw) if bounds else None
+        if self._is_chain:
+            self._call("mpcrl_chain_bound_vjp", 0, self._solve_status, gX, gU, g_x0, g_th, g_lb, g_ub)
+            return g_x0, g_th, g_lb, g_ub
+        self._call("mpcrl_bound_vjp", 0, gX, gU, g_x0, g_th, g_lb, g_ub)
+        st = self._solve_status
+        if st is not None:      # as in trajectory_vjp: the library sees the stored iterate, not the status word
+            good = st == 0
+            g_x0, g_th, g_lb, g_ub = (None if t is None else torch.where(good.reshape((self.B,) + (1,) * (t.dim() - 1)), t, torch.zeros_like(t))
+                                      for t in (g_x0, g_th, g_lb, g_ub))
+        return g_x0, g_th, g_lb, g_ub
+
+    def fold_bound_grad(self, g: torch.Tensor):
+        """A per-stage bound gradient g [B, N+1, nu+nx] (``bound_vjp``, ``bound_value_grad``) summed onto the three groups of
+        ``set_bounds``: (U0 [B, nu]: the controls of stage 0, STAGE [B, nu+nx]: stages 1 .. N-1, TERMINAL [B, nx]: the states of
+        stage N).  Tensors only: runs on any device."""
+        if g.dim() != 3 or g.shape[1] != self.N + 1 or g.shape[2] != self.nu + self.nx:
+            raise ValueError(f"a bound gradient is [B, {self.N + 1}, {self.nu + self.nx}]")
+        return g[:, 0, :self.nu], g[:, 1:self.N].sum(1), g[:, self.N, self.nu:]
 
     def get_action(self, x0) -> torch.Tensor:
         """Batched MPC.get_action (mpc.py:27-50)."""

@@ -84,9 +84,12 @@ int launch_policy_state_sens(MpcrlSolver *h, const int32_t *status, double *dpi_
 // workspace after a solve that ran MPCRL_SENS_PI in V mode; otherwise the second-order point pass and chain_sens_ad first, as above.
 // Then the adjoint solve for the cotangent, the mixed term of its one solution (only g_theta reads it) and the outputs.  Every
 // dynamic-LDS request is at most the du0*/dp pass's (LargeLds: one solution staged instead of 1 + NU).
+// g_lb / g_ub (include/mpcrl_bound_ext.h, mpcrl_chain_bound_vjp; both null for mpcrl_chain_traj_vjp): one launch more, of
+// chain_bound_out_kernel on the solution the adjoint solve left, when either is requested; g_x0 and g_theta may then both be null,
+// and chain_traj_out_kernel runs only when one of them is requested.
 template <class M>
 int launch_traj_vjp(MpcrlSolver *h, const int32_t *status, const double *gX, const double *gU, double *g_x0, double *g_theta,
-                    bool adjoint_current, hipStream_t st) {
+                    double *g_lb, double *g_ub, bool adjoint_current, hipStream_t st) {
     const int B = h->B, N = h->N;
     const LargeLds<M> lds(N);
     if (!lds.fits()) return MPCRL_E_ARG;   // (mpcrl_create has checked: not reached)
@@ -103,7 +106,9 @@ int launch_traj_vjp(MpcrlSolver *h, const int32_t *status, const double *gX, con
     if (g_theta)
         hipLaunchKernelGGL((chain_sens_mix2_kernel<M, 1>), dim3((unsigned)(((long)B * N + 63) / 64)), dim3(64), lds.mix2, st, h->large, a);
     const unsigned lds_out = (unsigned)((64 + 2 * ((N + 1) * M::NX + N * M::NU)) * sizeof(double));
-    hipLaunchKernelGGL(chain_traj_out_kernel<M>, dim3((unsigned)B), dim3(1024), lds_out, st, h->large, a, gX, g_x0, g_theta);
+    if (g_x0 || g_theta)
+        hipLaunchKernelGGL(chain_traj_out_kernel<M>, dim3((unsigned)B), dim3(1024), lds_out, st, h->large, a, gX, g_x0, g_theta);
+    if (g_lb || g_ub) hipLaunchKernelGGL(chain_bound_out_kernel<M>, dim3((unsigned)B), dim3(64), 0, st, h->large, a, g_lb, g_ub);
     HIP_OK(hipGetLastError());
     return 0;
 }

@@ -12,6 +12,7 @@
 //   chain_traj_riccati        wavefront per instance: the same factorisation, ONE adjoint solve for a cotangent on the whole plan
 //   chain_sens_mix2<M, 1>     lane per (instance, stage): the mixed term of that one solution
 //   chain_traj_out            workgroup per instance: g_theta and g_x0
+//   chain_bound_out           wavefront per instance: g_lb and g_ub of include/mpcrl_bound_ext.h from the same solution
 // They re-use [B A], lam, t, nu left in the workspace by the last SQP round (its linearisation is at the final iterate).
 #pragma once
 #include "chain_linearise.hpp"
@@ -705,6 +706,59 @@ __global__ void __launch_bounds__(1024) chain_traj_out_kernel(const LargeSpec sp
         for (int r = 0; r < NX; ++r) acc = fma(Tdnu[r], BA0[r * NW + NU + tid], acc);
         const double g0 = gX ? gX[(size_t)inst * (N + 1) * NX + tid] : 0.0;
         gx[tid] = sens_ok ? g0 - acc : NAN;
+    }
+}
+
+// The bound outputs of include/mpcrl_bound_ext.h (mpcrl_chain_bound_vjp) from the ONE solution y chain_traj_riccati_kernel left in
+// Tdx / Tdu: a bound of side sd on coordinate i of stage k enters the KKT residual through its own row h + t alone (dR/db = -sgn), and
+// with (lam, t) of that row eliminated
+//     G' dw*/dlb[k, i] = (lam_l / t_l)[k, i] y_v[k, i],     G' dw*/dub[k, i] = (lam_u / t_u)[k, i] y_v[k, i]
+// with the weight that kernel's factorisation used, min(LAM / TT, SENS_W_MAX) of the workspace, and its has() / skipc() (V mode: the
+// bounds staged in LDS as ChainSolver::setup stages them).  One wavefront per instance, a lane per entry in strides of 64: no sums,
+// every entry is one product stored by one lane, so the same workspace gives the same bits.  Every requested row is written in full by
+// every call: the values for status 0 / 2, zeros otherwise and where no bound row exists, NaN where the factorisation was not pd.
+template <class M>
+__global__ void __launch_bounds__(64) chain_bound_out_kernel(const LargeSpec sp, const LargeArgs a, double *__restrict__ g_lb,
+                                                             double *__restrict__ g_ub) {
+    constexpr int NX = M::NX, NU = M::NU, NW = NX + NU;
+    __shared__ double sb[4 * NW + 8];   // lb, ub (stages 1 .. N - 1), lbe, ube: NW each; lb0, ub0: 4 each
+    const int N = sp.N, inst = blockIdx.x, lane = threadIdx.x, ne = (N + 1) * NW;
+    double *ol = g_lb ? g_lb + (size_t)inst * ne : nullptr, *ou = g_ub ? g_ub + (size_t)inst * ne : nullptr;
+    const int status = a.status[inst];
+    if (!(status == 0 || status == 2)) {
+        for (int e = lane; e < ne; e += 64) {
+            if (ol) ol[e] = 0.0;
+            if (ou) ou[e] = 0.0;
+        }
+        return;
+    }
+    if (lane == 0) {   // one lane, compile-time indices: the kernel arguments stay scalar operands
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+            sb[i] = sp.lb[i], sb[NW + i] = sp.ub[i];
+            sb[2 * NW + i] = i >= NU ? sp.lbe[i >= NU ? i - NU : 0] : -1e30, sb[3 * NW + i] = i >= NU ? sp.ube[i >= NU ? i - NU : 0] : 1e30;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sb[4 * NW + i] = sp.lb0[i], sb[4 * NW + 4 + i] = sp.ub0[i];
+    }
+    wave_sync();
+    const LargeLayout<M> lay(N);
+    const double *w = a.ws + (size_t)inst * a.ws_stride;
+    const double *lam = w + lay.lamw, *tt = w + lay.tw, *Tdx = w + lay.Tdx, *Tdu = w + lay.Tdu;
+    const bool sens_ok = w[lay.state + ST_TRAJ] == 0.0;
+    for (int e = lane; e < ne; e += 64) {
+        const int k = e / NW, i = e - k * NW;
+        double lo, hi;      // ChainSolver::lbv / ubv in V mode
+        if (k == 0)
+            lo = i < NU ? sb[4 * NW + (i < NU ? i : 0)] : -1e30, hi = i < NU ? sb[4 * NW + 4 + (i < NU ? i : 0)] : 1e30;
+        else if (k == N)
+            lo = i >= NU ? sb[2 * NW + i] : -1e30, hi = i >= NU ? sb[3 * NW + i] : 1e30;
+        else
+            lo = sb[i], hi = sb[NW + i];
+        const bool skip = k == N && i < NU;
+        const double y = i < NU ? (k < N ? Tdu[k * NU + i] : 0.0) : Tdx[k * NX + i - NU];
+        if (ol) ol[e] = (!skip && lo > -NO_BOUND) ? (sens_ok ? fmin(lam[e] / tt[e], SENS_W_MAX) * y : NAN) : 0.0;
+        if (ou) ou[e] = (!skip && hi < NO_BOUND) ? (sens_ok ? fmin(lam[ne + e] / tt[ne + e], SENS_W_MAX) * y : NAN) : 0.0;
     }
 }
 

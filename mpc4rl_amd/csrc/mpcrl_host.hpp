@@ -72,9 +72,10 @@ struct MpcrlChainEntry {
     // du0*/dx0 of the last solve (mpcrl_chain_policy_state_sens): the contraction alone, or the adjoint pipeline in front of it
     int (*policy_state_sens)(MpcrlSolver *h, const int32_t *status, double *dpi_dx0, bool adjoint_current, hipStream_t st);
     // trajectory VJP of the last solve (mpcrl_chain_traj_vjp): the adjoint solve for the cotangent and its contractions, the
-    // second-order point pass and the exact Hessians in front of them unless that solve left them
+    // second-order point pass and the exact Hessians in front of them unless that solve left them; g_lb / g_ub (mpcrl_chain_bound_vjp,
+    // null for mpcrl_chain_traj_vjp): the bound rows contracted with the same solution, one launch more
     int (*traj_vjp)(MpcrlSolver *h, const int32_t *status, const double *gX, const double *gU, double *g_x0, double *g_theta,
-                    bool adjoint_current, hipStream_t st);
+                    double *g_lb, double *g_ub, bool adjoint_current, hipStream_t st);
 };
 const MpcrlChainEntry *mpcrl_chain_entry_3(), *mpcrl_chain_entry_4(), *mpcrl_chain_entry_5(), *mpcrl_chain_entry_6(), *mpcrl_chain_entry_7();
 // n_mass (3 .. 7, a free integer in the reference: rlmpc/mpc/chain_mass/ocp_utils.py:344-350) -> the translation unit of that chain size

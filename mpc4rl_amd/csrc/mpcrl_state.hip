@@ -1,14 +1,17 @@
 // mpcrl_state.hip — include/mpcrl_ext.h: state sensitivities of a solve (dV/dx0, dQ/du0, du0*/dx0) from the iterate the handle
 // stores; include/mpcrl_chain_ext.h and include/mpcrl_chain_traj_ext.h: du0*/dx0 and the trajectory VJP of the chain, from the workspace
-// of its last solve (kernels and launches: chain_sens.hpp, chain_inst.hip).  The kernels are state_sens_kernel.hpp; this unit instantiates them for the cartpole, the linear system and every chain
+// of its last solve (kernels and launches: chain_sens.hpp, chain_inst.hip); include/mpcrl_bound_ext.h: the derivatives with respect to
+// the box bounds (bound_vjp_kernel.hpp, and the chain's launcher with its bound outputs).  The kernels are state_sens_kernel.hpp; this unit instantiates them for the cartpole, the linear system and every chain
 // size, and launches them.  Nothing here allocates or waits: two launches (or one and a memset) on the caller's stream.
 #include "mpcrl_host.hpp"
 
 #include "../../include/mpcrl_chain_ext.h"
 #include "../../include/mpcrl_chain_traj_ext.h"
+#include "../../include/mpcrl_bound_ext.h"
 #include "../../include/mpcrl_traj_ext.h"
 #include "state_sens_kernel.hpp"
 #include "traj_vjp_kernel.hpp"
+#include "bound_vjp_kernel.hpp"
 
 using namespace mpcrl;
 
@@ -53,6 +56,40 @@ int launch_traj_vjp(const MpcrlSolver *h, const TrajVjpArgs &a, hipStream_t st) 
     hipLaunchKernelGGL((small_traj_vjp_kernel<M, false>), grid, wave, 0, st, h->small, a);
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+template <class M>
+int launch_bound_vjp(const MpcrlSolver *h, const BoundVjpArgs &a, hipStream_t st) {   // the dispatch of launch_traj_vjp
+    constexpr SmallTraits T = small_traits<M>();
+    const int ipw = std::min(64 / (h->N + 1), T.max_ipw);
+    const dim3 grid((unsigned)((h->B + ipw - 1) / ipw)), wave(64);
+    if constexpr (!T.seg_skip) {
+        if (seg_short(T, h->N)) {
+            hipLaunchKernelGGL((small_bound_vjp_kernel<M, true>), grid, wave, 0, st, h->small, a);
+            HIP_OK(hipGetLastError());
+            return 0;
+        }
+    }
+    hipLaunchKernelGGL((small_bound_vjp_kernel<M, false>), grid, wave, 0, st, h->small, a);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+template <class M>
+int launch_bound_value(const MpcrlSolver *h, const BoundValueArgs &a, hipStream_t st) {
+    hipLaunchKernelGGL(bound_value_grad_kernel<M>, dim3((unsigned)h->B), dim3(64), 0, st, a);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// which bound rows the handle's OCP has, per group of mpcrl_set_bounds (the rule of SmallSolver::init_bounds / ChainSolver::lbv)
+template <class Spec>
+void bound_rows_of(const Spec &sp, int nu, int nx, bool qmode, unsigned char (&rows)[3][BOUND_MAXNW]) {
+    for (int i = 0; i < nu + nx; ++i) {
+        rows[0][i] = (i < nu && !qmode) ? (sp.lb0[i] > -MPCRL_NO_BOUND * 0.1 ? 1 : 0) | (sp.ub0[i] < MPCRL_NO_BOUND * 0.1 ? 2 : 0) : 0;
+        rows[1][i] = (sp.lb[i] > -MPCRL_NO_BOUND * 0.1 ? 1 : 0) | (sp.ub[i] < MPCRL_NO_BOUND * 0.1 ? 2 : 0);
+        rows[2][i] = i >= nu ? (sp.lbe[i - nu] > -MPCRL_NO_BOUND * 0.1 ? 1 : 0) | (sp.ube[i - nu] < MPCRL_NO_BOUND * 0.1 ? 2 : 0) : 0;
+    }
 }
 
 }  // namespace
@@ -149,7 +186,64 @@ int mpcrl_chain_traj_vjp(mpcrl_handle h, int flags, const int32_t *status, const
     if (!e) return MPCRL_E_MODEL;
     ON_DEVICE(h->device);
     // the solution and its parameter terms have a region of their own in the workspace: chain_adjoint_current stays as it is
-    return e->traj_vjp(h, status, gX, gU, g_x0, g_theta, h->chain_adjoint_current, (hipStream_t)stream);
+    return e->traj_vjp(h, status, gX, gU, g_x0, g_theta, nullptr, nullptr, h->chain_adjoint_current, (hipStream_t)stream);
+}
+
+int mpcrl_bound_ext_version(void) { return MPCRL_BOUND_EXT_VERSION; }
+
+int mpcrl_bound_value_grad(mpcrl_handle h, int flags, double *dV_dlb, double *dV_dub, void *stream) {
+    if (!h || (flags & ~MPCRL_STATE_Q_MODE)) return MPCRL_E_ARG;
+    if (!h->have_iterate || h->dual_cold) return MPCRL_E_ARG;
+    if (!dV_dlb && !dV_dub) return MPCRL_E_ARG;
+    if (h->nu + h->nx > BOUND_MAXNW) return MPCRL_E_MODEL;   // (no model has more: not reached)
+    ON_DEVICE(h->device);
+    const hipStream_t st = (hipStream_t)stream;
+    BoundValueArgs a{};
+    a.B = h->B, a.N = h->N, a.theta_stride = h->theta_stride, a.qmode = (flags & MPCRL_STATE_Q_MODE) != 0, a.theta = h->theta;
+    a.X = h->X, a.U = h->U, a.PI = h->PI, a.BND = h->BND, a.RES = h->RES, a.dlb = dV_dlb, a.dub = dV_dub;
+    if (h->is_large) bound_rows_of(h->large, h->nu, h->nx, a.qmode, a.rows);
+    else bound_rows_of(h->small, h->nu, h->nx, a.qmode, a.rows);
+    if (h->model == MPCRL_MODEL_CARTPOLE) return launch_bound_value<CartpoleDev>(h, a, st);
+    if (h->model == MPCRL_MODEL_LINEAR) return launch_bound_value<LinearDev>(h, a, st);
+    switch (h->n_mass) {
+        case 3: return launch_bound_value<ChainDev<3>>(h, a, st);
+        case 4: return launch_bound_value<ChainDev<4>>(h, a, st);
+        case 5: return launch_bound_value<ChainDev<5>>(h, a, st);
+        case 6: return launch_bound_value<ChainDev<6>>(h, a, st);
+        case 7: return launch_bound_value<ChainDev<7>>(h, a, st);
+    }
+    return MPCRL_E_MODEL;
+}
+
+int mpcrl_bound_vjp(mpcrl_handle h, int flags, const double *gX, const double *gU, double *g_x0, double *g_theta, double *g_lb,
+                    double *g_ub, void *stream) {
+    if (!h || flags) return MPCRL_E_ARG;   // (MPCRL_STATE_Q_MODE included, as in mpcrl_traj_vjp)
+    if (h->is_large) return MPCRL_E_MODEL;
+    if (!h->have_iterate || h->dual_cold) return MPCRL_E_ARG;
+    if ((!gX && !gU) || (!g_x0 && !g_theta && !g_lb && !g_ub)) return MPCRL_E_ARG;
+    ON_DEVICE(h->device);
+    TrajVjpArgs t;
+    t.B = h->B, t.theta_stride = h->theta_stride, t.perm = h->have_perm ? h->perm : nullptr, t.theta = h->theta;
+    t.X = h->X, t.U = h->U, t.PI = h->PI, t.BND = h->BND, t.RES = h->RES;
+    t.gX = gX, t.gU = gU, t.g_x0 = g_x0, t.g_theta = g_theta;
+    if (!g_lb && !g_ub)   // the launch of mpcrl_traj_vjp itself: its bits
+        return h->model == MPCRL_MODEL_LINEAR ? launch_traj_vjp<LinearDev>(h, t, (hipStream_t)stream)
+                                              : launch_traj_vjp<CartpoleDev>(h, t, (hipStream_t)stream);
+    const BoundVjpArgs a{t, g_lb, g_ub};
+    return h->model == MPCRL_MODEL_LINEAR ? launch_bound_vjp<LinearDev>(h, a, (hipStream_t)stream)
+                                          : launch_bound_vjp<CartpoleDev>(h, a, (hipStream_t)stream);
+}
+
+int mpcrl_chain_bound_vjp(mpcrl_handle h, int flags, const int32_t *status, const double *gX, const double *gU, double *g_x0,
+                          double *g_theta, double *g_lb, double *g_ub, void *stream) {
+    if (!h || flags) return MPCRL_E_ARG;   // (MPCRL_STATE_Q_MODE included, as in mpcrl_chain_traj_vjp)
+    if (!h->is_large) return MPCRL_E_MODEL;
+    if (!status || (!gX && !gU) || (!g_x0 && !g_theta && !g_lb && !g_ub)) return MPCRL_E_ARG;
+    if (!h->chain_ws_current) return MPCRL_E_ARG;
+    const MpcrlChainEntry *e = chain_entry(h->n_mass);
+    if (!e) return MPCRL_E_MODEL;
+    ON_DEVICE(h->device);
+    return e->traj_vjp(h, status, gX, gU, g_x0, g_theta, g_lb, g_ub, h->chain_adjoint_current, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -13,6 +13,10 @@
 //
 // Lane layout, loads, the "solved" rule and the linearisation are those of small_state_sens_kernel; the Hessian assembly and the cap /
 // extrapolation block restate it so that du0*/dp, du0*/dx0 and this product describe one linearised KKT system.
+//
+// The kernel's body is small_traj_vjp_body<M, S, BOUNDS>: BOUNDS = false is this kernel, BOUNDS = true the kernel of
+// include/mpcrl_bound_ext.h (bound_vjp_kernel.hpp), which contracts the same solution with the bound rows as well.  Everything the
+// bound outputs add sits behind `if constexpr (BOUNDS)`, so this kernel's arithmetic and its order are untouched by it.
 #pragma once
 #include "state_sens_kernel.hpp"
 
@@ -29,8 +33,11 @@ struct TrajVjpArgs {
 
 // Every requested row is written in full: zeros for an instance without a solved iterate and at the entries of p the sensitivity pass
 // does not differentiate (M::p_has_gradient), NaN where the factorisation met a non-positive pivot.
-template <class M, bool SHORT = false>
-__global__ void __launch_bounds__(64) small_traj_vjp_kernel(const SmallSpec sp, const TrajVjpArgs a) {
+// g_lb / g_ub [B, N + 1, nu + nx] (BOUNDS only; either may be null): for the bound row of side sd on coordinate i of this stage's
+// v = [u; x], dR/db is -sgn in the row h + t of that bound alone, and eliminating (lam, t) leaves G' dw*/db = (lam / t) y_v[i] for
+// either side — with the weight the solve used, min(lam / t, SENS_W_MAX).  Exactly 0 where has() says there is no row.
+template <class M, bool SHORT, bool BOUNDS>
+MPCRL_DI void small_traj_vjp_body(const SmallSpec sp, const TrajVjpArgs a, double *g_lb, double *g_ub) {
     using SS = SmallSolver<M, SHORT>;
     constexpr int NX = M::NX, NU = M::NU, NW = NX + NU, NP = M::NP, NTD = M::NTD, NTC = M::NTC, NT = NTD + NTC;
     const int lane = threadIdx.x;
@@ -134,6 +141,33 @@ __global__ void __launch_bounds__(64) small_traj_vjp_kernel(const SmallSpec sp, 
 #pragma unroll
     for (int i = 0; i < NX; ++i) zero[i] = 0.0;
     bool okall = true;
+    // BOUNDS: the products w y_v of this stage's rows, from the solution (yx, yu) at the cap W and, where the instance extrapolates
+    // (ex), also from the one at W / 2 still in S.Dx / S.Du: each solve with its own capped weight, then 2 w1 y(W) - w2 y(W / 2).  On a
+    // capped row y = a / c + b / c^2 + ..., so c y = a + b / c: the extrapolation takes b / c out only if it acts on the product.
+    [[maybe_unused]] auto bound_rows = [&](const double *yx, const double *yu, bool ex) {
+        if constexpr (!BOUNDS) return;   // (and nothing is captured)
+        else {
+        if (!valid) return;
+        const size_t row = ((size_t)inst * (N + 1) + k) * NW;
+#pragma unroll
+        for (int sd = 0; sd < 2; ++sd) {
+            double *o = sd ? g_ub : g_lb;
+            if (!o) continue;   // (wave-uniform)
+#pragma unroll
+            for (int i = 0; i < NW; ++i) {
+                double v = 0.0;
+                if (S.has(sd, i)) {
+                    const double w = S.lam[sd][i] / S.t[sd][i];
+                    v = fmin(w, SENS_W_MAX) * S.dvc(yx, yu, i);
+                    if (ex) v = fma(2.0, v, -(fmin(w, 0.5 * SENS_W_MAX) * S.dvc(S.Dx, S.Du, i)));
+                    v = sv ? (okall ? v : NAN) : 0.0;
+                }
+                o[row + i] = v;
+            }
+        }
+        }
+    };
+    [[maybe_unused]] bool rows_done = false;   // (wave-uniform)
     if constexpr (SS::MX) {
         const bool okf = S.template mx_pred<true>(Hs, S.rt, zero);
         S.mx_dnu(S.rt, true);
@@ -158,6 +192,7 @@ __global__ void __launch_bounds__(64) small_traj_vjp_kernel(const SmallSpec sp, 
             S.mx_dnu(S.rt, true);
             const bool ok2 = seg_max<M::SEG_SKIP, SHORT>(okf2 ? 0.0 : 1.0, k, lpi, base) < 0.5;
             okall = okall && (ok2 || !extrap);
+            if constexpr (BOUNDS) bound_rows(y1x, &y1u, extrap), rows_done = true;   // (before the two solutions are merged)
             S.Du[0] = extrap ? fma(2.0, y1u, -S.Du[0]) : y1u;
 #pragma unroll
             for (int i = 0; i < NX; ++i)
@@ -168,6 +203,8 @@ __global__ void __launch_bounds__(64) small_traj_vjp_kernel(const SmallSpec sp, 
         okall = seg_max<M::SEG_SKIP, SHORT>(okf ? 0.0 : 1.0, k, lpi, base) < 0.5;
         S.forward_scan(zero);
     }
+    if constexpr (BOUNDS)
+        if (!rows_done) bound_rows(S.Dx, S.Du, false);
     double ynn[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) ynn[i] = lane_dn(S.Dnu[i]);
@@ -228,6 +265,11 @@ __global__ void __launch_bounds__(64) small_traj_vjp_kernel(const SmallSpec sp, 
     if (valid)
         for (int e = k; e < NP; e += lpi)
             if (!M::p_has_gradient(e)) a.g_theta[inst * NP + e] = 0.0;
+}
+
+template <class M, bool SHORT = false>
+__global__ void __launch_bounds__(64) small_traj_vjp_kernel(const SmallSpec sp, const TrajVjpArgs a) {
+    small_traj_vjp_body<M, SHORT, false>(sp, a, nullptr, nullptr);
 }
 
 }  // namespace mpcrl
