@@ -108,7 +108,8 @@ MPCRL_DI double lane_select(unsigned long long mask, double yes, double no) {
     asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(rh) : "v"(nh), "v"(yh), "s"(mask));
     return __hiloint2double(rh, rl);
 }
-constexpr unsigned long long LANES_C0 = 0x1111111111111111ull, LANES_C1 = 0x2222222222222222ull, LANES_C01 = 0x3333333333333333ull;   // lane & 3 == 0 / == 1 / < 2
+constexpr unsigned long long LANES_C0 = 0x1111111111111111ull, LANES_C1 = 0x2222222222222222ull;   // lane & 3 == 0 / == 1
+constexpr unsigned long long LANES_C13 = 0xaaaaaaaaaaaaaaaaull, LANES_C013 = 0xbbbbbbbbbbbbbbbbull;   // lane & 3 odd / != 2
 
 // segmented reductions over the LPI lanes of one instance; result broadcast to all of its lanes.  One tree for every reduction:
 // distances 32, 16, 8, 4, 2, 1, lane k takes its partner's value in when k + s < lpi, operands in the order (own, partner).
@@ -610,6 +611,7 @@ struct SmallSolver {
     //   X1 = mfma(P, A)            = P A                      Y  = mfma(P, W, pc) = [P B | p + P bb | P bb | 0]
     //   Q  = mfma(A, X1, Hxx + D)  = A' P A + Hxx + D_x       Zc = mfma(A, Y, [Hxu | g_x | 0 | 0]) = [S | mv_x | A' P bb | 0]  (columns)
     //   Zr = mfma(Y, A, [Hux; 0])  : row 0 = S'               Zb = mfma(BB, Y, [Huu + D_u | g_u | 0 | 0]): every row = [R, mv_u, beta, 0]
+    //   (as built, column 3 of pc, of both addends and hence of Y, Zc, Zb repeats column 1: its lanes store p_k, see mx_factor)
     //   K = S / R, kff = mv_u / R,  t = Zc - K Zb (own column): p_k in column 1, q_k = Acl_k' P_{k+1} bb_k in column 2,
     //   P = Q - K S' (one fma per element: S' arrives broadcast over the rows from an MFMA on the column-0 broadcast of Y),
     //   d_k = bb - B kff.  7 MFMAs + ~50 VALU per step instead of ~300 VALU instructions.
@@ -629,7 +631,7 @@ struct SmallSolver {
     //            overwrites the second member with P_k(r,c)
     //   [32,48)  per row r: (B[r], Hxu[r]) at 32 + 4 r — the factor sweep / the backward chain leave p_k[r] in the second member;
     //            (bb[r], g_x[r]) at 34 + 4 r — second member: d_k[r] after the factor sweep, then c_k[r], then the corrector's d_k[r]
-    //   [48,56)  per column c: ([Huu + D_u | g_u | 0 | 0][c], Hxu[c]) at 48 + 2 c — afterwards (q_k[c], Dx_k[c])
+    //   [48,56)  per column c: ([Huu + D_u | g_u | 0 | g_u][c], Hxu[c]) at 48 + 2 c — afterwards (q_k[c], Dx_k[c])
     //   56 K[4], 60 1/R (0 for a pinned u_0), 61 kff, 62 beta = B' P_{k+1} bb
     // After the 64 slots: one ok flag per block, and a write-only dump pair for lanes with nothing to store.
     static constexpr int mxAH = 0, mxCol = 32, mxRow = 48, mxK = 56, mxMisc = 60,
@@ -709,7 +711,7 @@ struct SmallSolver {
             const double hxu = hscale * Hs(NU + i, 0);
             lds_pair_store(sl + mxCol + 4 * i, Bm[i], hxu);
             lds_pair_store(sl + mxCol + 4 * i + 2, bb[i], g[NU + i]);
-            lds_pair_store(sl + mxRow + 2 * i, i == 0 ? fma(hscale, Hs(0, 0), Dg[0]) : (i == 1 ? g[0] : 0.0), hxu);
+            lds_pair_store(sl + mxRow + 2 * i, i == 0 ? fma(hscale, Hs(0, 0), Dg[0]) : (i == 2 ? 0.0 : g[0]), hxu);   // (g_u in columns 1 AND 3)
         }
     }
     // the factor sweep, all lanes in matrix layout.  WANT_P: also leave p_k of this right-hand side in the slots (adjoint solves
@@ -729,67 +731,79 @@ struct SmallSolver {
         const int oAH = mxAH + 2 * (4 * r + c), oCol = mxCol + 4 * r + (c >= 1 ? 2 : 0), oB = mxCol + 4 * r, oRow = mxRow + 2 * c;
         // store targets: slot-relative for lanes with something to store, else the dump pair (stride 0)
         double *const dump = ms + mxDump;   // (every lane its own dump word instead of one for all: measured, no difference)
-        const bool has1 = live && c < 3, has2 = live && r == 0 && c < 3, has3 = live && c == 1;
+        const bool has1 = live && (c < 3 || WANT_P), has2 = live && r == 0 && c < 3;
         double *const wP = live ? S0 + oAH + 1 : dump;
-        double *const w1 = has1 ? S0 + (c == 0 ? mxK + r : (c == 1 ? mxCol + 4 * r + 3 : mxRow + 2 * r)) : dump;   // K[r] | d[r] | q[r]
+        double *const w1 = has1 ? S0 + (c == 0 ? mxK + r : (c == 1 ? mxCol + 4 * r + 3 : (c == 2 ? mxRow + 2 * r : mxCol + 4 * r + 1))) : dump;   // K[r] | d[r] | q[r] | p[r]
         double *const w2 = has2 ? S0 + mxMisc + c : dump + 1;                                                      // 1/R | kff | beta
-        double *const w3 = has3 ? S0 + mxCol + 4 * r + 1 : dump;                                                   // p[r]
-        const int sL = live ? MSLOT : 0, s1 = has1 ? MSLOT : 0, s2 = has2 ? MSLOT : 0, s3 = has3 ? MSLOT : 0;
+        const int sL = live ? MSLOT : 0, s1 = has1 ? MSLOT : 0, s2 = has2 ? MSLOT : 0;
         double Pm, pcol;
         {
             const double *sl = S0 + N * MSLOT;
             Pm = sl[oAH + 1];
-            pcol = c == 1 ? sl[oCol + 1] : 0.0;   // g_x of the terminal stage (column 1)
+            pcol = (c & 1) ? sl[oCol + 1] : 0.0;   // g_x of the terminal stage (columns 1 and 3)
         }
-        double okacc = 1.0;             // > 0 while every pivot was positive
+        unsigned long long bad = 0;     // lanes that met a pivot that is not positive (NaN included)
         auto load = [&](MxOps &o, int kk) {
             const double *sl = S0 + (kk > 0 ? kk : 0) * MSLOT;
             o.ah = lds_pair(sl + oAH), o.cp = lds_pair(sl + oCol), o.rp = lds_pair(sl + oRow), o.Br = sl[oB];
         };
-        double sV1 = 0.0, sV2 = 0.0, sV3 = 0.0;   // results of a step
-        // the arithmetic of one step.  PIN: the step of stage 0 in Q-mode (u_0 pinned: K_0 = 0, kff_0 = 0, P_0 = Q)
+        double sV1 = 0.0, sV2 = 0.0;   // results of a step
+        // the arithmetic of one step.  Column 3 carries what column 1 carries (pcol, g_x in CZc and g_u in the published row vector are
+        // in both; W has bb there anyway), so its t is p_k bit for bit and the c == 3 lanes store it through w1: three stores a step.
+        // maypin: std::true_type for the step of stage 0, the only one that can be pinned (Q-mode: K_0 = 0, kff_0 = 0, P_0 = Q) — the
+        // sweep peels it, so that the other steps carry no select on it.  A pivot that is not positive (NaN included) and not pinned
+        // sets the lane's bit in `bad`: one compare into a scalar pair and one scalar or.
         auto head = [&](const MxOps &o, double &Y, double &X1) {
-            Y = mfma4(Pm, o.cp.x, pcol);          // column 3 of W is never read: bb there as well (no select)
+            Y = mfma4(Pm, o.cp.x, pcol);          // W = [B | bb | bb | bb]: columns 1 .. 3 load the same pair (no select)
             X1 = mfma4(Pm, o.ah.x, 0.0);
         };
-        auto tail = [&](const MxOps &o, double Y, double X1, bool pin) {
-            const double Am = o.ah.x, CZc = lane_select(LANES_C01, o.cp.y, 0.0);
+        auto tail = [&](const MxOps &o, double Y, double X1, auto maypin) {
+            const bool pin = decltype(maypin)::value && qmode;
+            const double Am = o.ah.x, CZc = lane_select(LANES_C013, o.cp.y, 0.0);
             const double Yb = quad_bcast<0>(Y);
             const double Zc = mfma4(Am, Y, CZc);
             const double Zb = mfma4(o.Br, Y, o.rp.x);
             const double Qt = mfma4(Am, X1, o.ah.y);
             const double Zr = mfma4(Yb, Am, o.rp.y);            // every row = S'
-            const double R = quad_bcast<0>(Zb), mvu = quad_bcast<1>(Zb), Sr = quad_bcast<0>(Zc);
-            okacc = (R > 0.0 || pin) ? okacc : 0.0;
-            const double Rinv = pin ? 0.0 : fast_rcp(R);
+            const double R = quad_bcast<0>(Zb), Sr = quad_bcast<0>(Zc);
+            double Rinv = fast_rcp(R);
+            if constexpr (decltype(maypin)::value) {
+                if (!pin) bad |= __builtin_amdgcn_ballot_w64(!(R > 0.0));
+                Rinv = pin ? 0.0 : Rinv;
+            } else
+                bad |= __builtin_amdgcn_ballot_w64(!(R > 0.0));
             const double Kr = Sr * Rinv;
             Pm = fma(-Kr, Zr, Qt);                              // P_k = Q - K S'
-            const double t = fma(-Kr, Zb, Zc);                  // own column: p_k (c = 1), q_k (c = 2)
-            pcol = lane_select(LANES_C1, t, 0.0);
-            const double kf = mvu * Rinv;
+            const double t = fma(-Kr, Zb, Zc);                  // own column: p_k (c = 1 and 3), q_k (c = 2)
+            pcol = lane_select(LANES_C13, t, 0.0);
+            const double kf = Zb * Rinv;                        // c = 1: kff = mv_u / R (kf and dk are kept in those lanes only)
             const double dk = fma(-o.Br, kf, o.cp.x);           // c = 1: bb[r] - B[r] kff
-            sV1 = lane_select(LANES_C0, Kr, lane_select(LANES_C1, dk, t));       // K[r] | d[r] | q[r]
+            sV1 = lane_select(LANES_C0, Kr, lane_select(LANES_C1, dk, t));       // K[r] | d[r] | q[r] | p[r]
             sV2 = lane_select(LANES_C0, Rinv, lane_select(LANES_C1, kf, Zb));    // 1/R | kff | beta
-            sV3 = t;
         };
         auto store = [&](int kk) {
             wP[kk * sL] = Pm;
             w1[kk * s1] = sV1;
             w2[kk * s2] = sV2;
-            if constexpr (WANT_P) w3[kk * s3] = sV3;
         };
         // the operands of a stage do not depend on the recursion: those of stage kk - 1 are fetched while stage kk is computed
         MxOps on;
         load(on, N - 1);
-        for (int kk = N - 1; kk >= 0; --kk) {
+        for (int kk = N - 1; kk >= 1; --kk) {
             const MxOps o = on;
             load(on, kk - 1);
             double Y, X1;
             head(o, Y, X1);
-            tail(o, Y, X1, kk == 0 && qmode);
+            tail(o, Y, X1, std::false_type());
             store(kk);
         }
-        if (live && r == 0 && c == 0) ms[mxFlag + blk] = okacc;
+        {
+            double Y, X1;
+            head(on, Y, X1);
+            tail(on, Y, X1, std::true_type());
+            store(0);
+        }
+        if (live && r == 0 && c == 0) ms[mxFlag + blk] = ((bad >> l) & 1ull) ? 0.0 : 1.0;
     }
     // One affine chain over the horizon on the matrix cores, all four columns of a block carrying the same vector:
     //   FWD   v_{k+1} = Acl_k v_k + d_k   (k = 0 .. N-1, v_0 = 0),    d_k at [35 + 4 r] of slot k, v_{k+1} -> [49 + 2 r] of slot k+1
