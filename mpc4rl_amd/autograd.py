@@ -33,6 +33,15 @@ for the bounds, one ``bound_vjp`` with g_u as the cotangent on stage 0 of U* plu
 Members of ``bounds`` that do not require a gradient get none; instances excluded from the theta gradient (status != 0) contribute
 zero; both backward passes read the stored iterate, so the pass-counter rule above covers them.  With ``bounds=None`` nothing changes:
 the layer makes the calls it made before.  ``layer.q`` takes no bounds.
+
+``MPCLayer(batch, cost_gradient=True)`` (cartpole only; off by default) also differentiates with respect to the tracking cost, the 80
+entries W_0, W, W_e, yref_0, yref, yref_e of theta (include/mpcrl_cost_ext.h; ``cartpole_cost_of`` / ``cartpole_theta`` split and join
+them): ``theta.grad`` then carries the cost block, which is exactly zero without the opt-in (dV/dp, du0*/dp and g_theta keep the
+convention of the reference's mirror, whose cost is not parameterised).  The backward pass of ``trajectory`` is ONE
+``MPCBatch.cost_vjp`` for x0, theta, the cost block and the bounds; ``forward`` adds g_V dV/dcost (``cost_value_grad``, computed in the
+forward pass when theta requires a gradient) plus, when g_u arrives, one ``cost_vjp`` with g_u as the cotangent on stage 0 of U* — the
+call that serves the bounds as well when they need a gradient; ``q`` adds g_Q dQ/dcost.  Instances with a status other than 0 are
+selected out, and the pass-counter rule covers the ``cost_vjp`` calls.
 """
 from __future__ import annotations
 
@@ -122,6 +131,7 @@ class MPCQFunction(torch.autograd.Function):
         ctx.shared = theta.dim() == 1
         ctx.dtypes = (x0.dtype, u0.dtype, theta.dtype)
         ctx.jac = (r.status, None if s is None else s.dV_dx0, None if s is None else s.dQ_du0, r.dV_dp)
+        ctx.dQ_dc = mpc.cost_value_grad() if need_p and layer.cost_gradient else None
         return r.V.to(x0.dtype)
 
     @staticmethod
@@ -132,6 +142,8 @@ class MPCQFunction(torch.autograd.Function):
         g_Q = g_Q.to(torch.float64)
         g_x0, g_th = mpc_backward_terms(None, g_Q, status, None, dQ_dx0, None, dQ_dp, ctx.shared)
         g_u0, _ = mpc_backward_terms(None, g_Q, status, None, dQ_du0, None, None, ctx.shared)
+        if ctx.dQ_dc is not None:
+            g_th = g_th + _cost_term(g_Q.reshape(-1, 1) * ctx.dQ_dc, status == 0, ctx.shared)
         return tuple(g.to(dt) if need and g is not None else None
                      for g, need, dt in zip((g_x0, g_u0, g_th), ctx.needs_input_grad[:3], ctx.dtypes)) + (None,)
 
@@ -281,6 +293,108 @@ class MPCBoundedTrajectoryFunction(torch.autograd.Function):
         return (None if g_x0 is None else g_x0.to(ctx.dtypes[0]), None if g_th is None else g_th.to(ctx.dtypes[1])) + g_b + (None,)
 
 
+def _cost_term(g: torch.Tensor, good: torch.Tensor, shared: bool) -> torch.Tensor:
+    """A per-instance cost gradient g [B, n_p] as a term of theta's gradient: rows outside ``good`` selected out (not multiplied),
+    summed over the batch for a shared theta."""
+    g = torch.where(good.reshape(-1, 1), g, torch.zeros_like(g))
+    return g.sum(0) if shared else g
+
+
+class MPCCostFunction(torch.autograd.Function):
+    """``MPCFunction`` / ``MPCBoundedFunction`` of a layer with ``cost_gradient=True``: (x0, theta, layer[, lb0, ub0, lb, ub, lbe, ube])
+    -> (u0, V).  theta's gradient gets, on the cost block, g_V dV/dcost (``MPCBatch.cost_value_grad``) plus one ``MPCBatch.cost_vjp``
+    with g_u as the cotangent on stage 0 of U*; when bounds need a gradient that same call serves them."""
+
+    @staticmethod
+    def forward(ctx, x0, theta, layer, *bounds):
+        mpc: MPCBatch = layer.batch
+        need_x, need_p, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[3:9]
+        if bounds:
+            _apply_bounds(mpc, bounds)
+        mpc.set_theta(theta.detach().to(torch.float64))
+        r = mpc.solve(x0.detach().to(torch.float64), sens_v=need_p, sens_pi=need_p, **layer.solve_args)
+        s = mpc.state_sens(q_mode=False, value=True, policy=layer.has_policy_jacobian) if need_x else None
+        layer.last_status = r.status
+        ctx.set_materialize_grads(False)
+        ctx.layer, ctx.pass_id = layer, layer.pass_counter
+        ctx.shared = theta.dim() == 1
+        ctx.dtypes, ctx.like = (x0.dtype, theta.dtype), tuple((b.device, b.dtype) for b in bounds)
+        ctx.policy = layer.has_policy_jacobian
+        ctx.jac = (r.status, None if s is None else s.dpi_dx0, None if s is None else s.dV_dx0, r.dpi_dp, r.dV_dp)
+        ctx.dV_db = mpc.bound_value_grad(q_mode=False) if any(need_b) else None
+        ctx.dV_dc = mpc.cost_value_grad() if need_p else None
+        return r.u0.to(x0.dtype), r.V.to(x0.dtype)
+
+    @staticmethod
+    def backward(ctx, g_u, g_V):
+        status, du_dx0, dV_dx0, du_dp, dV_dp = ctx.jac
+        need_p, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[3:9]
+        if g_u is not None and ctx.needs_input_grad[0] and not ctx.policy:
+            raise RuntimeError("MPCLayer: the loss depends on u0 and x0 requires a gradient, but du0*/dx0 is not available: build the layer "
+                               "with policy_jacobian=True, detach x0 or keep u0 out of the loss.")
+        f64 = [None if g is None else g.to(torch.float64) for g in (g_u, g_V)]
+        g_x0, g_th = mpc_backward_terms(f64[0], f64[1], status, du_dx0, dV_dx0, du_dp, dV_dp, ctx.shared)
+        g_b = (None,) * len(need_b)
+        if (need_p or any(need_b)) and (g_u is not None or g_V is not None):
+            mpc = ctx.layer.batch
+            g_lb = g_ub = g_c = None
+            if g_u is not None:
+                _stale(ctx, "forward")
+                gU = torch.zeros((mpc.B, mpc.N, mpc.nu), dtype=torch.float64, device=f64[0].device)
+                gU[:, 0] = f64[0]
+                g_lb, g_ub, g_c = mpc.cost_vjp(None, gU, x0=False, theta=False, bounds=any(need_b), cost=need_p)[2:]
+            if g_V is not None:
+                if any(need_b):
+                    dlb, dub = (f64[1].reshape(-1, 1, 1) * d for d in ctx.dV_db)
+                    g_lb, g_ub = (dlb, dub) if g_lb is None else (g_lb + dlb, g_ub + dub)
+                if need_p:
+                    dc = f64[1].reshape(-1, 1) * ctx.dV_dc
+                    g_c = dc if g_c is None else g_c + dc
+            if any(need_b):
+                g_b = _bound_grads(mpc, g_lb, g_ub, status == 0, need_b, ctx.like)
+            if need_p:
+                g_th = g_th + _cost_term(g_c, status == 0, ctx.shared)
+        return (None if g_x0 is None or not ctx.needs_input_grad[0] else g_x0.to(ctx.dtypes[0]),
+                None if g_th is None or not need_p else g_th.to(ctx.dtypes[1]), None) + g_b
+
+
+class MPCCostTrajectoryFunction(torch.autograd.Function):
+    """``MPCTrajectoryFunction`` / ``MPCBoundedTrajectoryFunction`` of a layer with ``cost_gradient=True``: (x0, theta, layer[, lb0, ub0,
+    lb, ub, lbe, ube]) -> (X, U); ``backward`` is ONE ``MPCBatch.cost_vjp`` for everything that requires a gradient, and theta's
+    gradient is g_theta + g_cost."""
+
+    @staticmethod
+    def forward(ctx, x0, theta, layer, *bounds):
+        mpc = layer.batch
+        if bounds:
+            _apply_bounds(mpc, bounds)
+        mpc.set_theta(theta.detach().to(torch.float64))
+        r = mpc.solve(x0.detach().to(torch.float64), **layer.solve_args)
+        X, U = mpc.get_iterate()[:2]
+        layer.last_status = r.status
+        ctx.set_materialize_grads(False)
+        ctx.layer, ctx.pass_id, ctx.status = layer, layer.pass_counter, r.status
+        ctx.shared = theta.dim() == 1
+        ctx.dtypes, ctx.like = (x0.dtype, theta.dtype), tuple((b.device, b.dtype) for b in bounds)
+        return X.to(x0.dtype), U.to(x0.dtype)
+
+    @staticmethod
+    def backward(ctx, g_X, g_U):
+        need_x, need_p, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[3:9]
+        if (g_X is None and g_U is None) or not (need_x or need_p or any(need_b)):
+            return (None,) * (3 + len(need_b))
+        _stale(ctx, "trajectory")
+        mpc = ctx.layer.batch
+        g_x0, g_th, g_lb, g_ub, g_c = mpc.cost_vjp(None if g_X is None else g_X.to(torch.float64), None if g_U is None else g_U.to(torch.float64),
+                                                   x0=need_x, theta=need_p, bounds=any(need_b), cost=need_p)
+        if g_th is not None:      # (cost_vjp has selected the rows of instances with a status other than 0 out of both)
+            g_th = g_th + g_c
+            if ctx.shared:
+                g_th = g_th.sum(0)
+        g_b = _bound_grads(mpc, g_lb, g_ub, torch.ones_like(ctx.status, dtype=torch.bool), need_b, ctx.like) if any(need_b) else (None,) * len(need_b)
+        return (None if g_x0 is None else g_x0.to(ctx.dtypes[0]), None if g_th is None else g_th.to(ctx.dtypes[1]), None) + g_b
+
+
 class MPCLayer(torch.nn.Module):
     """``layer(x0, theta) -> (u0, V)``, ``layer.q(x0, u0, theta) -> Q`` and ``layer.trajectory(x0, theta) -> (X, U)`` around one
     ``MPCBatch`` (its batch size is the layer's).  ``pass_counter``: incremented by each of the three (the staleness rule of
@@ -288,10 +402,16 @@ class MPCLayer(torch.nn.Module):
     ``policy_jacobian``: whether ``forward`` computes du0*/dx0 when ``x0`` needs a gradient — None = on for the cartpole and the linear
     system, off for the chain of masses (where it costs up to three more launches per forward pass); True / False = on / off on any
     model.  ``solve_args`` go to every ``MPCBatch.solve`` of the layer (e.g. ``cold=True``).  ``last_status`` [B] int32: the statuses
-    of the last forward pass."""
+    of the last forward pass.
+    ``cost_gradient`` (cartpole only, ValueError otherwise; off by default): ``theta.grad`` also carries the cost block, entries
+    3 .. 82 of p, each an independent variable (include/mpcrl_cost_ext.h, see the module's docstring)."""
 
-    def __init__(self, batch: MPCBatch, policy_jacobian: Optional[bool] = None, **solve_args):
+    def __init__(self, batch: MPCBatch, policy_jacobian: Optional[bool] = None, cost_gradient: bool = False, **solve_args):
         super().__init__()
+        if cost_gradient and batch.ocp.name != "cartpole":
+            raise ValueError("MPCLayer: cost_gradient=True is for the cartpole (the linear system keeps its weights in consts, the chain "
+                             f"has Q, R in its parameter gradient already), not for {batch.ocp.name!r}")
+        self.cost_gradient = bool(cost_gradient)
         self.batch = batch
         self.solve_args = solve_args
         self.has_policy_jacobian = (not batch.ocp.name.startswith("chain")) if policy_jacobian is None else bool(policy_jacobian)
@@ -302,6 +422,8 @@ class MPCLayer(torch.nn.Module):
         """``bounds``: a BoxBounds whose members may require a gradient (a host synchronisation per call, see the module's docstring);
         None = the bounds the batch has, as constants."""
         self.pass_counter += 1
+        if self.cost_gradient:
+            return MPCCostFunction.apply(x0, theta, self, *(() if bounds is None else BoxBounds(*bounds)))
         if bounds is None:
             return MPCFunction.apply(x0, theta, self)
         return MPCBoundedFunction.apply(x0, theta, *BoxBounds(*bounds), self)
@@ -313,6 +435,8 @@ class MPCLayer(torch.nn.Module):
     def trajectory(self, x0: torch.Tensor, theta: torch.Tensor, bounds: Optional[BoxBounds] = None):
         """``bounds``: as in ``forward``."""
         self.pass_counter += 1
+        if self.cost_gradient:
+            return MPCCostTrajectoryFunction.apply(x0, theta, self, *(() if bounds is None else BoxBounds(*bounds)))
         if bounds is None:
             return MPCTrajectoryFunction.apply(x0, theta, self)
         return MPCBoundedTrajectoryFunction.apply(x0, theta, *BoxBounds(*bounds), self)

@@ -47,6 +47,47 @@ class BoxBounds(NamedTuple):
     ube: torch.Tensor     # [nx]
 
 
+class CartpoleCost(NamedTuple):
+    """The cost block of the cartpole's parameter vector (entries 3 .. 82 of p) as tensors: l = 1/2 r' W r, r = y - yref, y = [x; u]
+    on stages 0 .. N-1 (W_0, yref_0 on stage 0; W, yref on stages 1 .. N-1) and y = x on stage N (W_e, yref_e).  Leading batch
+    dimensions are allowed on every member."""
+    W_0: torch.Tensor       # [..., 5, 5]
+    W: torch.Tensor         # [..., 5, 5]
+    W_e: torch.Tensor       # [..., 4, 4]
+    yref_0: torch.Tensor    # [..., 5]
+    yref: torch.Tensor      # [..., 5]
+    yref_e: torch.Tensor    # [..., 4]
+
+
+_CARTPOLE_NP, _CARTPOLE_NDYN = 83, 3
+_CARTPOLE_COST_FIELDS = ((3, 5, True), (28, 5, True), (53, 4, True), (69, 5, False), (74, 5, False), (79, 4, False))   # (offset, side, matrix)
+
+
+def cartpole_cost_of(theta: torch.Tensor) -> CartpoleCost:
+    """``theta[..., 3:]`` of a cartpole parameter vector [..., 83] as the six tensors of a CartpoleCost (each matrix is stored
+    column-major in p).  Differentiable: views of ``theta``."""
+    if theta.shape[-1] != _CARTPOLE_NP:
+        raise ValueError(f"a cartpole parameter vector has {_CARTPOLE_NP} entries, got {theta.shape[-1]}")
+    lead = theta.shape[:-1]
+    return CartpoleCost(*(theta[..., o:o + n * n].reshape(lead + (n, n)).transpose(-1, -2) if mat else theta[..., o:o + n]
+                          for o, n, mat in _CARTPOLE_COST_FIELDS))
+
+
+def cartpole_theta(dyn: torch.Tensor, cost: CartpoleCost) -> torch.Tensor:
+    """The inverse of ``cartpole_cost_of``: the dynamics block ``dyn`` [..., 3] and a CartpoleCost to a parameter vector [..., 83].
+    Differentiable."""
+    cost = CartpoleCost(*cost)
+    if dyn.shape[-1] != _CARTPOLE_NDYN:
+        raise ValueError(f"the cartpole's dynamics block has {_CARTPOLE_NDYN} entries, got {dyn.shape[-1]}")
+    parts = [dyn]
+    for t, (o, n, mat) in zip(cost, _CARTPOLE_COST_FIELDS):
+        if (t.shape[-2:] != (n, n)) if mat else (t.shape[-1] != n):
+            raise ValueError(f"CartpoleCost.{CartpoleCost._fields[len(parts) - 1]} has the shape {tuple(t.shape)}")
+        parts.append(t.transpose(-1, -2).reshape(t.shape[:-2] + (n * n,)) if mat else t)
+    lead = torch.broadcast_shapes(*(p.shape[:-1] for p in parts))
+    return torch.cat([p.expand(lead + p.shape[-1:]) for p in parts], dim=-1)
+
+
 class MPCBatch:
     """B independent instances of one OCP on one GPU.  The handle keeps the warm-start iterate of every
     instance (like the reference's solver object keeps its single iterate)."""
@@ -369,6 +410,55 @@ class MPCBatch:
             g_x0, g_th, g_lb, g_ub = (None if t is None else torch.where(good.reshape((self.B,) + (1,) * (t.dim() - 1)), t, torch.zeros_like(t))
                                       for t in (g_x0, g_th, g_lb, g_ub))
         return g_x0, g_th, g_lb, g_ub
+
+    def cost_value_grad(self) -> torch.Tensor:
+        """dV/dcost [B, n_p] of the last solve (dQ/dcost after a solve with u0 fixed), cartpole only: the derivative of the value with
+        respect to every entry of the cost block of p, each an independent variable (include/mpcrl_cost_ext.h mpcrl_cost_value_grad;
+        ``cartpole_cost_of`` splits a row into W_0, W, W_e, yref_0, yref, yref_e).  Entries 0 .. 2 are exactly zero — the dynamics
+        block is ``SolveResult.dV_dp``'s, whose own cost block stays zero.  Rows of instances whose status is neither 0 nor 2 are
+        zeros."""
+        if self.ocp.name != "cartpole":
+            raise RuntimeError("cost_value_grad is for the cartpole: the linear system keeps its weights in consts, the chain has Q, R in dV_dp")
+        if not (self.has_iterate and self.duals_valid):
+            raise RuntimeError("cost_value_grad needs the iterate of a solve (solve with store_bounds=True first)")
+        dV = torch.empty((self.B, self.n_p), dtype=torch.float64, device=self.device)
+        self._call("mpcrl_cost_value_grad", 0, dV)
+        st = self._solve_status
+        if st is not None:      # as in state_sens: the library sees the stored iterate, not the status word
+            dV = torch.where(((st == 0) | (st == 2)).reshape(self.B, 1), dV, torch.zeros_like(dV))
+        return dV
+
+    def cost_vjp(self, gX=None, gU=None, x0: bool = True, theta: bool = True, bounds: bool = False, cost: bool = True):
+        """(g_x0 [B, nx], g_theta [B, n_p], g_lb, g_ub [B, N+1, nu+nx], g_cost [B, n_p]; None where not asked for): ``bound_vjp`` with
+        the cotangents also pulled back to the cartpole's cost block (include/mpcrl_cost_ext.h mpcrl_cost_vjp): the same ONE launch
+        and ONE adjoint solve per instance serve all five.  g_cost is in the layout of p with exact zeros on entries 0 .. 2, and
+        g_theta keeps its zero cost block, so the gradient with respect to the whole of p is ``g_theta + g_cost``.  Cartpole only;
+        the conditions and the rows that are zeros are those of ``trajectory_vjp``."""
+        if self.ocp.name != "cartpole":
+            raise RuntimeError("cost_vjp is for the cartpole: the linear system keeps its weights in consts, the chain has Q, R in g_theta")
+        if not (self.has_iterate and self.duals_valid):
+            raise RuntimeError("cost_vjp needs the iterate of a solve with its bound multipliers (solve with store_bounds=True first)")
+        if self._solve_status is not None and self._solve_q_mode:
+            raise RuntimeError("cost_vjp after a solve with u0 fixed (Q mode) is not available")
+        if gX is None and gU is None:
+            raise ValueError("cost_vjp needs a cotangent: gX, gU or both")
+        if not (x0 or theta or bounds or cost):
+            raise ValueError("cost_vjp needs an output: x0, theta, bounds, cost or any of them")
+        gX = None if gX is None else self._dev(gX, (self.B, self.N + 1, self.nx))
+        gU = None if gU is None else self._dev(gU, (self.B, self.N, self.nu))
+        kw = dict(dtype=torch.float64, device=self.device)
+        g_x0 = torch.empty((self.B, self.nx), **kw) if x0 else None
+        g_th = torch.empty((self.B, self.n_p), **kw) if theta else None
+        g_lb = torch.empty((self.B, self.N + 1, self.nu + self.nx), **kw) if bounds else None
+        g_ub = torch.empty((self.B, self.N + 1, self.nu + self.nx), **kw) if bounds else None
+        g_c = torch.empty((self.B, self.n_p), **kw) if cost else None
+        self._call("mpcrl_cost_vjp", 0, gX, gU, g_x0, g_th, g_lb, g_ub, g_c)
+        st = self._solve_status
+        if st is not None:      # as in trajectory_vjp: the library sees the stored iterate, not the status word
+            good = st == 0
+            g_x0, g_th, g_lb, g_ub, g_c = (None if t is None else torch.where(good.reshape((self.B,) + (1,) * (t.dim() - 1)), t, torch.zeros_like(t))
+                                           for t in (g_x0, g_th, g_lb, g_ub, g_c))
+        return g_x0, g_th, g_lb, g_ub, g_c
 
     def fold_bound_grad(self, g: torch.Tensor):
         """A per-stage bound gradient g [B, N+1, nu+nx] (``bound_vjp``, ``bound_value_grad``) summed onto the three groups of

@@ -1,17 +1,20 @@
 // mpcrl_state.hip — include/mpcrl_ext.h: state sensitivities of a solve (dV/dx0, dQ/du0, du0*/dx0) from the iterate the handle
 // stores; include/mpcrl_chain_ext.h and include/mpcrl_chain_traj_ext.h: du0*/dx0 and the trajectory VJP of the chain, from the workspace
 // of its last solve (kernels and launches: chain_sens.hpp, chain_inst.hip); include/mpcrl_bound_ext.h: the derivatives with respect to
-// the box bounds (bound_vjp_kernel.hpp, and the chain's launcher with its bound outputs).  The kernels are state_sens_kernel.hpp; this unit instantiates them for the cartpole, the linear system and every chain
+// the box bounds (bound_vjp_kernel.hpp, and the chain's launcher with its bound outputs); include/mpcrl_cost_ext.h: the derivatives with
+// respect to the cartpole's tracking cost (cost_vjp_kernel.hpp).  The kernels are state_sens_kernel.hpp; this unit instantiates them for the cartpole, the linear system and every chain
 // size, and launches them.  Nothing here allocates or waits: two launches (or one and a memset) on the caller's stream.
 #include "mpcrl_host.hpp"
 
 #include "../../include/mpcrl_chain_ext.h"
 #include "../../include/mpcrl_chain_traj_ext.h"
 #include "../../include/mpcrl_bound_ext.h"
+#include "../../include/mpcrl_cost_ext.h"
 #include "../../include/mpcrl_traj_ext.h"
 #include "state_sens_kernel.hpp"
 #include "traj_vjp_kernel.hpp"
 #include "bound_vjp_kernel.hpp"
+#include "cost_vjp_kernel.hpp"
 
 using namespace mpcrl;
 
@@ -71,6 +74,23 @@ int launch_bound_vjp(const MpcrlSolver *h, const BoundVjpArgs &a, hipStream_t st
         }
     }
     hipLaunchKernelGGL((small_bound_vjp_kernel<M, false>), grid, wave, 0, st, h->small, a);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+template <class M>
+int launch_cost_vjp(const MpcrlSolver *h, const CostVjpArgs &a, hipStream_t st) {   // the dispatch of launch_traj_vjp
+    constexpr SmallTraits T = small_traits<M>();
+    const int ipw = std::min(64 / (h->N + 1), T.max_ipw);
+    const dim3 grid((unsigned)((h->B + ipw - 1) / ipw)), wave(64);
+    if constexpr (!T.seg_skip) {
+        if (seg_short(T, h->N)) {
+            hipLaunchKernelGGL((small_cost_vjp_kernel<M, true>), grid, wave, 0, st, h->small, a);
+            HIP_OK(hipGetLastError());
+            return 0;
+        }
+    }
+    hipLaunchKernelGGL((small_cost_vjp_kernel<M, false>), grid, wave, 0, st, h->small, a);
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -244,6 +264,41 @@ int mpcrl_chain_bound_vjp(mpcrl_handle h, int flags, const int32_t *status, cons
     if (!e) return MPCRL_E_MODEL;
     ON_DEVICE(h->device);
     return e->traj_vjp(h, status, gX, gU, g_x0, g_theta, g_lb, g_ub, h->chain_adjoint_current, (hipStream_t)stream);
+}
+
+int mpcrl_cost_ext_version(void) { return MPCRL_COST_EXT_VERSION; }
+
+int mpcrl_cost_value_grad(mpcrl_handle h, int flags, double *dV_dcost, void *stream) {
+    if (!h || flags || !dV_dcost) return MPCRL_E_ARG;
+    if (h->model != MPCRL_MODEL_CARTPOLE) return MPCRL_E_MODEL;
+    if (!h->have_iterate || h->dual_cold) return MPCRL_E_ARG;
+    ON_DEVICE(h->device);
+    CostValueArgs a;
+    a.B = h->B, a.N = h->N, a.theta_stride = h->theta_stride, a.cost_kind = h->small.cost_kind;
+    a.dT = h->small.dT, a.gamma = h->small.gamma, a.theta = h->theta;
+    a.X = h->X, a.U = h->U, a.PI = h->PI, a.RES = h->RES, a.dV = dV_dcost;
+    hipLaunchKernelGGL(cost_value_grad_kernel<CartpoleDev>, dim3((unsigned)h->B), dim3(64), 0, (hipStream_t)stream, a);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int mpcrl_cost_vjp(mpcrl_handle h, int flags, const double *gX, const double *gU, double *g_x0, double *g_theta, double *g_lb,
+                   double *g_ub, double *g_cost, void *stream) {
+    if (!h || flags) return MPCRL_E_ARG;   // (MPCRL_STATE_Q_MODE included, as in mpcrl_traj_vjp)
+    if (h->model != MPCRL_MODEL_CARTPOLE) return MPCRL_E_MODEL;
+    if (!g_cost) {   // the launch of mpcrl_bound_vjp itself: its refusals, its bits
+        if (!g_x0 && !g_theta && !g_lb && !g_ub) return MPCRL_E_ARG;
+        return mpcrl_bound_vjp(h, flags, gX, gU, g_x0, g_theta, g_lb, g_ub, stream);
+    }
+    if (!h->have_iterate || h->dual_cold) return MPCRL_E_ARG;
+    if (!gX && !gU) return MPCRL_E_ARG;
+    ON_DEVICE(h->device);
+    TrajVjpArgs t;
+    t.B = h->B, t.theta_stride = h->theta_stride, t.perm = h->have_perm ? h->perm : nullptr, t.theta = h->theta;
+    t.X = h->X, t.U = h->U, t.PI = h->PI, t.BND = h->BND, t.RES = h->RES;
+    t.gX = gX, t.gU = gU, t.g_x0 = g_x0, t.g_theta = g_theta;
+    const CostVjpArgs a{BoundVjpArgs{t, g_lb, g_ub}, g_cost};
+    return launch_cost_vjp<CartpoleDev>(h, a, (hipStream_t)stream);
 }
 
 }  // extern "C"

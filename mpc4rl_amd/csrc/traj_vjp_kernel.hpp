@@ -14,13 +14,19 @@
 // Lane layout, loads, the "solved" rule and the linearisation are those of small_state_sens_kernel; the Hessian assembly and the cap /
 // extrapolation block restate it so that du0*/dp, du0*/dx0 and this product describe one linearised KKT system.
 //
-// The kernel's body is small_traj_vjp_body<M, S, BOUNDS>: BOUNDS = false is this kernel, BOUNDS = true the kernel of
+// The kernel's body is small_traj_vjp_body<M, S, BOUNDS, COST>: BOUNDS = false is this kernel, BOUNDS = true the kernel of
 // include/mpcrl_bound_ext.h (bound_vjp_kernel.hpp), which contracts the same solution with the bound rows as well.  Everything the
-// bound outputs add sits behind `if constexpr (BOUNDS)`, so this kernel's arithmetic and its order are untouched by it.
+// bound outputs add sits behind `if constexpr (BOUNDS)`, so this kernel's arithmetic and its order are untouched by it.  COST is a hook
+// of the same kind: a functor with COST::ON that contracts the merged solution with the stage's cost residual (cost_vjp_kernel.hpp,
+// include/mpcrl_cost_ext.h); the default, NoCostOut, is never called.
 #pragma once
 #include "state_sens_kernel.hpp"
 
 namespace mpcrl {
+
+struct NoCostOut {
+    static constexpr bool ON = false;
+};
 
 struct TrajVjpArgs {
     int B, theta_stride;
@@ -36,8 +42,8 @@ struct TrajVjpArgs {
 // g_lb / g_ub [B, N + 1, nu + nx] (BOUNDS only; either may be null): for the bound row of side sd on coordinate i of this stage's
 // v = [u; x], dR/db is -sgn in the row h + t of that bound alone, and eliminating (lam, t) leaves G' dw*/db = (lam / t) y_v[i] for
 // either side — with the weight the solve used, min(lam / t, SENS_W_MAX).  Exactly 0 where has() says there is no row.
-template <class M, bool SHORT, bool BOUNDS>
-MPCRL_DI void small_traj_vjp_body(const SmallSpec sp, const TrajVjpArgs a, double *g_lb, double *g_ub) {
+template <class M, bool SHORT, bool BOUNDS, class COST = NoCostOut>
+MPCRL_DI void small_traj_vjp_body(const SmallSpec sp, const TrajVjpArgs a, double *g_lb, double *g_ub, [[maybe_unused]] const COST cost = COST()) {
     using SS = SmallSolver<M, SHORT>;
     constexpr int NX = M::NX, NU = M::NU, NW = NX + NU, NP = M::NP, NTD = M::NTD, NTC = M::NTC, NT = NTD + NTC;
     const int lane = threadIdx.x;
@@ -205,6 +211,7 @@ MPCRL_DI void small_traj_vjp_body(const SmallSpec sp, const TrajVjpArgs a, doubl
     }
     if constexpr (BOUNDS)
         if (!rows_done) bound_rows(S.Dx, S.Du, false);
+    if constexpr (COST::ON) cost(S, inst, valid, sv, okall);   // (after the two solutions are merged: the product is linear in y)
     double ynn[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) ynn[i] = lane_dn(S.Dnu[i]);
