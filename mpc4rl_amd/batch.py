@@ -47,6 +47,15 @@ class BoxBounds(NamedTuple):
     ube: torch.Tensor     # [nx]
 
 
+class TrajectoryJacobian(NamedTuple):
+    """``MPCBatch.trajectory_jacobian``: the Jacobian of the planned trajectory with respect to the initial state and the
+    parameters.  The columns of the parameter blocks at entries the sensitivity pass does not differentiate are zeros."""
+    dX_dx0: torch.Tensor       # [B, N + 1, nx, nx]
+    dU_dx0: torch.Tensor       # [B, N, nu, nx]
+    dX_dtheta: torch.Tensor    # [B, N + 1, nx, n_p]
+    dU_dtheta: torch.Tensor    # [B, N, nu, n_p]
+
+
 class CartpoleCost(NamedTuple):
     """The cost block of the cartpole's parameter vector (entries 3 .. 82 of p) as tensors: l = 1/2 r' W r, r = y - yref, y = [x; u]
     on stages 0 .. N-1 (W_0, yref_0 on stage 0; W, yref on stages 1 .. N-1) and y = x on stage N (W_e, yref_e).  Leading batch
@@ -327,6 +336,73 @@ class MPCBatch:
             good = (st == 0).reshape(self.B, 1)
             g_x0, g_th = (None if t is None else torch.where(good, t, torch.zeros_like(t)) for t in (g_x0, g_th))
         return g_x0, g_th
+
+    def n_diff(self) -> int:
+        """Number of leading entries of p the sensitivity pass differentiates on the cartpole and the linear system: the dynamics
+        block m, M, l of the cartpole (its cost block is not), all twelve of the linear system."""
+        if self._is_chain:
+            raise RuntimeError("n_diff and the trajectory Jacobian are not available for the chain of masses")
+        return _CARTPOLE_NDYN if self.n_p == _CARTPOLE_NP else self.n_p
+
+    def trajectory_jvp(self, dx0=None, dtheta=None, X: bool = True, U: bool = True):
+        """(dX [B, N+1, nx] or None, dU [B, N, nu] or None): how X* and U* of the last solve move when its initial state moves along
+        dx0 [B, nx] and its parameters along dtheta [B, n_p] or [n_p] (None = zeros, not both) — the forward mode of
+        ``trajectory_vjp``, one solve of the same linearised KKT system per instance and direction (include/mpcrl_traj_jvp_ext.h
+        mpcrl_traj_jvp), from the iterate the handle stores.  With R directions per instance, dx0 [B, R, nx] and dtheta [B, R, n_p],
+        the outputs are [B, R, N+1, nx] and [B, R, N, nu], from one launch.  dX[..., 0, :] is dx0.  Of dtheta only the entries the
+        sensitivity pass differentiates are read (the first ``n_diff()``); the cartpole's cost block is ignored.  Rows of instances
+        whose status is not 0 are zeros.  Cartpole and linear system, after a solve without u0."""
+        if self._is_chain:
+            raise RuntimeError("trajectory_jvp is not available for the chain of masses")
+        if not (self.has_iterate and self.duals_valid):
+            raise RuntimeError("trajectory_jvp needs the iterate of a solve with its bound multipliers (solve with store_bounds=True first)")
+        if self._solve_status is not None and self._solve_q_mode:
+            raise RuntimeError("trajectory_jvp after a solve with u0 fixed (Q mode) is not available")
+        if dx0 is None and dtheta is None:
+            raise ValueError("trajectory_jvp needs a direction: dx0, dtheta or both")
+        if not (X or U):
+            raise ValueError("trajectory_jvp needs an output: X, U or both")
+        kw = dict(dtype=torch.float64, device=self.device)
+        dx0 = None if dx0 is None else torch.as_tensor(dx0, **kw)
+        dtheta = None if dtheta is None else torch.as_tensor(dtheta, **kw)
+        if dtheta is not None and dtheta.dim() == 1:      # one direction in theta for the whole batch
+            lead = (self.B,) if dx0 is None or dx0.dim() == 2 else (self.B, dx0.shape[1])
+            dtheta = dtheta.reshape((1,) * len(lead) + (self.n_p,)).expand(lead + (self.n_p,))
+        ranks = {t.dim() for t in (dx0, dtheta) if t is not None}
+        if ranks not in ({2}, {3}):
+            raise ValueError("trajectory_jvp takes dx0 [B, nx] / dtheta [B, n_p] or dx0 [B, R, nx] / dtheta [B, R, n_p]")
+        single = ranks == {2}
+        R = 1 if single else (dx0 if dx0 is not None else dtheta).shape[1]
+        if R < 1:
+            raise ValueError("trajectory_jvp needs at least one direction")
+        dx0 = None if dx0 is None else self._dev(dx0, (self.B, R, self.nx))
+        dtheta = None if dtheta is None else self._dev(dtheta, (self.B, R, self.n_p))
+        dX = torch.empty((self.B, R, self.N + 1, self.nx), **kw) if X else None
+        dU = torch.empty((self.B, R, self.N, self.nu), **kw) if U else None
+        self._call("mpcrl_traj_jvp", 0, R, dx0, dtheta, dX, dU)
+        st = self._solve_status
+        if st is not None:      # as in trajectory_vjp: the library sees the stored iterate, not the status word
+            good = (st == 0).reshape(self.B, 1, 1, 1)
+            dX, dU = (None if t is None else torch.where(good, t, torch.zeros_like(t)) for t in (dX, dU))
+        if single:
+            dX, dU = (None if t is None else t[:, 0] for t in (dX, dU))
+        return dX, dU
+
+    def trajectory_jacobian(self) -> TrajectoryJacobian:
+        """The full Jacobian of the last solve's plan, d(X*, U*) / d(x0, theta), from one ``trajectory_jvp`` with the
+        nx + ``n_diff()`` unit directions.  The columns of the theta blocks past ``n_diff()`` are exact zeros."""
+        nd, nx = self.n_diff(), self.nx      # (raises on the chain)
+        kw = dict(dtype=torch.float64, device=self.device)
+        dx0 = torch.zeros((self.B, nx + nd, nx), **kw)
+        dth = torch.zeros((self.B, nx + nd, self.n_p), **kw)
+        dx0[:, :nx] = torch.eye(nx, **kw)
+        dth[:, nx:, :nd] = torch.eye(nd, **kw)
+        dX, dU = self.trajectory_jvp(dx0, dth)
+        dX, dU = dX.permute(0, 2, 3, 1), dU.permute(0, 2, 3, 1)      # [B, N + 1, nx, R], [B, N, nu, R]
+        dX_dth = torch.zeros((self.B, self.N + 1, nx, self.n_p), **kw)
+        dU_dth = torch.zeros((self.B, self.N, self.nu, self.n_p), **kw)
+        dX_dth[..., :nd], dU_dth[..., :nd] = dX[..., nx:], dU[..., nx:]
+        return TrajectoryJacobian(dX[..., :nx].contiguous(), dU[..., :nx].contiguous(), dX_dth, dU_dth)
 
     def chain_trajectory_vjp(self, gX=None, gU=None, x0: bool = True, theta: bool = True):
         """``trajectory_vjp`` for the chain of masses (include/mpcrl_chain_traj_ext.h mpcrl_chain_traj_vjp): (g_x0 [B, nx] or None,

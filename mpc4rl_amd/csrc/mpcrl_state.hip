@@ -2,7 +2,7 @@
 // stores; include/mpcrl_chain_ext.h and include/mpcrl_chain_traj_ext.h: du0*/dx0 and the trajectory VJP of the chain, from the workspace
 // of its last solve (kernels and launches: chain_sens.hpp, chain_inst.hip); include/mpcrl_bound_ext.h: the derivatives with respect to
 // the box bounds (bound_vjp_kernel.hpp, and the chain's launcher with its bound outputs); include/mpcrl_cost_ext.h: the derivatives with
-// respect to the cartpole's tracking cost (cost_vjp_kernel.hpp).  The kernels are state_sens_kernel.hpp; this unit instantiates them for the cartpole, the linear system and every chain
+// respect to the cartpole's tracking cost (cost_vjp_kernel.hpp); include/mpcrl_traj_jvp_ext.h: the trajectory JVP (traj_jvp_kernel.hpp).  The kernels are state_sens_kernel.hpp; this unit instantiates them for the cartpole, the linear system and every chain
 // size, and launches them.  Nothing here allocates or waits: two launches (or one and a memset) on the caller's stream.
 #include "mpcrl_host.hpp"
 
@@ -11,10 +11,12 @@
 #include "../../include/mpcrl_bound_ext.h"
 #include "../../include/mpcrl_cost_ext.h"
 #include "../../include/mpcrl_traj_ext.h"
+#include "../../include/mpcrl_traj_jvp_ext.h"
 #include "state_sens_kernel.hpp"
 #include "traj_vjp_kernel.hpp"
 #include "bound_vjp_kernel.hpp"
 #include "cost_vjp_kernel.hpp"
+#include "traj_jvp_kernel.hpp"
 
 using namespace mpcrl;
 
@@ -57,6 +59,24 @@ int launch_traj_vjp(const MpcrlSolver *h, const TrajVjpArgs &a, hipStream_t st) 
         }
     }
     hipLaunchKernelGGL((small_traj_vjp_kernel<M, false>), grid, wave, 0, st, h->small, a);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+template <class M>
+int launch_traj_jvp(const MpcrlSolver *h, const TrajJvpArgs &a, hipStream_t st) {   // the dispatch of launch_traj_vjp over B * R items
+    constexpr SmallTraits T = small_traits<M>();
+    const int ipw = std::min(64 / (h->N + 1), T.max_ipw);
+    const long items = (long)a.B * a.R;
+    const dim3 grid((unsigned)((items + ipw - 1) / ipw)), wave(64);
+    if constexpr (!T.seg_skip) {
+        if (seg_short(T, h->N)) {
+            hipLaunchKernelGGL((small_traj_jvp_kernel<M, true>), grid, wave, 0, st, h->small, a);
+            HIP_OK(hipGetLastError());
+            return 0;
+        }
+    }
+    hipLaunchKernelGGL((small_traj_jvp_kernel<M, false>), grid, wave, 0, st, h->small, a);
     HIP_OK(hipGetLastError());
     return 0;
 }
@@ -175,6 +195,22 @@ int mpcrl_traj_vjp(mpcrl_handle h, int flags, const double *gX, const double *gU
     a.gX = gX, a.gU = gU, a.g_x0 = g_x0, a.g_theta = g_theta;
     return h->model == MPCRL_MODEL_LINEAR ? launch_traj_vjp<LinearDev>(h, a, (hipStream_t)stream)
                                           : launch_traj_vjp<CartpoleDev>(h, a, (hipStream_t)stream);
+}
+
+int mpcrl_traj_jvp_ext_version(void) { return MPCRL_TRAJ_JVP_EXT_VERSION; }
+
+int mpcrl_traj_jvp(mpcrl_handle h, int flags, int ndir, const double *dx0, const double *dtheta, double *dX, double *dU, void *stream) {
+    if (!h || flags) return MPCRL_E_ARG;   // (MPCRL_STATE_Q_MODE included, as in mpcrl_traj_vjp)
+    if (h->is_large) return MPCRL_E_MODEL;
+    if (!h->have_iterate || h->dual_cold) return MPCRL_E_ARG;
+    if (ndir < 1 || (!dx0 && !dtheta) || (!dX && !dU)) return MPCRL_E_ARG;
+    ON_DEVICE(h->device);
+    TrajJvpArgs a;
+    a.B = h->B, a.R = ndir, a.theta_stride = h->theta_stride, a.theta = h->theta;
+    a.X = h->X, a.U = h->U, a.PI = h->PI, a.BND = h->BND, a.RES = h->RES;
+    a.dx0 = dx0, a.dth = dtheta, a.dX = dX, a.dU = dU;
+    return h->model == MPCRL_MODEL_LINEAR ? launch_traj_jvp<LinearDev>(h, a, (hipStream_t)stream)
+                                          : launch_traj_jvp<CartpoleDev>(h, a, (hipStream_t)stream);
 }
 
 int mpcrl_chain_ext_version(void) { return MPCRL_CHAIN_EXT_VERSION; }
