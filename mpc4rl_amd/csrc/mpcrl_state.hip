@@ -29,90 +29,45 @@ int launch_stage0(const MpcrlSolver *h, Stage0Args a, hipStream_t st) {
     return 0;
 }
 
-template <class M>
-int launch_policy(const MpcrlSolver *h, const StateSensArgs &a, hipStream_t st) {
-    constexpr SmallTraits T = small_traits<M>();
-    const int ipw = std::min(64 / (h->N + 1), T.max_ipw);
-    const dim3 grid((unsigned)((h->B + ipw - 1) / ipw)), wave(64);
-    if constexpr (!T.seg_skip) {   // at most 32 lanes per instance: the reductions without the level at distance 32, as launch_small picks
-        if (seg_short(T, h->N)) {
-            hipLaunchKernelGGL((small_state_sens_kernel<M, true>), grid, wave, 0, st, h->small, a);
-            HIP_OK(hipGetLastError());
-            return 0;
-        }
+// The launch of the lane-layout kernels (du0*/dx0, the trajectory / bound / cost VJPs over B instances, the trajectory JVP over
+// B * R items): min(64 / (N + 1), max_ipw) items per wavefront, and at most 32 lanes per instance take the reductions without the
+// level at distance 32, as launch_small picks.  P names the kernel template: LANE_KERNEL(K) declares K_p for the kernel K<M, SHORT>.
+#define LANE_KERNEL(K)                                 \
+    struct K##_p {                                     \
+        template <class M, bool SHORT>                 \
+        static constexpr auto kernel() {               \
+            return K<M, SHORT>;                        \
+        }                                              \
     }
-    hipLaunchKernelGGL((small_state_sens_kernel<M, false>), grid, wave, 0, st, h->small, a);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-template <class M>
-int launch_traj_vjp(const MpcrlSolver *h, const TrajVjpArgs &a, hipStream_t st) {   // the dispatch of launch_policy
+LANE_KERNEL(small_state_sens_kernel);
+LANE_KERNEL(small_traj_vjp_kernel);
+LANE_KERNEL(small_bound_vjp_kernel);
+LANE_KERNEL(small_cost_vjp_kernel);
+LANE_KERNEL(small_traj_jvp_kernel);
+#undef LANE_KERNEL
+template <class P, class M, class Args>
+int launch_lanes(const MpcrlSolver *h, long items, const Args &a, hipStream_t st) {
     constexpr SmallTraits T = small_traits<M>();
     const int ipw = std::min(64 / (h->N + 1), T.max_ipw);
-    const dim3 grid((unsigned)((h->B + ipw - 1) / ipw)), wave(64);
-    if constexpr (!T.seg_skip) {
-        if (seg_short(T, h->N)) {
-            hipLaunchKernelGGL((small_traj_vjp_kernel<M, true>), grid, wave, 0, st, h->small, a);
-            HIP_OK(hipGetLastError());
-            return 0;
-        }
-    }
-    hipLaunchKernelGGL((small_traj_vjp_kernel<M, false>), grid, wave, 0, st, h->small, a);
-    HIP_OK(hipGetLastError());
-    return 0;
-}
-
-template <class M>
-int launch_traj_jvp(const MpcrlSolver *h, const TrajJvpArgs &a, hipStream_t st) {   // the dispatch of launch_traj_vjp over B * R items
-    constexpr SmallTraits T = small_traits<M>();
-    const int ipw = std::min(64 / (h->N + 1), T.max_ipw);
-    const long items = (long)a.B * a.R;
     const dim3 grid((unsigned)((items + ipw - 1) / ipw)), wave(64);
     if constexpr (!T.seg_skip) {
         if (seg_short(T, h->N)) {
-            hipLaunchKernelGGL((small_traj_jvp_kernel<M, true>), grid, wave, 0, st, h->small, a);
+            hipLaunchKernelGGL((P::template kernel<M, true>()), grid, wave, 0, st, h->small, a);
             HIP_OK(hipGetLastError());
             return 0;
         }
     }
-    hipLaunchKernelGGL((small_traj_jvp_kernel<M, false>), grid, wave, 0, st, h->small, a);
+    hipLaunchKernelGGL((P::template kernel<M, false>()), grid, wave, 0, st, h->small, a);
     HIP_OK(hipGetLastError());
     return 0;
 }
-
-template <class M>
-int launch_bound_vjp(const MpcrlSolver *h, const BoundVjpArgs &a, hipStream_t st) {   // the dispatch of launch_traj_vjp
-    constexpr SmallTraits T = small_traits<M>();
-    const int ipw = std::min(64 / (h->N + 1), T.max_ipw);
-    const dim3 grid((unsigned)((h->B + ipw - 1) / ipw)), wave(64);
-    if constexpr (!T.seg_skip) {
-        if (seg_short(T, h->N)) {
-            hipLaunchKernelGGL((small_bound_vjp_kernel<M, true>), grid, wave, 0, st, h->small, a);
-            HIP_OK(hipGetLastError());
-            return 0;
-        }
-    }
-    hipLaunchKernelGGL((small_bound_vjp_kernel<M, false>), grid, wave, 0, st, h->small, a);
-    HIP_OK(hipGetLastError());
-    return 0;
+template <class P, class Args>   // ... for the handle's small model
+int launch_lanes_model(const MpcrlSolver *h, long items, const Args &a, hipStream_t st) {
+    return h->model == MPCRL_MODEL_LINEAR ? launch_lanes<P, LinearDev>(h, items, a, st) : launch_lanes<P, CartpoleDev>(h, items, a, st);
 }
-
-template <class M>
-int launch_cost_vjp(const MpcrlSolver *h, const CostVjpArgs &a, hipStream_t st) {   // the dispatch of launch_traj_vjp
-    constexpr SmallTraits T = small_traits<M>();
-    const int ipw = std::min(64 / (h->N + 1), T.max_ipw);
-    const dim3 grid((unsigned)((h->B + ipw - 1) / ipw)), wave(64);
-    if constexpr (!T.seg_skip) {
-        if (seg_short(T, h->N)) {
-            hipLaunchKernelGGL((small_cost_vjp_kernel<M, true>), grid, wave, 0, st, h->small, a);
-            HIP_OK(hipGetLastError());
-            return 0;
-        }
-    }
-    hipLaunchKernelGGL((small_cost_vjp_kernel<M, false>), grid, wave, 0, st, h->small, a);
-    HIP_OK(hipGetLastError());
-    return 0;
+// the iterate the handle stores, as the derivative kernels read it
+IterateArgs iterate_args(const MpcrlSolver *h) {
+    return IterateArgs{h->B, h->theta_stride, h->have_perm ? h->perm : nullptr, h->theta, h->X, h->U, h->PI, h->BND, h->RES};
 }
 
 template <class M>
@@ -171,10 +126,8 @@ int mpcrl_state_sens(mpcrl_handle h, int flags, double *dV_dx0, double *dQ_du0, 
         if (qmode)   // u_0 is data: du0/dx0 = 0, as du0/dp is
             HIP_OK(hipMemsetAsync(dpi_dx0, 0, (size_t)h->B * h->nu * h->nx * sizeof(double), st));
         else {
-            StateSensArgs a;
-            a.B = h->B, a.theta_stride = h->theta_stride, a.perm = h->have_perm ? h->perm : nullptr, a.theta = h->theta;
-            a.X = h->X, a.U = h->U, a.PI = h->PI, a.BND = h->BND, a.RES = h->RES, a.dpi = dpi_dx0;
-            const int rc = h->model == MPCRL_MODEL_LINEAR ? launch_policy<LinearDev>(h, a, st) : launch_policy<CartpoleDev>(h, a, st);
+            const StateSensArgs a{iterate_args(h), dpi_dx0};
+            const int rc = launch_lanes_model<small_state_sens_kernel_p>(h, h->B, a, st);
             if (rc) return rc;
         }
     }
@@ -189,12 +142,7 @@ int mpcrl_traj_vjp(mpcrl_handle h, int flags, const double *gX, const double *gU
     if (!h->have_iterate || h->dual_cold) return MPCRL_E_ARG;
     if ((!gX && !gU) || (!g_x0 && !g_theta)) return MPCRL_E_ARG;
     ON_DEVICE(h->device);
-    TrajVjpArgs a;
-    a.B = h->B, a.theta_stride = h->theta_stride, a.perm = h->have_perm ? h->perm : nullptr, a.theta = h->theta;
-    a.X = h->X, a.U = h->U, a.PI = h->PI, a.BND = h->BND, a.RES = h->RES;
-    a.gX = gX, a.gU = gU, a.g_x0 = g_x0, a.g_theta = g_theta;
-    return h->model == MPCRL_MODEL_LINEAR ? launch_traj_vjp<LinearDev>(h, a, (hipStream_t)stream)
-                                          : launch_traj_vjp<CartpoleDev>(h, a, (hipStream_t)stream);
+    return launch_lanes_model<small_traj_vjp_kernel_p>(h, h->B, TrajVjpArgs{iterate_args(h), gX, gU, g_x0, g_theta}, (hipStream_t)stream);
 }
 
 int mpcrl_traj_jvp_ext_version(void) { return MPCRL_TRAJ_JVP_EXT_VERSION; }
@@ -205,12 +153,8 @@ int mpcrl_traj_jvp(mpcrl_handle h, int flags, int ndir, const double *dx0, const
     if (!h->have_iterate || h->dual_cold) return MPCRL_E_ARG;
     if (ndir < 1 || (!dx0 && !dtheta) || (!dX && !dU)) return MPCRL_E_ARG;
     ON_DEVICE(h->device);
-    TrajJvpArgs a;
-    a.B = h->B, a.R = ndir, a.theta_stride = h->theta_stride, a.theta = h->theta;
-    a.X = h->X, a.U = h->U, a.PI = h->PI, a.BND = h->BND, a.RES = h->RES;
-    a.dx0 = dx0, a.dth = dtheta, a.dX = dX, a.dU = dU;
-    return h->model == MPCRL_MODEL_LINEAR ? launch_traj_jvp<LinearDev>(h, a, (hipStream_t)stream)
-                                          : launch_traj_jvp<CartpoleDev>(h, a, (hipStream_t)stream);
+    const TrajJvpArgs a{iterate_args(h), ndir, dx0, dtheta, dX, dU};
+    return launch_lanes_model<small_traj_jvp_kernel_p>(h, (long)h->B * ndir, a, (hipStream_t)stream);
 }
 
 int mpcrl_chain_ext_version(void) { return MPCRL_CHAIN_EXT_VERSION; }
@@ -278,16 +222,10 @@ int mpcrl_bound_vjp(mpcrl_handle h, int flags, const double *gX, const double *g
     if (!h->have_iterate || h->dual_cold) return MPCRL_E_ARG;
     if ((!gX && !gU) || (!g_x0 && !g_theta && !g_lb && !g_ub)) return MPCRL_E_ARG;
     ON_DEVICE(h->device);
-    TrajVjpArgs t;
-    t.B = h->B, t.theta_stride = h->theta_stride, t.perm = h->have_perm ? h->perm : nullptr, t.theta = h->theta;
-    t.X = h->X, t.U = h->U, t.PI = h->PI, t.BND = h->BND, t.RES = h->RES;
-    t.gX = gX, t.gU = gU, t.g_x0 = g_x0, t.g_theta = g_theta;
-    if (!g_lb && !g_ub)   // the launch of mpcrl_traj_vjp itself: its bits
-        return h->model == MPCRL_MODEL_LINEAR ? launch_traj_vjp<LinearDev>(h, t, (hipStream_t)stream)
-                                              : launch_traj_vjp<CartpoleDev>(h, t, (hipStream_t)stream);
+    const TrajVjpArgs t{iterate_args(h), gX, gU, g_x0, g_theta};
+    if (!g_lb && !g_ub) return launch_lanes_model<small_traj_vjp_kernel_p>(h, h->B, t, (hipStream_t)stream);   // the launch of mpcrl_traj_vjp itself: its bits
     const BoundVjpArgs a{t, g_lb, g_ub};
-    return h->model == MPCRL_MODEL_LINEAR ? launch_bound_vjp<LinearDev>(h, a, (hipStream_t)stream)
-                                          : launch_bound_vjp<CartpoleDev>(h, a, (hipStream_t)stream);
+    return launch_lanes_model<small_bound_vjp_kernel_p>(h, h->B, a, (hipStream_t)stream);
 }
 
 int mpcrl_chain_bound_vjp(mpcrl_handle h, int flags, const int32_t *status, const double *gX, const double *gU, double *g_x0,
@@ -329,12 +267,8 @@ int mpcrl_cost_vjp(mpcrl_handle h, int flags, const double *gX, const double *gU
     if (!h->have_iterate || h->dual_cold) return MPCRL_E_ARG;
     if (!gX && !gU) return MPCRL_E_ARG;
     ON_DEVICE(h->device);
-    TrajVjpArgs t;
-    t.B = h->B, t.theta_stride = h->theta_stride, t.perm = h->have_perm ? h->perm : nullptr, t.theta = h->theta;
-    t.X = h->X, t.U = h->U, t.PI = h->PI, t.BND = h->BND, t.RES = h->RES;
-    t.gX = gX, t.gU = gU, t.g_x0 = g_x0, t.g_theta = g_theta;
-    const CostVjpArgs a{BoundVjpArgs{t, g_lb, g_ub}, g_cost};
-    return launch_cost_vjp<CartpoleDev>(h, a, (hipStream_t)stream);
+    const CostVjpArgs a{BoundVjpArgs{TrajVjpArgs{iterate_args(h), gX, gU, g_x0, g_theta}, g_lb, g_ub}, g_cost};
+    return launch_lanes<small_cost_vjp_kernel_p, CartpoleDev>(h, h->B, a, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -58,8 +58,9 @@ constexpr double IPM_SKIP_SIGMA = 3e-6;
 // Riccati recursion all sixteen digits of the entries next to it (against a dense pivoted solve on the hardest test instances:
 // cap 1e8 -> 2e-7, 1e9 -> 1e-7 (bias 1e-8), 1e10 -> 1e-6, 1e12 -> 9e-5, 1e14 -> 3e-2, none -> 5e-1).  Round 6: with an active STATE
 // bound the bias is larger than on those instances (c / W with c ~ 3.6e3: 3.6e-6 at 1e9) — removed by Richardson extrapolation in
-// the cap where it occurs (SmallSolver::sensitivities, matrix-layout models).
+// the cap where it occurs (SmallSolver::kkt_solve, matrix-layout models).
 constexpr double SENS_W_MAX = 1e9;
+constexpr double SENS_W_2 = 0.5 * SENS_W_MAX;   // the cap of the second solve of that extrapolation (SmallSolver::kkt_solve)
 
 struct SmallArgs {
     int B;                 // instances
@@ -1418,10 +1419,159 @@ struct SmallSolver {
         return ok;
     }
 
+    // ---- the linearised KKT system of the derivative passes, stated once ---------------------------
+    // du0*/dp (sensitivities below), du0*/dx0 (state_sens_kernel.hpp), the trajectory / bound / cost VJPs (traj_vjp_kernel.hpp) and
+    // the trajectory JVP (traj_jvp_kernel.hpp) are derivatives of ONE system: the exact Lagrangian Hessian, the barrier diagonal
+    // lam / t capped at SENS_W_MAX and, on the matrix-layout models, the extrapolation 2 y(W) - y(W / 2) where the cap binds on a
+    // state row.  Every one of those kernels loads the stored iterate and linearises it (its own prologue: shared, it cost the
+    // headline benchmark time, profiles/sens_kkt_ab.txt), then runs kkt_assemble and kkt_solve; they differ in the right-hand side
+    // (rt, bb) and in what they contract the solution with.
+    static constexpr int NT = NTD + NTC, NHD = M::NLD * (M::NLD + 1) / 2;   // (NHD: packed size of hdd)
+
+    // stiffness of the bound row (sd, i) in the adjoint solve: lam / t of the stored iterate, capped (SENS_W_MAX above)
+    MPCRL_DI double capped_w(int sd, int i, double cap, bool *binds = nullptr) const {
+        const double w = lam[sd][i] / t[sd][i];
+        if (binds) *binds = w > cap;
+        return fmin(w, cap);
+    }
+    // Dg = barrier diagonal from the final (lam, t) of the BOUND rows; slacks are constants of the mirror (quirk q1).  Returns whether
+    // the cap binds on a STATE row of this stage (an active state bound).
+    MPCRL_DI bool barrier_diag(double cap) {
+        bool capped_x = false;
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+            double d = 0.0;
+#pragma unroll
+            for (int sd = 0; sd < 2; ++sd)
+                if (has(sd, i)) {
+                    bool binds;
+                    d += capped_w(sd, i, cap, &binds);
+                    if (i >= NU && binds) capped_x = true;
+                }
+            Dg[i] = d;
+        }
+        return capped_x;
+    }
+    // Hx = exact Lagrangian Hessian of the stage (nlp.py:1202,1224): c hess l + sum_m nu_{k+1,m} hess F_m, and Dg at SENS_W_MAX.
+    MPCRL_DI bool kkt_assemble(double (&Hx)[NHT], const double (&hdd)[NHD]) {
+#pragma unroll
+        for (int i = 0; i < NW; ++i)
+#pragma unroll
+            for (int j = 0; j <= i; ++j) Hx[sym(i, j)] = ck * hess_of_stage(i, j);
+        // second derivatives of F vanish along the coordinates whose Jacobian columns are constant (M::lin_coord lists the others);
+        // the rest came out of the linearisation's own evaluation of the map (linearize<true>; zero on the terminal lane)
+#pragma unroll
+        for (int di = 0; di < M::NLD; ++di)
+#pragma unroll
+            for (int dj = 0; dj <= di; ++dj) Hx[sym(M::lin_coord(di), M::lin_coord(dj))] += hdd[di * (di + 1) / 2 + dj];
+        hscale = 1.0;
+        return barrier_diag(SENS_W_MAX);
+    }
+
+    // Solves the system kkt_assemble left for the right-hand side (rt, bb) into Dx, Du and (WANT_NU) Dnu.  okall: no factorisation
+    // of the instance met a non-positive pivot; the factors are made for iu == 0 and a later right-hand side only re-scans them.
+    // (small_traj_vjp_body keeps this block as its own text, with its bound rows between the second solve and the merge.)
+    template <bool WANT_NU>
+    MPCRL_DI void kkt_solve(const double (&Hx)[NHT], const double (&bb)[NX], bool capped_x, int iu, bool &okall) {
+        auto Hs = [&](int i, int j) { return Hx[sym(i, j)]; };
+        if constexpr (MX) {   // NU = 1: one solve
+            const bool okf = mx_pred<true>(Hs, rt, bb);
+            if constexpr (WANT_NU) mx_dnu(rt, true);
+            double oe[2] = {okf ? 0.0 : 1.0, capped_x ? 1.0 : 0.0};   // the two flags of the instance in one reduction pass
+            seg_reduce<2, 0, M::SEG_SKIP, SHORT>(oe, nullptr, k, lpi, base);
+            okall = oe[0] < 0.5;
+            // Richardson extrapolation in the stiffness cap (round 6).  Where the cap binds on a STATE row the capped solve is off by
+            // c / W — 1.5e-6 ... 3.6e-6 of du0/dp on cartpole states with the cart at the end of its track, measured against
+            // third-party finite differences (G7b) — linear in 1 / W down to W ~ 1e11, while the recursion's rounding grows with W
+            // (table at SENS_W_MAX).  y = 2 y(W) - y(W / 2) takes the bias out at W's rounding level (3e-9 on the same states).
+            // Decided per INSTANCE (an instance's numbers never depend on its wavefront neighbours); the second solve runs for the
+            // wavefront when any of its instances needs it — none of the benchmark's, whose state bounds are inactive.
+            const bool extrap = oe[1] > 0.5;
+            if (__any(extrap)) {
+                double y1x[NX];
+                [[maybe_unused]] double y1n[NX];
+                const double y1u = Du[0];
+#pragma unroll
+                for (int i = 0; i < NX; ++i) {
+                    y1x[i] = Dx[i];
+                    if constexpr (WANT_NU) y1n[i] = Dnu[i];
+                }
+                barrier_diag(SENS_W_2);
+                const bool okf2 = mx_pred<true>(Hs, rt, bb);
+                if constexpr (WANT_NU) mx_dnu(rt, true);
+                const bool ok2 = seg_max<M::SEG_SKIP, SHORT>(okf2 ? 0.0 : 1.0, k, lpi, base) < 0.5;
+                okall = okall && (ok2 || !extrap);
+                Du[0] = extrap ? fma(2.0, y1u, -Du[0]) : y1u;
+#pragma unroll
+                for (int i = 0; i < NX; ++i) {
+                    Dx[i] = extrap ? fma(2.0, y1x[i], -Dx[i]) : y1x[i];
+                    if constexpr (WANT_NU) Dnu[i] = extrap ? fma(2.0, y1n[i], -Dnu[i]) : y1n[i];
+                }
+            }
+        } else {
+            if (iu == 0) {
+                const bool okf = backward(Hs, rt, bb);
+                okall = seg_max<M::SEG_SKIP, SHORT>(okf ? 0.0 : 1.0, k, lpi, base) < 0.5;
+            } else
+                backward_scan(rt, bb);
+            forward_scan(bb);
+        }
+    }
+
+    // x_0 is eliminated, so x0 enters the stationarity row of u_0 through d2 l0 / du dx and the dynamics row F(x0, u_0) - x_1
+    // through A_0: column j of that block against the solution (Du, ynn = Dnu of the next lane).  Meaningful on the first lane.
+    MPCRL_DI double dx0_contract(const double (&Hx)[NHT], const double (&ynn)[NX], int j) const {
+        double s = 0.0;
+#pragma unroll
+        for (int i = 0; i < NU; ++i) s = fma(Du[i], Hx[sym(i, NU + j)], s);
+#pragma unroll
+        for (int m = 0; m < NX; ++m) s = fma(ynn[m], Aget(m * NX + j), s);
+        return s;
+    }
+    // This stage's terms of y' dR/dtheta into sums[0 .. NT), differentiable parameters first: M::cost_mixed plus the mixed
+    // second-order evaluation of the discrete map along y = (Dx, Du).  Fth (or null) is WRITE-ONLY here: dF/dtheta of the stage, the
+    // first-order part jn[m].g[d] of this evaluation, for the caller's dV/dp terms.  The contraction with ynn reads jn[m].g[d] itself;
+    // sensitivities() used to read the Fth it had stored at its first control instead — the same numbers, since the g part of a Jet2
+    // depends on the point (x, u, theta) and not on the direction e, and both small models have one control.
+    MPCRL_DI void dtheta_contract(const double (&nun)[NX], const double (&ynn)[NX], double *sums, double *Fth) const {
+        double yv[NW];
+#pragma unroll
+        for (int i = 0; i < NW; ++i) yv[i] = dvc(Dx, Du, i);
+        double outc[NTC > 0 ? NTC : 1];
+#pragma unroll
+        for (int d = 0; d < NTD; ++d) sums[d] = 0.0;
+#pragma unroll
+        for (int d = 0; d < (NTC > 0 ? NTC : 1); ++d) outc[d] = 0.0;
+        M::cost_mixed(term, yv, ck, outc);
+#pragma unroll
+        for (int d = 0; d < NTC; ++d) sums[NTD + d] = outc[d];
+        if (term) return;
+        Jet2<NTD> jx[NX], ju[NU], jt[NTD], jn[NX];
+#pragma unroll
+        for (int i = 0; i < NU; ++i) ju[i] = Jet2<NTD>(u[i]), ju[i].e = yv[i];
+#pragma unroll
+        for (int i = 0; i < NX; ++i) jx[i] = Jet2<NTD>(x[i]), jx[i].e = yv[NU + i];
+#pragma unroll
+        for (int i = 0; i < NTD; ++i) jt[i] = Jet2<NTD>(thd[i]), jt[i].g[i] = 1.0;
+        disc_map<M, Jet2<NTD>>(jx, ju, jt, jn, sp.h, sp.rk_steps);
+#pragma unroll
+        for (int m = 0; m < NX; ++m)
+#pragma unroll
+            for (int d = 0; d < NTD; ++d)
+                if (Fth) Fth[m * NTD + d] = jn[m].g[d];
+#pragma unroll
+        for (int d = 0; d < NTD; ++d) {
+            double s = 0.0;
+#pragma unroll
+            for (int m = 0; m < NX; ++m) s = fma(nun[m], jn[m].m[d], fma(ynn[m], jn[m].g[d], s));
+            sums[d] = s;
+        }
+    }
+
     // ---- sensitivities: dV/dp = dL/dp (nlp.py:1211,1401) and du0*/dp (nlp.py:1413-1424) by an adjoint solve --
     // nun: multiplier nu_{k+1} of the dynamics leaving this stage.  dVa / dpia: per-instance output rows.
     // hdd: sum_m nu_{k+1,m} hess F_m along the non-trivial coordinates, from linearize<true>() (only read when du0*/dp is wanted)
-    MPCRL_DI void sensitivities(int flags, bool valid, const double *nun, double *dVa, double *dpia, const double *hdd) {
+    MPCRL_DI void sensitivities(int flags, bool valid, const double (&nun)[NX], double *dVa, double *dpia, const double (&hdd)[NHD]) {
         // dF/dtheta of the stage is the first-order part of the mixed second-order evaluation of the map below — for du0*/dp and
         // for dV/dp alike, whichever of the two is asked for: dV/dp is the same bits with and without du0*/dp, because the same
         // instructions compute it (a request for dV/dp alone runs the evaluation with a zero direction and skips the adjoint solve).
@@ -1450,7 +1600,6 @@ struct SmallSolver {
         // With du0*/dp the per-instance sums of the pass — dV/dp: NT = NTD + NTC of them, du0*/dp: NT per control — travel through
         // ONE reduction tree (seg_reduce<0, ...>): the trees of the single sums were walked one after the other, each level waiting
         // for its cross-lane move.  Every sum keeps its own tree (same partners, same order of the additions).
-        constexpr int NT = NTD + NTC;
         auto dV_parts = [&](double *dvp) {   // this stage's terms of dV/dp, differentiable parameters first
             double cpart[NTC > 0 ? NTC : 1];
 #pragma unroll
@@ -1499,37 +1648,8 @@ struct SmallSolver {
             }
             return;
         }
-        // exact Lagrangian Hessian of the stage (nlp.py:1202,1224): c hess l + sum_m nu_{k+1,m} hess F_m
-        double Hx[NW * (NW + 1) / 2];
-#pragma unroll
-        for (int i = 0; i < NW; ++i)
-#pragma unroll
-            for (int j = 0; j <= i; ++j) Hx[sym(i, j)] = ck * hess_of_stage(i, j);
-        {
-            // second derivatives of F vanish along the coordinates whose Jacobian columns are constant (M::lin_coord lists the others);
-            // the rest came out of the linearisation's own evaluation of the map (linearize<true>; zero on the terminal lane)
-            constexpr int ND = M::NLD;
-#pragma unroll
-            for (int di = 0; di < ND; ++di)
-#pragma unroll
-                for (int dj = 0; dj <= di; ++dj) Hx[sym(M::lin_coord(di), M::lin_coord(dj))] += hdd[di * (di + 1) / 2 + dj];
-        }
-        // barrier diagonal from the final (lam, t) of the BOUND rows; slacks are constants of the mirror (quirk q1)
-        bool capped_x = false;      // the cap binds on a STATE row of this stage (an active state bound)
-#pragma unroll
-        for (int i = 0; i < NW; ++i) {
-            double d = 0.0;
-#pragma unroll
-            for (int sd = 0; sd < 2; ++sd)
-                if (has(sd, i)) {
-                    const double w = lam[sd][i] / t[sd][i];
-                    d += fmin(w, SENS_W_MAX);
-                    if (i >= NU && w > SENS_W_MAX) capped_x = true;
-                }
-            Dg[i] = d;
-        }
-        auto Hs = [&](int i, int j) { return Hx[sym(i, j)]; };
-        hscale = 1.0;
+        double Hx[NHT];
+        const bool capped_x = kkt_assemble(Hx, hdd);
         double zero[NX];
 #pragma unroll
         for (int i = 0; i < NX; ++i) zero[i] = 0.0;
@@ -1543,88 +1663,13 @@ struct SmallSolver {
                 for (int i = 0; i < NX; ++i) Dx[i] = 0.0, Dnu[i] = 0.0;
 #pragma unroll
                 for (int i = 0; i < NU; ++i) Du[i] = 0.0;
-            } else if constexpr (MX) {   // NU = 1: one adjoint solve
-                const bool okf = mx_pred<true>(Hs, rt, zero);
-                mx_dnu(rt, true);
-                double oe[2] = {okf ? 0.0 : 1.0, capped_x ? 1.0 : 0.0};   // the two flags of the instance in one reduction pass
-                seg_reduce<2, 0, M::SEG_SKIP, SHORT>(oe, nullptr, k, lpi, base);
-                okall = oe[0] < 0.5;
-                // Richardson extrapolation in the stiffness cap (round 6).  Where the cap binds on a STATE row the capped solve is off by
-                // c / W — 1.5e-6 ... 3.6e-6 of du0/dp on cartpole states with the cart at the end of its track, measured against
-                // third-party finite differences (G7b) — linear in 1 / W down to W ~ 1e11, while the recursion's rounding grows with W
-                // (table at SENS_W_MAX).  y = 2 y(W) - y(W / 2) takes the bias out at W's rounding level (3e-9 on the same states).
-                // Decided per INSTANCE (an instance's numbers never depend on its wavefront neighbours); the second solve runs for the
-                // wavefront when any of its instances needs it — none of the benchmark's, whose state bounds are inactive.
-                const bool extrap = oe[1] > 0.5;
-                if (__any(extrap)) {
-                    double y1x[NX], y1n[NX];
-                    const double y1u = Du[0];
-#pragma unroll
-                    for (int i = 0; i < NX; ++i) y1x[i] = Dx[i], y1n[i] = Dnu[i];
-#pragma unroll
-                    for (int i = 0; i < NW; ++i) {
-                        double d = 0.0;
-#pragma unroll
-                        for (int sd = 0; sd < 2; ++sd)
-                            if (has(sd, i)) d += fmin(lam[sd][i] / t[sd][i], 0.5 * SENS_W_MAX);
-                        Dg[i] = d;
-                    }
-                    const bool okf2 = mx_pred<true>(Hs, rt, zero);
-                    mx_dnu(rt, true);
-                    const bool ok2 = seg_max<M::SEG_SKIP, SHORT>(okf2 ? 0.0 : 1.0, k, lpi, base) < 0.5;
-                    okall = okall && (ok2 || !extrap);
-                    Du[0] = extrap ? fma(2.0, y1u, -Du[0]) : y1u;
-#pragma unroll
-                    for (int i = 0; i < NX; ++i) Dx[i] = extrap ? fma(2.0, y1x[i], -Dx[i]) : y1x[i], Dnu[i] = extrap ? fma(2.0, y1n[i], -Dnu[i]) : y1n[i];
-                }
-            } else {
-                if (iu == 0) {
-                    const bool okf = backward(Hs, rt, zero);
-                    okall = seg_max<M::SEG_SKIP, SHORT>(okf ? 0.0 : 1.0, k, lpi, base) < 0.5;
-                } else
-                    backward_scan(rt, zero);
-                forward_scan(zero);
-            }
-            double ynn[NX], yv[NW];
+            } else
+                kkt_solve<true>(Hx, zero, capped_x, iu, okall);
+            // the sums of this control's row of du0*/dp and, with the first control, those of dV/dp
+            double ynn[NX], sums[2 * NT];
 #pragma unroll
             for (int i = 0; i < NX; ++i) ynn[i] = lane_dn(Dnu[i]);
-#pragma unroll
-            for (int i = 0; i < NW; ++i) yv[i] = dvc(Dx, Du, i);
-            double outd[NTD], outc[NTC > 0 ? NTC : 1];
-#pragma unroll
-            for (int d = 0; d < NTD; ++d) outd[d] = 0.0;
-#pragma unroll
-            for (int d = 0; d < (NTC > 0 ? NTC : 1); ++d) outc[d] = 0.0;
-            M::cost_mixed(term, yv, ck, outc);
-            if (!term) {
-                Jet2<NTD> jx[NX], ju[NU], jt[NTD], jn[NX];
-#pragma unroll
-                for (int i = 0; i < NU; ++i) ju[i] = Jet2<NTD>(u[i]), ju[i].e = yv[i];
-#pragma unroll
-                for (int i = 0; i < NX; ++i) jx[i] = Jet2<NTD>(x[i]), jx[i].e = yv[NU + i];
-#pragma unroll
-                for (int i = 0; i < NTD; ++i) jt[i] = Jet2<NTD>(thd[i]), jt[i].g[i] = 1.0;
-                disc_map<M, Jet2<NTD>>(jx, ju, jt, jn, sp.h, sp.rk_steps);
-                if (iu == 0) {
-#pragma unroll
-                    for (int m = 0; m < NX; ++m)
-#pragma unroll
-                        for (int d = 0; d < NTD; ++d) Fth[m * NTD + d] = jn[m].g[d];
-                }
-#pragma unroll
-                for (int d = 0; d < NTD; ++d) {
-                    double a = 0.0;
-#pragma unroll
-                    for (int m = 0; m < NX; ++m) a = fma(nun[m], jn[m].m[d], fma(ynn[m], Fth[m * NTD + d], a));
-                    outd[d] = a;
-                }
-            }
-            // the sums of this control's row of du0*/dp and, with the first control, those of dV/dp
-            double sums[2 * NT];
-#pragma unroll
-            for (int d = 0; d < NTD; ++d) sums[d] = outd[d];
-#pragma unroll
-            for (int d = 0; d < NTC; ++d) sums[NTD + d] = outc[d];
+            dtheta_contract(nun, ynn, sums, iu == 0 ? Fth : nullptr);
             if (iu == 0 && want_v) {   // (wave-uniform)
                 dV_parts(sums + NT);
                 seg_reduce<0, 2 * NT, M::SEG_SKIP, SHORT>(nullptr, sums, k, lpi, base);

@@ -4,10 +4,9 @@
 //   stage0_grad_kernel<M>            dV/dx0 (dQ/dx0 in Q mode) = grad_x l0 and dQ/du0 = grad_u l0 at (x_0, u_0), with
 //                                    l0(x, u) = c_0 l_0(x, u, theta) + pi_1' F(x, u, theta).  All three models.
 //   small_state_sens_kernel<M, S>    du0*/dx0 of the cartpole and the linear system: the adjoint solve of the du0*/dp pass
-//                                    (SmallSolver::sensitivities: exact Lagrangian Hessian, barrier diagonal lam / t capped at
-//                                    SENS_W_MAX, on the cartpole the extrapolation 2 y(W) - y(W / 2) where the cap binds on a state
-//                                    row), contracted with the two places x0 enters once x_0 is eliminated: the (u, x) block of the
-//                                    stage-0 Hessian and A_0.  No parameter jets run.
+//                                    (SmallSolver::kkt_assemble / kkt_solve, small_kernel.hpp), contracted with the two places x0
+//                                    enters once x_0 is eliminated: the (u, x) block of the stage-0 Hessian and A_0
+//                                    (SmallSolver::dx0_contract).  No parameter jets run.
 //
 // Neither kernel has the status word of the solve (mpcrl_solve writes it into the caller's array, the handle does not keep it): an
 // instance counts as solved when its stored residuals, its stored x, u, pi and its dynamics parameters are all finite
@@ -18,6 +17,14 @@
 #include "small_kernel.hpp"
 
 namespace mpcrl {
+
+// the iterate a solve stored, as the lane-layout kernels of this unit take it (mpcrl_state.hip: iterate_args)
+struct IterateArgs {
+    int B, theta_stride;
+    const int *perm;                         // packing order of the handle or null (results do not depend on it)
+    const double *theta;                     // [np] or [B, np]
+    const double *X, *U, *PI, *BND, *RES;    // stored iterate, layouts of mpcrl_get_iterate
+};
 
 struct Stage0Args {
     int B, N, theta_stride, rk_steps;
@@ -97,16 +104,13 @@ __global__ void __launch_bounds__(64) stage0_grad_kernel(const Stage0Args a) {
 }
 
 struct StateSensArgs {
-    int B, theta_stride;
-    const int *perm;                         // packing order of the handle or null (results do not depend on it)
-    const double *theta;
-    const double *X, *U, *PI, *BND, *RES;    // stored iterate
-    double *dpi;                             // [B, nu, nx]
+    IterateArgs it;
+    double *dpi;   // [B, nu, nx]
 };
 
 // Lane layout, loads and linearisation of small_sens_kernel (one lane per stage, min(64 / (N + 1), M::MAX_IPW) instances per
-// wavefront); V mode only (the host writes the zeros of Q mode).  The Hessian assembly and the cap / extrapolation block restate
-// SmallSolver::sensitivities so that du0*/dp and du0*/dx0 describe one linearised KKT system.
+// wavefront); V mode only (the host writes the zeros of Q mode).  The linearised KKT system and its solve are SmallSolver's
+// (kkt_assemble, kkt_solve in small_kernel.hpp), the ones of the du0*/dp pass.
 template <class M, bool SHORT = false>
 __global__ void __launch_bounds__(64) small_state_sens_kernel(const SmallSpec sp, const StateSensArgs a) {
     using SS = SmallSolver<M, SHORT>;
@@ -115,9 +119,9 @@ __global__ void __launch_bounds__(64) small_state_sens_kernel(const SmallSpec sp
     const int N = sp.N, lpi = N + 1, ipw = min(64 / lpi, M::MAX_IPW);
     const int slot = lane / lpi, k = lane - slot * lpi, base = slot * lpi;
     long inst = (long)blockIdx.x * ipw + slot;
-    const bool valid = slot < ipw && inst < a.B;
-    if (!valid) inst = a.B - 1;
-    if (a.perm) inst = a.perm[inst];
+    const bool valid = slot < ipw && inst < a.it.B;
+    if (!valid) inst = a.it.B - 1;
+    if (a.it.perm) inst = a.it.perm[inst];
     SS S(sp, k, lpi, base);
     __shared__ __attribute__((aligned(16))) double mx_lds[SS::MX ? SS::MX_LDS : 2];
     S.ms = mx_lds;
@@ -128,7 +132,7 @@ __global__ void __launch_bounds__(64) small_state_sens_kernel(const SmallSpec sp
         S.ck = term ? 1.0 : sp.dT;
     else
         S.ck = first ? sp.dT : (term ? pow(sp.gamma, (double)N) : pow(sp.gamma, (double)k) * sp.dT);
-    const double *th = a.theta + (size_t)inst * a.theta_stride;
+    const double *th = a.it.theta + (size_t)inst * a.it.theta_stride;
     __shared__ double c_lds[M::MAX_IPW * SS::CTAB];
     S.fill_cost_table(c_lds, slot < ipw ? slot : 0, slot < ipw, th);
     SS::wave_lds_sync();
@@ -145,59 +149,31 @@ __global__ void __launch_bounds__(64) small_state_sens_kernel(const SmallSpec sp
 #pragma unroll
     for (int i = 0; i < NTC; ++i) S.thc.set(i, th[M::tc_index(i)]);
     const size_t nb = (size_t)(N + 1) * NW;
-    const double *bnd = a.BND + (size_t)inst * 10 * nb + (size_t)k * NW;
+    const double *bnd = a.it.BND + (size_t)inst * 10 * nb + (size_t)k * NW;
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
-        S.x[i] = a.X[(inst * (N + 1) + k) * NX + i];
-        S.nu_[i] = first ? 0.0 : a.PI[(inst * N + k - 1) * NX + i];
+        S.x[i] = a.it.X[(inst * (N + 1) + k) * NX + i];
+        S.nu_[i] = first ? 0.0 : a.it.PI[(inst * N + k - 1) * NX + i];
         bad |= iterate_entry_bad(S.x[i]) || iterate_entry_bad(S.nu_[i]);
     }
 #pragma unroll
-    for (int i = 0; i < NU; ++i) S.u[i] = term ? 0.0 : a.U[(inst * N + k) * NU + i], bad |= iterate_entry_bad(S.u[i]);
+    for (int i = 0; i < NU; ++i) S.u[i] = term ? 0.0 : a.it.U[(inst * N + k) * NU + i], bad |= iterate_entry_bad(S.u[i]);
 #pragma unroll
     for (int i = 0; i < NW; ++i) S.lam[0][i] = bnd[0 * nb + i], S.lam[1][i] = bnd[1 * nb + i], S.t[0][i] = bnd[2 * nb + i], S.t[1][i] = bnd[3 * nb + i];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) bad |= iterate_entry_bad(a.RES[inst * 4 + j]);
+    for (int j = 0; j < 4; ++j) bad |= iterate_entry_bad(a.it.RES[inst * 4 + j]);
     const bool sv = valid && seg_max<M::SEG_SKIP, SHORT>(bad ? 1.0 : 0.0, k, lpi, base) < 0.5;
+    double nun[NX], hdd[SS::NHD], Hx[SS::NHT];
     // the dynamics Jacobians and the second-order term of the final iterate, as the du0*/dp pass linearises it
-    double xn[NX], nun[NX];
+    double xn[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) xn[i] = lane_dn(S.x[i]), nun[i] = lane_dn(S.nu_[i]);
-    double hdd[M::NLD * (M::NLD + 1) / 2];
     S.template linearize<true>(xn, nun, hdd);
 #pragma unroll
     for (int i = 0; i < SS::NPK; ++i) S.P[i] = 0.0;
 #pragma unroll
     for (int i = 0; i < NX; ++i) S.p[i] = 0.0;
-    // exact Lagrangian Hessian of the stage: c hess l + sum_m nu_{k+1,m} hess F_m
-    double Hx[NW * (NW + 1) / 2];
-#pragma unroll
-    for (int i = 0; i < NW; ++i)
-#pragma unroll
-        for (int j = 0; j <= i; ++j) Hx[SS::sym(i, j)] = S.ck * S.hess_of_stage(i, j);
-    {
-        constexpr int ND = M::NLD;
-#pragma unroll
-        for (int di = 0; di < ND; ++di)
-#pragma unroll
-            for (int dj = 0; dj <= di; ++dj) Hx[SS::sym(M::lin_coord(di), M::lin_coord(dj))] += hdd[di * (di + 1) / 2 + dj];
-    }
-    // barrier diagonal from the final (lam, t) of the bound rows, capped as in the du0*/dp pass
-    bool capped_x = false;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) {
-        double d = 0.0;
-#pragma unroll
-        for (int sd = 0; sd < 2; ++sd)
-            if (S.has(sd, i)) {
-                const double w = S.lam[sd][i] / S.t[sd][i];
-                d += fmin(w, SENS_W_MAX);
-                if (i >= NU && w > SENS_W_MAX) capped_x = true;
-            }
-        S.Dg[i] = d;
-    }
-    auto Hs = [&](int i, int j) { return Hx[SS::sym(i, j)]; };
-    S.hscale = 1.0;
+    const bool capped_x = S.kkt_assemble(Hx, hdd);
     double zero[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) zero[i] = 0.0;
@@ -206,55 +182,14 @@ __global__ void __launch_bounds__(64) small_state_sens_kernel(const SmallSpec sp
     for (int iu = 0; iu < NU; ++iu) {
 #pragma unroll
         for (int i = 0; i < NW; ++i) S.rt[i] = (first && i == iu) ? -1.0 : 0.0;
-        if constexpr (SS::MX) {   // NU = 1: one adjoint solve
-            const bool okf = S.template mx_pred<true>(Hs, S.rt, zero);
-            S.mx_dnu(S.rt, true);
-            double oe[2] = {okf ? 0.0 : 1.0, capped_x ? 1.0 : 0.0};
-            seg_reduce<2, 0, M::SEG_SKIP, SHORT>(oe, nullptr, k, lpi, base);
-            okall = oe[0] < 0.5;
-            const bool extrap = oe[1] > 0.5;   // per instance; the second solve runs for the wavefront when any of its instances needs it
-            if (__any(extrap)) {
-                double y1x[NX], y1n[NX];
-                const double y1u = S.Du[0];
-#pragma unroll
-                for (int i = 0; i < NX; ++i) y1x[i] = S.Dx[i], y1n[i] = S.Dnu[i];
-#pragma unroll
-                for (int i = 0; i < NW; ++i) {
-                    double d = 0.0;
-#pragma unroll
-                    for (int sd = 0; sd < 2; ++sd)
-                        if (S.has(sd, i)) d += fmin(S.lam[sd][i] / S.t[sd][i], 0.5 * SENS_W_MAX);
-                    S.Dg[i] = d;
-                }
-                const bool okf2 = S.template mx_pred<true>(Hs, S.rt, zero);
-                S.mx_dnu(S.rt, true);
-                const bool ok2 = seg_max<M::SEG_SKIP, SHORT>(okf2 ? 0.0 : 1.0, k, lpi, base) < 0.5;
-                okall = okall && (ok2 || !extrap);
-                S.Du[0] = extrap ? fma(2.0, y1u, -S.Du[0]) : y1u;
-#pragma unroll
-                for (int i = 0; i < NX; ++i)
-                    S.Dx[i] = extrap ? fma(2.0, y1x[i], -S.Dx[i]) : y1x[i], S.Dnu[i] = extrap ? fma(2.0, y1n[i], -S.Dnu[i]) : y1n[i];
-            }
-        } else {
-            if (iu == 0) {
-                const bool okf = S.backward(Hs, S.rt, zero);
-                okall = seg_max<M::SEG_SKIP, SHORT>(okf ? 0.0 : 1.0, k, lpi, base) < 0.5;
-            } else
-                S.backward_scan(S.rt, zero);
-            S.forward_scan(zero);
-        }
-        // x_0 is eliminated: x0 enters the stationarity row of u_0 through d2 l0 / du dx and the dynamics row F(x0, u_0) - x_1
-        // through A_0.  The parameter pass solves with the right-hand side -e and stores minus its sums; so does this one.
+        S.template kkt_solve<true>(Hx, zero, capped_x, iu, okall);
+        // The parameter pass solves with the right-hand side -e and stores minus its sums; so does this one.
         double ynn[NX];
 #pragma unroll
         for (int i = 0; i < NX; ++i) ynn[i] = lane_dn(S.Dnu[i]);
 #pragma unroll
         for (int j = 0; j < NX; ++j) {
-            double s = 0.0;
-#pragma unroll
-            for (int i = 0; i < NU; ++i) s = fma(S.Du[i], Hx[SS::sym(i, NU + j)], s);
-#pragma unroll
-            for (int m = 0; m < NX; ++m) s = fma(ynn[m], S.Aget(m * NX + j), s);
+            const double s = S.dx0_contract(Hx, ynn, j);
             if (first && valid) a.dpi[(inst * NU + iu) * NX + j] = sv ? (okall ? -s : NAN) : 0.0;
         }
     }

@@ -4,9 +4,9 @@
 //   small_traj_jvp_kernel<M, S>    for R directions (dx0 [nx], dtheta [np]) per instance of the cartpole and the linear system:
 //                                  dX[k] = dx_k*/dx0 dx0 + dx_k*/dtheta dtheta and dU[k], the same for u_k*.
 //
-// The forward mode of small_traj_vjp_kernel (traj_vjp_kernel.hpp): the same KKT matrix K of the du0*/dp pass (exact Lagrangian
-// Hessian, barrier diagonal lam / t capped at SENS_W_MAX, on the cartpole the extrapolation 2 y(W) - y(W / 2) where the cap binds on a
-// state row), solved once with the right-hand side -(dR/dtheta dtheta + dR/dx0 dx0), and the primal part of the solution written out.
+// The forward mode of small_traj_vjp_kernel (traj_vjp_kernel.hpp): the same KKT matrix K of the du0*/dp pass
+// (SmallSolver::kkt_assemble / kkt_solve, small_kernel.hpp), solved once with the right-hand side
+// -(dR/dtheta dtheta + dR/dx0 dx0), and the primal part of the solution written out.
 // In the solver's terms, min 1/2 Dv' H Dv + g' Dv subject to Dx_{k+1} = A Dx_k + B Du_k + bb_k with, on stage lane k,
 //     bb_k   = dF_k/dtheta dtheta                          (k < N)           + A_0 dx0 on stage 0
 //     g_k[i] = sum_m nu_{k+1,m} d2 F_{k,m} / dv_i dtheta dtheta
@@ -18,18 +18,16 @@
 // the entries M::td_index(i) and M::tc_index(i) are read, the entries g_theta of the VJP is non-zero at; the rest (the cartpole's cost
 // block) is ignored.
 //
-// Lane layout, loads, the "solved" rule, the linearisation, the Hessian assembly and the cap / extrapolation block restate
-// small_traj_vjp_body so that du0*/dp, du0*/dx0, the VJP and this product describe one linearised KKT system.  Work item j = inst R + r
-// takes the place the instance has there; every item linearises and factors for itself.  The packing order of the handle is not used.
+// Lane layout, loads, the "solved" rule and the linearisation are those of small_traj_vjp_body.  Work item j = inst R + r takes
+// the place the instance has there; every item linearises and factors for itself.  The packing order of the handle is not used.
 #pragma once
 #include "state_sens_kernel.hpp"
 
 namespace mpcrl {
 
 struct TrajJvpArgs {
-    int B, R, theta_stride;
-    const double *theta;
-    const double *X, *U, *PI, *BND, *RES;    // stored iterate
+    IterateArgs it;                          // (perm is not read)
+    int R;
     const double *dx0, *dth;                 // directions [B, R, nx] / [B, R, np]; null = zeros
     double *dX, *dU;                         // [B, R, N + 1, nx] / [B, R, N, nu]; either may be null
 };
@@ -43,7 +41,7 @@ __global__ void __launch_bounds__(64) small_traj_jvp_kernel(const SmallSpec sp, 
     const int lane = threadIdx.x;
     const int N = sp.N, lpi = N + 1, ipw = min(64 / lpi, M::MAX_IPW);
     const int slot = lane / lpi, k = lane - slot * lpi, base = slot * lpi;
-    const long items = (long)a.B * a.R;
+    const long items = (long)a.it.B * a.R;
     long item = (long)blockIdx.x * ipw + slot;
     const bool valid = slot < ipw && item < items;
     if (!valid) item = items - 1;
@@ -58,7 +56,7 @@ __global__ void __launch_bounds__(64) small_traj_jvp_kernel(const SmallSpec sp, 
         S.ck = term ? 1.0 : sp.dT;
     else
         S.ck = first ? sp.dT : (term ? pow(sp.gamma, (double)N) : pow(sp.gamma, (double)k) * sp.dT);
-    const double *th = a.theta + (size_t)inst * a.theta_stride;
+    const double *th = a.it.theta + (size_t)inst * a.it.theta_stride;
     __shared__ double c_lds[M::MAX_IPW * SS::CTAB];
     S.fill_cost_table(c_lds, slot < ipw ? slot : 0, slot < ipw, th);
     SS::wave_lds_sync();
@@ -75,19 +73,19 @@ __global__ void __launch_bounds__(64) small_traj_jvp_kernel(const SmallSpec sp, 
 #pragma unroll
     for (int i = 0; i < NTC; ++i) S.thc.set(i, th[M::tc_index(i)]);
     const size_t nb = (size_t)(N + 1) * NW;
-    const double *bnd = a.BND + (size_t)inst * 10 * nb + (size_t)k * NW;
+    const double *bnd = a.it.BND + (size_t)inst * 10 * nb + (size_t)k * NW;
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
-        S.x[i] = a.X[(inst * (N + 1) + k) * NX + i];
-        S.nu_[i] = first ? 0.0 : a.PI[(inst * N + k - 1) * NX + i];
+        S.x[i] = a.it.X[(inst * (N + 1) + k) * NX + i];
+        S.nu_[i] = first ? 0.0 : a.it.PI[(inst * N + k - 1) * NX + i];
         bad |= iterate_entry_bad(S.x[i]) || iterate_entry_bad(S.nu_[i]);
     }
 #pragma unroll
-    for (int i = 0; i < NU; ++i) S.u[i] = term ? 0.0 : a.U[(inst * N + k) * NU + i], bad |= iterate_entry_bad(S.u[i]);
+    for (int i = 0; i < NU; ++i) S.u[i] = term ? 0.0 : a.it.U[(inst * N + k) * NU + i], bad |= iterate_entry_bad(S.u[i]);
 #pragma unroll
     for (int i = 0; i < NW; ++i) S.lam[0][i] = bnd[0 * nb + i], S.lam[1][i] = bnd[1 * nb + i], S.t[0][i] = bnd[2 * nb + i], S.t[1][i] = bnd[3 * nb + i];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) bad |= iterate_entry_bad(a.RES[inst * 4 + j]);
+    for (int j = 0; j < 4; ++j) bad |= iterate_entry_bad(a.it.RES[inst * 4 + j]);
     const bool sv = valid && seg_max<M::SEG_SKIP, SHORT>(bad ? 1.0 : 0.0, k, lpi, base) < 0.5;
     // the direction of this item
     double dx0[NX], dtd[NTD], dtc[NTC > 0 ? NTC : 1];
@@ -97,44 +95,28 @@ __global__ void __launch_bounds__(64) small_traj_jvp_kernel(const SmallSpec sp, 
     for (int i = 0; i < NTD; ++i) dtd[i] = a.dth ? a.dth[item * M::NP + M::td_index(i)] : 0.0;
 #pragma unroll
     for (int i = 0; i < NTC; ++i) dtc[i] = a.dth ? a.dth[item * M::NP + M::tc_index(i)] : 0.0;
+    double nun[NX], hdd[SS::NHD];
     // the dynamics Jacobians and the second-order term of the final iterate, as the du0*/dp pass linearises it
-    double xn[NX], nun[NX];
+    double xn[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) xn[i] = lane_dn(S.x[i]), nun[i] = lane_dn(S.nu_[i]);
-    double hdd[M::NLD * (M::NLD + 1) / 2];
     S.template linearize<true>(xn, nun, hdd);
 #pragma unroll
     for (int i = 0; i < SS::NPK; ++i) S.P[i] = 0.0;
 #pragma unroll
     for (int i = 0; i < NX; ++i) S.p[i] = 0.0;
-    // exact Lagrangian Hessian of the stage: c hess l + sum_m nu_{k+1,m} hess F_m
-    double Hx[NW * (NW + 1) / 2];
+    // the Hessian fill of SmallSolver::kkt_assemble in this kernel's own text: through the shared function the cartpole
+    // instantiations spill 92 bytes of scratch per lane instead of 76 (profiles/sens_kkt_kernel_resources.txt)
+    double Hx[SS::NHT];
 #pragma unroll
     for (int i = 0; i < NW; ++i)
 #pragma unroll
         for (int j = 0; j <= i; ++j) Hx[SS::sym(i, j)] = S.ck * S.hess_of_stage(i, j);
-    {
-        constexpr int ND = M::NLD;
 #pragma unroll
-        for (int di = 0; di < ND; ++di)
+    for (int di = 0; di < M::NLD; ++di)
 #pragma unroll
-            for (int dj = 0; dj <= di; ++dj) Hx[SS::sym(M::lin_coord(di), M::lin_coord(dj))] += hdd[di * (di + 1) / 2 + dj];
-    }
-    // barrier diagonal from the final (lam, t) of the bound rows, capped as in the du0*/dp pass
-    bool capped_x = false;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) {
-        double d = 0.0;
-#pragma unroll
-        for (int sd = 0; sd < 2; ++sd)
-            if (S.has(sd, i)) {
-                const double w = S.lam[sd][i] / S.t[sd][i];
-                d += fmin(w, SENS_W_MAX);
-                if (i >= NU && w > SENS_W_MAX) capped_x = true;
-            }
-        S.Dg[i] = d;
-    }
-    auto Hs = [&](int i, int j) { return Hx[SS::sym(i, j)]; };
+        for (int dj = 0; dj <= di; ++dj) Hx[SS::sym(M::lin_coord(di), M::lin_coord(dj))] += hdd[di * (di + 1) / 2 + dj];
+    const bool capped_x = S.barrier_diag(SENS_W_MAX);
     S.hscale = 1.0;
     // the right-hand side: (dR/dtheta dtheta + dR/dx0 dx0) of this stage, stationarity rows in S.rt and dynamics rows in bb
     double bb[NX];
@@ -201,37 +183,7 @@ __global__ void __launch_bounds__(64) small_traj_jvp_kernel(const SmallSpec sp, 
         for (int i = 0; i < NU; ++i) S.rt[i] = 0.0;
     }
     bool okall = true;
-    if constexpr (SS::MX) {
-        const bool okf = S.template mx_pred<true>(Hs, S.rt, bb);
-        double oe[2] = {okf ? 0.0 : 1.0, capped_x ? 1.0 : 0.0};
-        seg_reduce<2, 0, M::SEG_SKIP, SHORT>(oe, nullptr, k, lpi, base);
-        okall = oe[0] < 0.5;
-        const bool extrap = oe[1] > 0.5;   // per item; the second solve runs for the wavefront when any of its items needs it
-        if (__any(extrap)) {
-            double y1x[NX];
-            const double y1u = S.Du[0];
-#pragma unroll
-            for (int i = 0; i < NX; ++i) y1x[i] = S.Dx[i];
-#pragma unroll
-            for (int i = 0; i < NW; ++i) {
-                double d = 0.0;
-#pragma unroll
-                for (int sd = 0; sd < 2; ++sd)
-                    if (S.has(sd, i)) d += fmin(S.lam[sd][i] / S.t[sd][i], 0.5 * SENS_W_MAX);
-                S.Dg[i] = d;
-            }
-            const bool okf2 = S.template mx_pred<true>(Hs, S.rt, bb);
-            const bool ok2 = seg_max<M::SEG_SKIP, SHORT>(okf2 ? 0.0 : 1.0, k, lpi, base) < 0.5;
-            okall = okall && (ok2 || !extrap);
-            S.Du[0] = extrap ? fma(2.0, y1u, -S.Du[0]) : y1u;
-#pragma unroll
-            for (int i = 0; i < NX; ++i) S.Dx[i] = extrap ? fma(2.0, y1x[i], -S.Dx[i]) : y1x[i];
-        }
-    } else {
-        const bool okf = S.backward(Hs, S.rt, bb);
-        okall = seg_max<M::SEG_SKIP, SHORT>(okf ? 0.0 : 1.0, k, lpi, base) < 0.5;
-        S.forward_scan(bb);
-    }
+    S.template kkt_solve<false>(Hx, bb, capped_x, 0, okall);
     if (!valid) return;
     if (a.dX) {
 #pragma unroll

@@ -4,15 +4,11 @@
 //   small_traj_vjp_kernel<M, S>    for a cotangent G = (G_X [N + 1, nx], G_U [N, nu]) on (X*, U*) of the cartpole and the linear system:
 //                                  g_theta = sum_k G_X[k]' dx_k*/dtheta + G_U[k]' du_k*/dtheta and g_x0, the same sums over d/dx0.
 //
-// The KKT matrix of the du0*/dp pass (SmallSolver::sensitivities: exact Lagrangian Hessian, barrier diagonal lam / t capped at
-// SENS_W_MAX, on the cartpole the extrapolation 2 y(W) - y(W / 2) where the cap binds on a state row) is symmetric, so G' dw*/d(.) =
+// The KKT matrix of the du0*/dp pass (SmallSolver::kkt_assemble / kkt_solve, small_kernel.hpp) is symmetric, so G' dw*/d(.) =
 // -(K^-1 G)' dR/d(.): ONE adjoint solve with the right-hand side -G spread over the stages, whatever the horizon, then the two
-// contractions the library already has for the right-hand side -e_{u_0}: with dR/dtheta as sensitivities() contracts it (the Jet2<NTD>
-// mixed evaluation of the discrete map along y, plus M::cost_mixed), and with dR/dx0 as small_state_sens_kernel contracts it (the (u, x)
-// block of the stage-0 Hessian and A_0), plus G_X[0] itself because x_0 = x0.
-//
-// Lane layout, loads, the "solved" rule and the linearisation are those of small_state_sens_kernel; the Hessian assembly and the cap /
-// extrapolation block restate it so that du0*/dp, du0*/dx0 and this product describe one linearised KKT system.
+// contractions the library already has for the right-hand side -e_{u_0}: with dR/dtheta as sensitivities() contracts it
+// (SmallSolver::dtheta_contract), and with dR/dx0 as small_state_sens_kernel contracts it (SmallSolver::dx0_contract), plus G_X[0]
+// itself because x_0 = x0.  Lane layout, loads, the "solved" rule and the linearisation are those of small_state_sens_kernel.
 //
 // The kernel's body is small_traj_vjp_body<M, S, BOUNDS, COST>: BOUNDS = false is this kernel, BOUNDS = true the kernel of
 // include/mpcrl_bound_ext.h (bound_vjp_kernel.hpp), which contracts the same solution with the bound rows as well.  Everything the
@@ -29,12 +25,9 @@ struct NoCostOut {
 };
 
 struct TrajVjpArgs {
-    int B, theta_stride;
-    const int *perm;                         // packing order of the handle or null (results do not depend on it)
-    const double *theta;
-    const double *X, *U, *PI, *BND, *RES;    // stored iterate
-    const double *gX, *gU;                   // cotangents [B, N + 1, nx] / [B, N, nu]; null = zeros
-    double *g_x0, *g_theta;                  // [B, nx] / [B, np]; either may be null
+    IterateArgs it;
+    const double *gX, *gU;     // cotangents [B, N + 1, nx] / [B, N, nu]; null = zeros
+    double *g_x0, *g_theta;    // [B, nx] / [B, np]; either may be null
 };
 
 // Every requested row is written in full: zeros for an instance without a solved iterate and at the entries of p the sensitivity pass
@@ -50,9 +43,9 @@ MPCRL_DI void small_traj_vjp_body(const SmallSpec sp, const TrajVjpArgs a, doubl
     const int N = sp.N, lpi = N + 1, ipw = min(64 / lpi, M::MAX_IPW);
     const int slot = lane / lpi, k = lane - slot * lpi, base = slot * lpi;
     long inst = (long)blockIdx.x * ipw + slot;
-    const bool valid = slot < ipw && inst < a.B;
-    if (!valid) inst = a.B - 1;
-    if (a.perm) inst = a.perm[inst];
+    const bool valid = slot < ipw && inst < a.it.B;
+    if (!valid) inst = a.it.B - 1;
+    if (a.it.perm) inst = a.it.perm[inst];
     SS S(sp, k, lpi, base);
     __shared__ __attribute__((aligned(16))) double mx_lds[SS::MX ? SS::MX_LDS : 2];
     S.ms = mx_lds;
@@ -63,7 +56,7 @@ MPCRL_DI void small_traj_vjp_body(const SmallSpec sp, const TrajVjpArgs a, doubl
         S.ck = term ? 1.0 : sp.dT;
     else
         S.ck = first ? sp.dT : (term ? pow(sp.gamma, (double)N) : pow(sp.gamma, (double)k) * sp.dT);
-    const double *th = a.theta + (size_t)inst * a.theta_stride;
+    const double *th = a.it.theta + (size_t)inst * a.it.theta_stride;
     __shared__ double c_lds[M::MAX_IPW * SS::CTAB];
     S.fill_cost_table(c_lds, slot < ipw ? slot : 0, slot < ipw, th);
     SS::wave_lds_sync();
@@ -80,19 +73,19 @@ MPCRL_DI void small_traj_vjp_body(const SmallSpec sp, const TrajVjpArgs a, doubl
 #pragma unroll
     for (int i = 0; i < NTC; ++i) S.thc.set(i, th[M::tc_index(i)]);
     const size_t nb = (size_t)(N + 1) * NW;
-    const double *bnd = a.BND + (size_t)inst * 10 * nb + (size_t)k * NW;
+    const double *bnd = a.it.BND + (size_t)inst * 10 * nb + (size_t)k * NW;
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
-        S.x[i] = a.X[(inst * (N + 1) + k) * NX + i];
-        S.nu_[i] = first ? 0.0 : a.PI[(inst * N + k - 1) * NX + i];
+        S.x[i] = a.it.X[(inst * (N + 1) + k) * NX + i];
+        S.nu_[i] = first ? 0.0 : a.it.PI[(inst * N + k - 1) * NX + i];
         bad |= iterate_entry_bad(S.x[i]) || iterate_entry_bad(S.nu_[i]);
     }
 #pragma unroll
-    for (int i = 0; i < NU; ++i) S.u[i] = term ? 0.0 : a.U[(inst * N + k) * NU + i], bad |= iterate_entry_bad(S.u[i]);
+    for (int i = 0; i < NU; ++i) S.u[i] = term ? 0.0 : a.it.U[(inst * N + k) * NU + i], bad |= iterate_entry_bad(S.u[i]);
 #pragma unroll
     for (int i = 0; i < NW; ++i) S.lam[0][i] = bnd[0 * nb + i], S.lam[1][i] = bnd[1 * nb + i], S.t[0][i] = bnd[2 * nb + i], S.t[1][i] = bnd[3 * nb + i];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) bad |= iterate_entry_bad(a.RES[inst * 4 + j]);
+    for (int j = 0; j < 4; ++j) bad |= iterate_entry_bad(a.it.RES[inst * 4 + j]);
     const bool sv = valid && seg_max<M::SEG_SKIP, SHORT>(bad ? 1.0 : 0.0, k, lpi, base) < 0.5;
     // the cotangent of this stage: no control at the terminal stage, and x_0 is eliminated (G_X[0] enters g_x0 directly, below)
     double gx0[NX];
@@ -104,30 +97,31 @@ MPCRL_DI void small_traj_vjp_body(const SmallSpec sp, const TrajVjpArgs a, doubl
         S.rt[NU + i] = first ? 0.0 : -g;
         gx0[i] = g;   // (read on the first lane only)
     }
+    double nun[NX], hdd[SS::NHD];
     // the dynamics Jacobians and the second-order term of the final iterate, as the du0*/dp pass linearises it
-    double xn[NX], nun[NX];
+    double xn[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) xn[i] = lane_dn(S.x[i]), nun[i] = lane_dn(S.nu_[i]);
-    double hdd[M::NLD * (M::NLD + 1) / 2];
     S.template linearize<true>(xn, nun, hdd);
 #pragma unroll
     for (int i = 0; i < SS::NPK; ++i) S.P[i] = 0.0;
 #pragma unroll
     for (int i = 0; i < NX; ++i) S.p[i] = 0.0;
-    // exact Lagrangian Hessian of the stage: c hess l + sum_m nu_{k+1,m} hess F_m
-    double Hx[NW * (NW + 1) / 2];
+    // the Hessian fill of SmallSolver::kkt_assemble, in this body's own text as well
+    double Hx[SS::NHT];
 #pragma unroll
     for (int i = 0; i < NW; ++i)
 #pragma unroll
         for (int j = 0; j <= i; ++j) Hx[SS::sym(i, j)] = S.ck * S.hess_of_stage(i, j);
-    {
-        constexpr int ND = M::NLD;
 #pragma unroll
-        for (int di = 0; di < ND; ++di)
+    for (int di = 0; di < M::NLD; ++di)
 #pragma unroll
-            for (int dj = 0; dj <= di; ++dj) Hx[SS::sym(M::lin_coord(di), M::lin_coord(dj))] += hdd[di * (di + 1) / 2 + dj];
-    }
-    // barrier diagonal from the final (lam, t) of the bound rows, capped as in the du0*/dp pass
+        for (int dj = 0; dj <= di; ++dj) Hx[SS::sym(M::lin_coord(di), M::lin_coord(dj))] += hdd[di * (di + 1) / 2 + dj];
+    // From here to the bound rows after the solve this body keeps its OWN text of SmallSolver::barrier_diag / kkt_solve (the barrier
+    // diagonal capped at SENS_W_MAX, the solve, the per-instance extrapolation with its second solve at SENS_W_MAX / 2, the merge): with
+    // the shared members, bound_rows as a hook of kkt_solve, the cartpole cost kernel measured 0.4 .. 1.0 us slower on its g_cost-only
+    // call than the parent's whichever build ran first; with this text the six cartpole kernels of this body compile to the parent's
+    // instructions (profiles/sens_kkt_kernel_resources.txt).  A change to the cap rule or to the extrapolation is made in both places.
     bool capped_x = false;
 #pragma unroll
     for (int i = 0; i < NW; ++i) {
@@ -215,52 +209,17 @@ MPCRL_DI void small_traj_vjp_body(const SmallSpec sp, const TrajVjpArgs a, doubl
     double ynn[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) ynn[i] = lane_dn(S.Dnu[i]);
-    // x_0 is eliminated: x0 enters the stationarity row of u_0 through d2 l0 / du dx and the dynamics row F(x0, u_0) - x_1 through
-    // A_0 (small_state_sens_kernel), and x_0 itself is x0.  The solve had the right-hand side -G, so the product is minus the sums.
+    // x_0 itself is x0, and the solve had the right-hand side -G, so the product is minus the sums.
     if (a.g_x0) {
 #pragma unroll
         for (int j = 0; j < NX; ++j) {
-            double s = 0.0;
-#pragma unroll
-            for (int i = 0; i < NU; ++i) s = fma(S.Du[i], Hx[SS::sym(i, NU + j)], s);
-#pragma unroll
-            for (int m = 0; m < NX; ++m) s = fma(ynn[m], S.Aget(m * NX + j), s);
+            const double s = S.dx0_contract(Hx, ynn, j);
             if (first && valid) a.g_x0[inst * NX + j] = sv ? (okall ? gx0[j] - s : NAN) : 0.0;
         }
     }
     if (!a.g_theta) return;   // (wave-uniform)
-    // y' dR/dtheta as sensitivities() forms it for one control: the mixed second-order evaluation of the map along y
-    double yv[NW];
-#pragma unroll
-    for (int i = 0; i < NW; ++i) yv[i] = S.dvc(S.Dx, S.Du, i);
     double sums[NT];
-#pragma unroll
-    for (int d = 0; d < NT; ++d) sums[d] = 0.0;
-    {
-        double outc[NTC > 0 ? NTC : 1];
-#pragma unroll
-        for (int d = 0; d < (NTC > 0 ? NTC : 1); ++d) outc[d] = 0.0;
-        M::cost_mixed(term, yv, S.ck, outc);
-#pragma unroll
-        for (int d = 0; d < NTC; ++d) sums[NTD + d] = outc[d];
-    }
-    if (!term) {
-        Jet2<NTD> jx[NX], ju[NU], jt[NTD], jn[NX];
-#pragma unroll
-        for (int i = 0; i < NU; ++i) ju[i] = Jet2<NTD>(S.u[i]), ju[i].e = yv[i];
-#pragma unroll
-        for (int i = 0; i < NX; ++i) jx[i] = Jet2<NTD>(S.x[i]), jx[i].e = yv[NU + i];
-#pragma unroll
-        for (int i = 0; i < NTD; ++i) jt[i] = Jet2<NTD>(S.thd[i]), jt[i].g[i] = 1.0;
-        disc_map<M, Jet2<NTD>>(jx, ju, jt, jn, sp.h, sp.rk_steps);
-#pragma unroll
-        for (int d = 0; d < NTD; ++d) {
-            double s = 0.0;
-#pragma unroll
-            for (int m = 0; m < NX; ++m) s = fma(nun[m], jn[m].m[d], fma(ynn[m], jn[m].g[d], s));
-            sums[d] = s;
-        }
-    }
+    S.dtheta_contract(nun, ynn, sums, nullptr);
     seg_reduce<0, NT, M::SEG_SKIP, SHORT>(nullptr, sums, k, lpi, base);
 #pragma unroll
     for (int d = 0; d < NTD; ++d)
