@@ -14,8 +14,8 @@
  * Of dtheta only the entries the sensitivity pass differentiates are read (cartpole: m, M, l, entries 0 .. 2; linear system: all
  * 12), the entries g_theta of mpcrl_traj_vjp is non-zero at.  The rest — the cartpole's cost block, entries 3 .. 82 — is ignored.
  *
- * Out of scope: the chain of masses, MPCRL_STATE_Q_MODE (u_0 pinned), directions in the box bounds or in the cartpole's cost block,
- * and the tangent of the multipliers.
+ * Out of scope: the chain of masses (mpcrl_chain_traj_jvp_ext.h has a call of its own), MPCRL_STATE_Q_MODE (u_0 pinned), directions
+ * in the box bounds or in the cartpole's cost block, and the tangent of the multipliers.
  */
 #ifndef MPCRL_TRAJ_JVP_EXT_H
 #define MPCRL_TRAJ_JVP_EXT_H

@@ -8,7 +8,7 @@ PyTorch is used for device memory and streams only.  There is no CPU fallback: i
 classes without ``libmpcrl_hip.so`` raises.
 """
 from .problems import OcpDescription, cartpole_ocp, chain_mass_ocp, linear_system_ocp  # noqa: F401
-from .batch import BoxBounds, CartpoleCost, MPCBatch, SolveResult, StateSens, TrajectoryJacobian, cartpole_cost_of, cartpole_theta  # noqa: F401
+from .batch import BoxBounds, CartpoleCost, ChainTrajectoryJacobian, MPCBatch, SolveResult, StateSens, TrajectoryJacobian, cartpole_cost_of, cartpole_theta  # noqa: F401
 from .autograd import MPCFunction, MPCLayer, MPCQFunction, MPCTrajectoryFunction, mpc_backward_terms  # noqa: F401
 from .envs import BatchedCartPoleSwingUpEnv, BatchedChainMassEnv, BatchedLinearSystemEnv  # noqa: F401
 from .qlearning import BatchedQLearning, qlearning_gn_box_step, qlearning_gn_step, qlearning_gn_terms  # noqa: F401

@@ -1,4 +1,4 @@
-"""ctypes binding of libmpcrl_hip.so, read from include/mpcrl.h (and include/mpcrl_ext.h, include/mpcrl_chain_ext.h, include/mpcrl_traj_ext.h, include/mpcrl_chain_traj_ext.h, include/mpcrl_bound_ext.h, include/mpcrl_cost_ext.h, include/mpcrl_traj_jvp_ext.h and include/mpcrl_probe_ext.h, a table of its own each), and the one path the package calls the library through
+"""ctypes binding of libmpcrl_hip.so, read from include/mpcrl.h (and include/mpcrl_ext.h, include/mpcrl_chain_ext.h, include/mpcrl_traj_ext.h, include/mpcrl_chain_traj_ext.h, include/mpcrl_bound_ext.h, include/mpcrl_cost_ext.h, include/mpcrl_traj_jvp_ext.h, include/mpcrl_chain_traj_jvp_ext.h and include/mpcrl_probe_ext.h, a table of its own each), and the one path the package calls the library through
 (``call``, ``workspace``).  Fails loudly when the library is missing.
 
 The .hip units include the same header, so the compiler holds the implementation to it; the prototypes, constants and error codes here
@@ -133,6 +133,13 @@ with open(TRAJ_JVP_EXT_HEADER_PATH) as _f:
     TRAJ_JVP_EXT_HEADER = parse_header(_f.read())      # a ninth table (the #include of mpcrl_ext.h is not followed)
 TRAJ_JVP_EXT_EXPORTS = list(TRAJ_JVP_EXT_HEADER.functions)
 TRAJ_JVP_EXT_VERSION = TRAJ_JVP_EXT_HEADER.constants["TRAJ_JVP_EXT_VERSION"]
+CHAIN_TRAJ_JVP_EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mpcrl_chain_traj_jvp_ext.h")   # the trajectory JVP of the chain of masses, versioned on its own
+if not os.path.exists(CHAIN_TRAJ_JVP_EXT_HEADER_PATH):
+    raise ImportError(f"mpc4rl_amd: {CHAIN_TRAJ_JVP_EXT_HEADER_PATH} not found. The binding is read from the headers: keep include/ beside the package.")
+with open(CHAIN_TRAJ_JVP_EXT_HEADER_PATH) as _f:
+    CHAIN_TRAJ_JVP_EXT_HEADER = parse_header(_f.read())      # a tenth table (the #include of mpcrl_ext.h is not followed)
+CHAIN_TRAJ_JVP_EXT_EXPORTS = list(CHAIN_TRAJ_JVP_EXT_HEADER.functions)
+CHAIN_TRAJ_JVP_EXT_VERSION = CHAIN_TRAJ_JVP_EXT_HEADER.constants["CHAIN_TRAJ_JVP_EXT_VERSION"]
 PROBE_EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mpcrl_probe_ext.h")   # test probes of single kernel phases, versioned on their own
 if not os.path.exists(PROBE_EXT_HEADER_PATH):
     raise ImportError(f"mpc4rl_amd: {PROBE_EXT_HEADER_PATH} not found. The binding is read from the headers: keep include/ beside the package.")
@@ -236,6 +243,11 @@ def load():
     if not older and lib.mpcrl_traj_jvp_ext_version() != TRAJ_JVP_EXT_VERSION:
         raise RuntimeError(f"mpc4rl_amd: {LIB_PATH} reports trajectory JVP extension version {lib.mpcrl_traj_jvp_ext_version()}, this binding "
                            f"expects {TRAJ_JVP_EXT_VERSION}; rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`).")
+    if not (older and not hasattr(lib, "mpcrl_chain_traj_jvp_ext_version")):
+        lib.mpcrl_chain_traj_jvp_ext_version.restype = C.c_int
+    if not older and lib.mpcrl_chain_traj_jvp_ext_version() != CHAIN_TRAJ_JVP_EXT_VERSION:
+        raise RuntimeError(f"mpc4rl_amd: {LIB_PATH} reports chain trajectory JVP extension version {lib.mpcrl_chain_traj_jvp_ext_version()}, "
+                           f"this binding expects {CHAIN_TRAJ_JVP_EXT_VERSION}; rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`).")
     if not (older and not hasattr(lib, "mpcrl_probe_ext_version")):
         lib.mpcrl_probe_ext_version.restype = C.c_int
         if not older and lib.mpcrl_probe_ext_version() != PROBE_EXT_VERSION:
@@ -244,10 +256,10 @@ def load():
     for name, (ret, params) in (list(HEADER.functions.items()) + list(EXT_HEADER.functions.items()) + list(CHAIN_EXT_HEADER.functions.items())
                                 + list(TRAJ_EXT_HEADER.functions.items()) + list(CHAIN_TRAJ_EXT_HEADER.functions.items())
                                 + list(BOUND_EXT_HEADER.functions.items()) + list(COST_EXT_HEADER.functions.items())
-                                + list(TRAJ_JVP_EXT_HEADER.functions.items())
+                                + list(TRAJ_JVP_EXT_HEADER.functions.items()) + list(CHAIN_TRAJ_JVP_EXT_HEADER.functions.items())
                                 + list(PROBE_EXT_HEADER.functions.items())):
         if older and (name in BOUND_EXT_HEADER.functions or name in COST_EXT_HEADER.functions or name in TRAJ_JVP_EXT_HEADER.functions
-                      or name in PROBE_EXT_HEADER.functions) and not hasattr(lib, name):
+                      or name in CHAIN_TRAJ_JVP_EXT_HEADER.functions or name in PROBE_EXT_HEADER.functions) and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         fn.restype = _CTYPE[ret]

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import _ptr      # noqa: F401  (tests and profiles/microbench call the library directly with it)
-from .problems import OcpDescription
+from .problems import OcpDescription, chain_param_layout
 
 
 @dataclass
@@ -54,6 +54,39 @@ class TrajectoryJacobian(NamedTuple):
     dU_dx0: torch.Tensor       # [B, N, nu, nx]
     dX_dtheta: torch.Tensor    # [B, N + 1, nx, n_p]
     dU_dtheta: torch.Tensor    # [B, N, nu, n_p]
+
+
+class ChainTrajectoryJacobian(NamedTuple):
+    """``MPCBatch.chain_trajectory_jacobian``: columns of the Jacobian of the chain's planned trajectory with respect to the initial
+    state and to the entries ``entries`` of the parameters.  The parameter blocks are compact: one column per entry asked for."""
+    dX_dx0: torch.Tensor       # [B, N + 1, nx, nx]
+    dU_dx0: torch.Tensor       # [B, N, nu, nx]
+    dX_dtheta: torch.Tensor    # [B, N + 1, nx, len(entries)]
+    dU_dtheta: torch.Tensor    # [B, N, nu, len(entries)]
+    entries: torch.Tensor      # [len(entries)] int64: the index into p of each column
+
+
+def chain_jacobian_entries(n_mass: int, entries=None) -> np.ndarray:
+    """The index array into the chain's p that ``MPCBatch.chain_trajectory_jacobian(entries)`` differentiates: ``entries`` is an index
+    array (checked against n_p and returned as int64), or a block name or tuple of block names of ``chain_param_layout`` — the blocks
+    in the order given, each whole; None is the dynamics block ("m", "D", "L", "C")."""
+    off, n_p = chain_param_layout(n_mass)[4:]
+    if entries is None:
+        entries = ("m", "D", "L", "C")
+    if isinstance(entries, str):
+        entries = (entries,)
+    if len(entries) > 0 and all(isinstance(e, str) for e in entries):
+        unknown = [e for e in entries if e not in off]
+        if unknown:
+            raise ValueError(f"the chain's parameter blocks are {', '.join(off)}; got {', '.join(unknown)}")
+        return np.concatenate([np.arange(*off[e], dtype=np.int64) for e in entries])
+    idx = np.asarray(entries.cpu() if isinstance(entries, torch.Tensor) else entries)
+    if idx.ndim != 1 or idx.size < 1 or idx.dtype.kind not in "iu":
+        raise ValueError("entries is a one-dimensional integer index array into p, or a tuple of block names")
+    idx = idx.astype(np.int64)
+    if idx.min() < 0 or idx.max() >= n_p:
+        raise ValueError(f"entries index p, which has {n_p} entries at n_mass {n_mass}")
+    return idx
 
 
 class CartpoleCost(NamedTuple):
@@ -431,6 +464,70 @@ class MPCBatch:
         g_th = torch.empty((self.B, self.n_p), **kw) if theta else None
         self._call("mpcrl_chain_traj_vjp", 0, self._solve_status, gX, gU, g_x0, g_th)
         return g_x0, g_th
+
+    def chain_trajectory_jvp(self, dx0=None, dtheta=None, X: bool = True, U: bool = True):
+        """``trajectory_jvp`` for the chain of masses (include/mpcrl_chain_traj_jvp_ext.h mpcrl_chain_traj_jvp): (dX [B, N+1, nx] or
+        None, dU [B, N, nu] or None), how X* and U* of the last solve move when its initial state moves along dx0 [B, nx] and its
+        parameters along dtheta [B, n_p] or [n_p] (None = zeros, not both) — the forward mode of ``chain_trajectory_vjp``, one primal
+        Riccati solve per instance and direction on the workspace of that solve.  With R directions per instance, dx0 [B, R, nx] and
+        dtheta [B, R, n_p], the outputs are [B, R, N+1, nx] and [B, R, N, nu]; a result does not depend on R or on the place of its
+        direction.  dX[..., 0, :] is dx0.  Every entry of dtheta is read (m, D, L, C, Q, R, w).  The conditions are those of
+        ``chain_trajectory_vjp``: the solve is the last thing that touched the handle, and it ran without u0.  Rows of instances whose
+        status is neither 0 nor 2 are zeros."""
+        if not self._is_chain:
+            raise RuntimeError("chain_trajectory_jvp is for the chain of masses; the cartpole and the linear system have trajectory_jvp")
+        if not (self.has_iterate and self.duals_valid):
+            raise RuntimeError("chain_trajectory_jvp needs the iterate of a solve with its bound multipliers (solve with store_bounds=True first)")
+        if self._solve_status is not None and self._solve_q_mode:
+            raise RuntimeError("chain_trajectory_jvp after a solve with u0 fixed (Q mode) is not available")
+        if not self._chain_ws_current or self._solve_status is None:
+            raise RuntimeError("chain_trajectory_jvp reads the workspace of the last solve, and the handle was changed since (set_theta, "
+                               "set_bounds, set_discount_factor, reset or set_iterate): solve again first")
+        if dx0 is None and dtheta is None:
+            raise ValueError("chain_trajectory_jvp needs a direction: dx0, dtheta or both")
+        if not (X or U):
+            raise ValueError("chain_trajectory_jvp needs an output: X, U or both")
+        kw = dict(dtype=torch.float64, device=self.device)
+        dx0 = None if dx0 is None else torch.as_tensor(dx0, **kw)
+        dtheta = None if dtheta is None else torch.as_tensor(dtheta, **kw)
+        if dtheta is not None and dtheta.dim() == 1:      # one direction in theta for the whole batch
+            lead = (self.B,) if dx0 is None or dx0.dim() == 2 else (self.B, dx0.shape[1])
+            dtheta = dtheta.reshape((1,) * len(lead) + (self.n_p,)).expand(lead + (self.n_p,))
+        ranks = {t.dim() for t in (dx0, dtheta) if t is not None}
+        if ranks not in ({2}, {3}):
+            raise ValueError("chain_trajectory_jvp takes dx0 [B, nx] / dtheta [B, n_p] or dx0 [B, R, nx] / dtheta [B, R, n_p]")
+        single = ranks == {2}
+        R = 1 if single else (dx0 if dx0 is not None else dtheta).shape[1]
+        if R < 1:
+            raise ValueError("chain_trajectory_jvp needs at least one direction")
+        dx0 = None if dx0 is None else self._dev(dx0, (self.B, R, self.nx))
+        dtheta = None if dtheta is None else self._dev(dtheta, (self.B, R, self.n_p))
+        dX = torch.empty((self.B, R, self.N + 1, self.nx), **kw) if X else None
+        dU = torch.empty((self.B, R, self.N, self.nu), **kw) if U else None
+        self._call("mpcrl_chain_traj_jvp", 0, self._solve_status, R, dx0, dtheta, dX, dU)
+        if single:
+            dX, dU = (None if t is None else t[:, 0] for t in (dX, dU))
+        return dX, dU
+
+    def chain_trajectory_jacobian(self, entries=None) -> ChainTrajectoryJacobian:
+        """Columns of the Jacobian of the last chain solve's plan, d(X*, U*) / d(x0, theta[entries]), from ONE
+        ``chain_trajectory_jvp`` with nx + len(entries) unit directions.  ``entries``: an index array into p, or a tuple of block names
+        of ``chain_param_layout`` ("m", "D", "L", "C", "Q", "R", "w"); the default is the dynamics block ("m", "D", "L", "C").  The theta
+        blocks are compact, [B, N+1, nx, len(entries)] and [B, N, nu, len(entries)]: a block n_p wide is 12.7 MB per instance at
+        n_mass 7, N 40."""
+        if not self._is_chain:
+            raise RuntimeError("chain_trajectory_jacobian is for the chain of masses; the cartpole and the linear system have trajectory_jacobian")
+        idx = chain_jacobian_entries((self.nx // 3 - 1) // 2 + 2, entries)
+        ne, nx = len(idx), self.nx
+        kw = dict(dtype=torch.float64, device=self.device)
+        dx0 = torch.zeros((self.B, nx + ne, nx), **kw)
+        dth = torch.zeros((self.B, nx + ne, self.n_p), **kw)
+        dx0[:, :nx] = torch.eye(nx, **kw)
+        dth[:, nx + torch.arange(ne, device=self.device), torch.as_tensor(idx, device=self.device)] = 1.0
+        dX, dU = self.chain_trajectory_jvp(dx0, dth)
+        dX, dU = dX.permute(0, 2, 3, 1), dU.permute(0, 2, 3, 1)      # [B, N + 1, nx, R], [B, N, nu, R]
+        return ChainTrajectoryJacobian(dX[..., :nx].contiguous(), dU[..., :nx].contiguous(), dX[..., nx:].contiguous(),
+                                       dU[..., nx:].contiguous(), torch.as_tensor(idx, device=self.device))
 
     def bound_value_grad(self, q_mode: bool = False):
         """(dV_dlb, dV_dub), each [B, N+1, nu+nx] in stage-vector order v = [u; x] (the layout of one plane of ``get_iterate``'s bnd):

@@ -145,7 +145,7 @@ struct LargeLayout {
 };
 
 enum { ST_ACTIVE = 0, ST_IT = 1, ST_NIPM = 2, ST_TIGHT = 3, ST_STEPN = 4, ST_COST = 5, ST_RES = 6, ST_STATUS = 10,
-       ST_TRAJ = 11 };   // ST_STATUS: the du0*/dp factorisation was positive definite (0) or not (4); ST_TRAJ: the same of the trajectory VJP's own
+       ST_TRAJ = 11, ST_JVP = 12 };   // ST_STATUS: the du0*/dp factorisation was positive definite (0) or not (4); ST_TRAJ: the same of the trajectory VJP's own; ST_JVP: of the trajectory JVP's last direction
 
 template <class M, bool SECOND, bool TH_LDS>
 __device__ __forceinline__ void chain_point_body(const double *X, const double *U, const double *th, double *w, int N, int k, double h, int steps, double *lacc);

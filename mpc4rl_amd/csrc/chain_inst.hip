@@ -113,6 +113,36 @@ int launch_traj_vjp(MpcrlSolver *h, const int32_t *status, const double *gX, con
     return 0;
 }
 
+// The trajectory JVP of the handle's last solve (include/mpcrl_chain_traj_jvp_ext.h).  The exact Hessians and the point tables as in
+// launch_traj_vjp; then per direction the right-hand side from the point tables (only with dtheta) and the primal solve, in sequence on
+// the stream: the directions of an instance share its workspace (rt / rb, the gain rows of the stage blocks, Dx / Du).  2 ndir launches
+// (ndir without dtheta), two more when the adjoint is not current — whatever the horizon.  The dynamic LDS of the right-hand-side
+// kernel (3 NX doubles per lane) is less than the mixed-term kernel's (NTD + NX).
+template <class M>
+int launch_traj_jvp(MpcrlSolver *h, const int32_t *status, int ndir, const double *dx0, const double *dtheta, double *dX, double *dU,
+                    bool adjoint_current, hipStream_t st) {
+    const int B = h->B, N = h->N;
+    const LargeLds<M> lds(N);
+    if (!lds.fits()) return MPCRL_E_ARG;   // (mpcrl_create has checked: not reached)
+    LargeArgs a{};
+    a.B = B, a.theta_stride = h->theta_stride, a.theta = h->theta;
+    a.X = h->X, a.U = h->U, a.PI = h->PI, a.BND = h->BND, a.RES = h->RES, a.LAG = h->LAG;
+    a.ws = h->ws, a.ws_stride = h->ws_stride, a.status = const_cast<int32_t *>(status);
+    a.flags = MPCRL_SENS_PI, a.u0fix = nullptr;      // (as launch_traj_vjp)
+    if (!adjoint_current) {
+        hipLaunchKernelGGL((chain_point_kernel<M, true>), dim3((unsigned)B), dim3(64), lds.point, st, h->large, a);
+        hipLaunchKernelGGL(chain_sens_ad_kernel<M>, dim3((unsigned)(B * HexCfg<M>::groups(N))), dim3(64), 0, st, h->large, a);
+    }
+    const unsigned lds_rhs = (unsigned)(3 * M::NX * 64 * sizeof(double));
+    for (int d = 0; d < ndir; ++d) {
+        if (dtheta)
+            hipLaunchKernelGGL(chain_jvp_rhs_kernel<M>, dim3((unsigned)(((long)B * N + 63) / 64)), dim3(64), lds_rhs, st, h->large, a, dtheta, ndir, d);
+        hipLaunchKernelGGL(chain_traj_jvp_riccati_kernel<M>, dim3(B), dim3(64), lds.sqp, st, h->large, a, dx0, dtheta, dX, dU, ndir, d);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 size_t ws_doubles(int N) { return LargeLayout<Model>(N).total; }
 bool lds_fits(int N) { return LargeLds<Model>(N).fits(); }
 
@@ -136,6 +166,6 @@ constexpr int (*debug_phases)(unsigned long long *, int) = nullptr;
 #define MPCRL_CAT(a, b) MPCRL_CAT_(a, b)
 const MpcrlChainEntry *MPCRL_CAT(mpcrl_chain_entry_, MPCRL_CHAIN_NMASS)() {
     static const MpcrlChainEntry e = {MPCRL_CHAIN_NMASS, (long)Model::NP, ws_doubles, lds_fits, launch_large<Model>, debug_phases,
-                                     launch_policy_state_sens<Model>, launch_traj_vjp<Model>};
+                                     launch_policy_state_sens<Model>, launch_traj_vjp<Model>, launch_traj_jvp<Model>};
     return &e;
 }

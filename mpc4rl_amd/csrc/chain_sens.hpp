@@ -13,8 +13,12 @@
 //   chain_sens_mix2<M, 1>     lane per (instance, stage): the mixed term of that one solution
 //   chain_traj_out            workgroup per instance: g_theta and g_x0
 //   chain_bound_out           wavefront per instance: g_lb and g_ub of include/mpcrl_bound_ext.h from the same solution
+// and the forward mode of include/mpcrl_chain_traj_jvp_ext.h, per direction:
+//   chain_jvp_rhs             lane per (instance, stage): the directional derivative of the KKT residual, the transpose of chain_sens_mix2<M, 1>
+//   chain_traj_jvp_riccati    wavefront per instance: the same matrix, one PRIMAL solve (factor sweep + the QP's forward sweep)
 // They re-use [B A], lam, t, nu left in the workspace by the last SQP round (its linearisation is at the final iterate).
 #pragma once
+#include "chain_jvp_rhs.hpp"
 #include "chain_linearise.hpp"
 
 namespace mpcrl {
@@ -516,6 +520,121 @@ __global__ void __launch_bounds__(64) chain_sens_mix2_kernel(const LargeSpec sp,
     double *term2 = w + (TRAJ ? lay.tterm : lay.term2) + ((size_t)iu * N + k) * NTD;
 #pragma unroll
     for (int d = 0; d < NTD; ++d) term2[d] = thd[d * 64];
+}
+
+// ---- the trajectory JVP (include/mpcrl_chain_traj_jvp_ext.h): dw = -(dR/dz)^-1 (dR/dtheta dtheta + dR/dx0 dx0) restricted to w = (U, X),
+// on the matrix chain_traj_riccati_kernel factors.  Per direction two launches that share the instance's workspace:
+//   chain_jvp_rhs              lane per (instance, stage): the dynamics entries of dtheta -> b_k (rb) and g_k (rt, stages < N), the
+//                              transpose of chain_sens_mix2_kernel<M, 1> on the same point tables (chain_jvp_rhs.hpp)
+//   chain_traj_jvp_riccati     wavefront per instance: the cost rows and the x0 terms on top, one factorisation, one forward sweep
+// The right-hand side lives in rt / rb, which every factorisation of the solve and of the VJP fills before it reads them.
+template <class M>
+__global__ void __launch_bounds__(64) chain_jvp_rhs_kernel(const LargeSpec sp, const LargeArgs a, const double *__restrict__ dtheta,
+                                                           const int ndir, const int dir) {
+    constexpr int NX = M::NX, NW = NX + M::NU, NL = M::NL, TAB2 = M::TAB2;
+    extern __shared__ double sm[];      // per lane, [index][lane]: the three scratch vectors of chain_jvp_rhs_lane (3 NX doubles)
+    const int N = sp.N, lane = threadIdx.x;
+    const long gid = (long)blockIdx.x * 64 + threadIdx.x;
+    const int inst = (int)(gid / N);
+    if (inst >= a.B) return;
+    const int status = a.status[inst];
+    if (!(status == 0 || status == 2)) return;
+    const int k = (int)(gid - (long)inst * N);
+    const LargeLayout<M> lay(N);
+    double *w = a.ws + (size_t)inst * a.ws_stride;
+    const double *th = a.theta + (size_t)inst * a.theta_stride;
+    const double *dth = dtheta + ((size_t)inst * ndir + dir) * M::NP;
+    double *scr = sm + lane;
+    chain_jvp_rhs_lane<M>(w + lay.ptab + (size_t)k * 8 * NL * TAB2, w + lay.gtab + (size_t)k * 8 * NL * 6, w + lay.qvtab + (size_t)k * 8 * NL * 6,
+                          th, dth, sp.h, sp.rk_steps, [scr](int slot, int i) -> double & { return scr[(slot * NX + i) * 64]; }, w + lay.rb + (size_t)k * NX,
+                          w + lay.rt + (size_t)k * NW);
+}
+
+// The primal solve of one direction: K dw = -[g; -b] with K the exact-Hessian barrier KKT matrix of chain_traj_riccati_kernel (same
+// guard on the status, same capped barrier diagonal, same terminal Hessian, u_0 free), as the QP of an SQP round is solved: the
+// factor sweep that leaves -K_k in the stage blocks, then forward2, whose recursion dx_{k+1} = b_k + A dx_k + B du_k carries the
+// dynamics offset the adjoint sweeps do not have.  The right-hand side on top of what chain_jvp_rhs_kernel left (zeros without dtheta):
+//   g_k[x] += c_k 1/2 (dQ + dQ') (x_k - x_ss), k = 1 .. N;   g_k[u] += c_k 1/2 (dR + dR') u_k, k < N      (chain_traj_out_kernel's closed forms)
+//   g_0[u] += Hex_0[u, x] dx0,   b_0 += A_0 dx0                                                          (x_0 is eliminated)
+// Out: dX[b, dir] (row 0 = dx0) and dU[b, dir], written in full by every call: the values for status 0 / 2, zeros otherwise, NaN
+// where the factorisation is not positive definite (its verdict also goes to ST_JVP).
+template <class M>
+__global__ void __launch_bounds__(64, 1) chain_traj_jvp_riccati_kernel(const LargeSpec sp, const LargeArgs a, const double *__restrict__ dx0,
+                                                                       const double *__restrict__ dtheta, double *__restrict__ dX,
+                                                                       double *__restrict__ dU, const int ndir, const int dir) {
+    using Cfg = ChainCfg<M>;
+    constexpr int NX = M::NX, NU = M::NU, NW = NX + NU, NT = 64;
+    extern __shared__ __attribute__((aligned(16))) double lds[];      // Cfg::lds_doubles(N) doubles (launch_traj_jvp)
+    __shared__ int sidx[196];
+    const int lane = threadIdx.x, inst = blockIdx.x, N = sp.N;
+    const size_t row = (size_t)inst * ndir + dir;
+    double *ox = dX ? dX + row * (N + 1) * NX : nullptr, *ou = dU ? dU + row * N * NU : nullptr;
+    const int status = a.status[inst];
+    if (!(status == 0 || status == 2)) {
+        if (ox)
+            for (int e = lane; e < (N + 1) * NX; e += NT) ox[e] = 0.0;
+        if (ou)
+            for (int e = lane; e < N * NU; e += NT) ou[e] = 0.0;
+        return;
+    }
+    ChainSolver<M> S(sp, lane);
+    S.th = a.theta + (size_t)inst * a.theta_stride;
+    S.qmode = false;      // u_0 is free (after a Q-mode solve: at the pinned value)
+    const LargeLayout<M> lay(N);
+    double *w = a.ws + (size_t)inst * a.ws_stride;
+    S.bind_workspace(w, lay);
+    S.setup(lds, sidx);
+    S.X = a.X + (size_t)inst * (N + 1) * NX, S.U = a.U + (size_t)inst * N * NU;
+    const int ne = (N + 1) * NW;
+    const double *th = S.th, *xs = sp.consts;
+    const WsArr Hex{(char *)w, (unsigned)lay.Hex};
+    for (int e = lane; e < NW * NW; e += NT) Hex[N * NW * NW + e] = S.ck(N) * M::hess(true, e / NW, e % NW, th);
+    for (int e = lane; e < ne; e += NT) {      // the capped barrier diagonal of chain_sens_riccati_kernel
+        const int k = e / NW, i = e - k * NW;
+        double d = 0.0;
+        if (!S.skipc(k, i))
+            for (int sd = 0; sd < 2; ++sd)
+                if (S.has(sd, k, i)) d += fmin(S.LAM(sd, e) / S.TT(sd, e), SENS_W_MAX);
+        S.Dg[e] = d;
+    }
+    const double *dth = dtheta ? dtheta + row * M::NP : nullptr, *vx = dx0 ? dx0 + (size_t)row * NX : nullptr;
+    for (int e = lane; e < ne; e += NT) {      // stationarity rows: what the point tables gave, the cost rows, the x0 term of stage 0
+        const int k = e / NW, i = e - k * NW;
+        double v = 0.0;
+        if (i < NU) {
+            if (k < N) {
+                if (dth) {
+                    v = S.rt[e];
+                    double c = 0.0;
+                    for (int j = 0; j < NU; ++j) c = fma(0.5 * (dth[M::OFF_R + j * NU + i] + dth[M::OFF_R + i * NU + j]), S.U[k * NU + j], c);
+                    v = fma(S.ck(k), c, v);
+                }
+                if (vx && k == 0)
+                    for (int j = 0; j < NX; ++j) v = fma(Hex[i * NW + NU + j], vx[j], v);
+            }
+        } else if (k > 0 && dth) {      // (the state rows of stage 0 stay zero: x_0 is eliminated)
+            const int ix = i - NU;
+            if (k < N) v = S.rt[e];
+            double c = 0.0;
+            for (int j = 0; j < NX; ++j) c = fma(0.5 * (dth[M::OFF_Q + j * NX + ix] + dth[M::OFF_Q + ix * NX + j]), S.X[k * NX + j] - xs[j], c);
+            v = fma(S.ck(k), c, v);
+        }
+        S.rt[e] = v;
+    }
+    for (int e = lane; e < N * NX; e += NT) {      // dynamics rows
+        double v = dth ? S.rb[e] : 0.0;
+        if (vx && e < NX)
+            for (int j = 0; j < NX; ++j) v = fma(S.BA[e * NW + NU + j], vx[j], v);
+        S.rb[e] = v;
+    }
+    wave_sync();
+    const bool okall = ChainSolver<M>::factor_gain_call(S.ctx(), Hex.off, S.rt.off, S.rb.off);
+    ChainSolver<M>::forward_call(S.ctx(), S.rb.off);
+    if (lane == 0) S.state[ST_JVP] = okall ? 0.0 : 4.0;
+    if (ox)
+        for (int e = lane; e < (N + 1) * NX; e += NT) ox[e] = okall ? (e < NX ? (vx ? vx[e] : 0.0) : S.Dx[e]) : NAN;
+    if (ou)
+        for (int e = lane; e < N * NU; e += NT) ou[e] = okall ? S.Du[e] : NAN;
 }
 
 // One output element per lane: slot 0 = dV/dp (with MPCRL_SENS_V), slots 1..NU = rows of du0*/dp (with MPCRL_SENS_PI).

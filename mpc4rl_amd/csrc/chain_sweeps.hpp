@@ -1839,6 +1839,15 @@ struct ChainSolver {
         hs.init(S, hex_off);
         return S.template factor2<HS, !std::is_same<HS, HessConst<M>>::value>(hs, S.arr(g_off), S.arr(bb_off));
     }
+    // the exact-Hessian factorisation in the QP's form (SENS = false: -K_k into the stage blocks, kff_k and p_k from the vector column,
+    // nothing streamed to G2 / P2) for a right-hand side with a dynamics offset: forward2 follows (the trajectory JVP, chain_sens.hpp).
+    // The path is the one of the SQP's QPs; M = H + D + W' T takes every tile of H from the Hessian source, cross blocks included.
+    __device__ MPCRL_PHASE_FN static bool factor_gain_call(Ctx c, unsigned hex_off, unsigned g_off, unsigned bb_off) {
+        ChainSolver S = from_ctx(c);
+        HessGlobal<M> hs;
+        hs.init(S, hex_off);
+        return S.template factor2<HessGlobal<M>, false>(hs, S.arr(g_off), S.arr(bb_off));
+    }
     __device__ MPCRL_PHASE_FN static void backward_vec_call(Ctx c, unsigned g_off) {
         ChainSolver S = from_ctx(c);
         S.backward_vec2(S.arr(g_off));

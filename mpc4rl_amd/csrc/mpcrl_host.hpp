@@ -76,6 +76,10 @@ struct MpcrlChainEntry {
     // null for mpcrl_chain_traj_vjp): the bound rows contracted with the same solution, one launch more
     int (*traj_vjp)(MpcrlSolver *h, const int32_t *status, const double *gX, const double *gU, double *g_x0, double *g_theta,
                     double *g_lb, double *g_ub, bool adjoint_current, hipStream_t st);
+    // trajectory JVP of the last solve (mpcrl_chain_traj_jvp): per direction the right-hand side and one primal Riccati solve, the
+    // second-order point pass and the exact Hessians in front of them unless that solve left them
+    int (*traj_jvp)(MpcrlSolver *h, const int32_t *status, int ndir, const double *dx0, const double *dtheta, double *dX, double *dU,
+                    bool adjoint_current, hipStream_t st);
 };
 const MpcrlChainEntry *mpcrl_chain_entry_3(), *mpcrl_chain_entry_4(), *mpcrl_chain_entry_5(), *mpcrl_chain_entry_6(), *mpcrl_chain_entry_7();
 // n_mass (3 .. 7, a free integer in the reference: rlmpc/mpc/chain_mass/ocp_utils.py:344-350) -> the translation unit of that chain size

@@ -2,7 +2,8 @@
 // stores; include/mpcrl_chain_ext.h and include/mpcrl_chain_traj_ext.h: du0*/dx0 and the trajectory VJP of the chain, from the workspace
 // of its last solve (kernels and launches: chain_sens.hpp, chain_inst.hip); include/mpcrl_bound_ext.h: the derivatives with respect to
 // the box bounds (bound_vjp_kernel.hpp, and the chain's launcher with its bound outputs); include/mpcrl_cost_ext.h: the derivatives with
-// respect to the cartpole's tracking cost (cost_vjp_kernel.hpp); include/mpcrl_traj_jvp_ext.h: the trajectory JVP (traj_jvp_kernel.hpp).  The kernels are state_sens_kernel.hpp; this unit instantiates them for the cartpole, the linear system and every chain
+// respect to the cartpole's tracking cost (cost_vjp_kernel.hpp); include/mpcrl_traj_jvp_ext.h: the trajectory JVP (traj_jvp_kernel.hpp);
+// include/mpcrl_chain_traj_jvp_ext.h: the chain's (chain_sens.hpp, chain_inst.hip).  The kernels are state_sens_kernel.hpp; this unit instantiates them for the cartpole, the linear system and every chain
 // size, and launches them.  Nothing here allocates or waits: two launches (or one and a memset) on the caller's stream.
 #include "mpcrl_host.hpp"
 
@@ -12,6 +13,7 @@
 #include "../../include/mpcrl_cost_ext.h"
 #include "../../include/mpcrl_traj_ext.h"
 #include "../../include/mpcrl_traj_jvp_ext.h"
+#include "../../include/mpcrl_chain_traj_jvp_ext.h"
 #include "state_sens_kernel.hpp"
 #include "traj_vjp_kernel.hpp"
 #include "bound_vjp_kernel.hpp"
@@ -187,6 +189,21 @@ int mpcrl_chain_traj_vjp(mpcrl_handle h, int flags, const int32_t *status, const
     ON_DEVICE(h->device);
     // the solution and its parameter terms have a region of their own in the workspace: chain_adjoint_current stays as it is
     return e->traj_vjp(h, status, gX, gU, g_x0, g_theta, nullptr, nullptr, h->chain_adjoint_current, (hipStream_t)stream);
+}
+
+int mpcrl_chain_traj_jvp_ext_version(void) { return MPCRL_CHAIN_TRAJ_JVP_EXT_VERSION; }
+
+int mpcrl_chain_traj_jvp(mpcrl_handle h, int flags, const int32_t *status, int ndir, const double *dx0, const double *dtheta, double *dX,
+                         double *dU, void *stream) {
+    if (!h || flags) return MPCRL_E_ARG;   // (MPCRL_STATE_Q_MODE included, as in mpcrl_chain_traj_vjp)
+    if (!h->is_large) return MPCRL_E_MODEL;
+    if (!status || ndir < 1 || (!dx0 && !dtheta) || (!dX && !dU)) return MPCRL_E_ARG;
+    if (!h->chain_ws_current) return MPCRL_E_ARG;
+    const MpcrlChainEntry *e = chain_entry(h->n_mass);
+    if (!e) return MPCRL_E_MODEL;
+    ON_DEVICE(h->device);
+    // the right-hand side and the solution live in regions every factorisation fills before it reads them: chain_adjoint_current stays
+    return e->traj_jvp(h, status, ndir, dx0, dtheta, dX, dU, h->chain_adjoint_current, (hipStream_t)stream);
 }
 
 int mpcrl_bound_ext_version(void) { return MPCRL_BOUND_EXT_VERSION; }
