@@ -1,4 +1,4 @@
-"""ctypes binding of libmpcrl_hip.so, read from include/mpcrl.h (and include/mpcrl_ext.h, include/mpcrl_chain_ext.h, include/mpcrl_traj_ext.h, include/mpcrl_chain_traj_ext.h, include/mpcrl_bound_ext.h, include/mpcrl_cost_ext.h, include/mpcrl_traj_jvp_ext.h, include/mpcrl_chain_traj_jvp_ext.h and include/mpcrl_probe_ext.h, a table of its own each), and the one path the package calls the library through
+"""ctypes binding of libmpcrl_hip.so, read from include/mpcrl.h (and include/mpcrl_ext.h, include/mpcrl_chain_ext.h, include/mpcrl_traj_ext.h, include/mpcrl_chain_traj_ext.h, include/mpcrl_bound_ext.h, include/mpcrl_cost_ext.h, include/mpcrl_traj_jvp_ext.h, include/mpcrl_chain_traj_jvp_ext.h, include/mpcrl_probe_ext.h and include/mpcrl_probe_chain_ext.h, a table of its own each), and the one path the package calls the library through
 (``call``, ``workspace``).  Fails loudly when the library is missing.
 
 The .hip units include the same header, so the compiler holds the implementation to it; the prototypes, constants and error codes here
@@ -148,6 +148,13 @@ with open(PROBE_EXT_HEADER_PATH) as _f:
 PROBE_EXT_EXPORTS = list(PROBE_EXT_HEADER.functions)
 PROBE_EXT_VERSION = PROBE_EXT_HEADER.constants["PROBE_EXT_VERSION"]
 PROBE_MX_SLOT, PROBE_MX_PIN, PROBE_MX_WANT_P = (PROBE_EXT_HEADER.constants[n] for n in ("PROBE_MX_SLOT", "PROBE_MX_PIN", "PROBE_MX_WANT_P"))
+PROBE_CHAIN_EXT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mpcrl_probe_chain_ext.h")   # the test probe of the vector sweeps' chains, versioned on its own
+if not os.path.exists(PROBE_CHAIN_EXT_HEADER_PATH):
+    raise ImportError(f"mpc4rl_amd: {PROBE_CHAIN_EXT_HEADER_PATH} not found. The binding is read from the headers: keep include/ beside the package.")
+with open(PROBE_CHAIN_EXT_HEADER_PATH) as _f:
+    PROBE_CHAIN_EXT_HEADER = parse_header(_f.read())      # a table of its own (the #include of mpcrl_probe_ext.h is not followed)
+PROBE_CHAIN_EXT_EXPORTS = list(PROBE_CHAIN_EXT_HEADER.functions)
+PROBE_CHAIN_EXT_VERSION = PROBE_CHAIN_EXT_HEADER.constants["PROBE_CHAIN_EXT_VERSION"]
 
 
 def _constants(names: str):
@@ -253,13 +260,19 @@ def load():
         if not older and lib.mpcrl_probe_ext_version() != PROBE_EXT_VERSION:
             raise RuntimeError(f"mpc4rl_amd: {LIB_PATH} reports probe extension version {lib.mpcrl_probe_ext_version()}, this binding expects "
                                f"{PROBE_EXT_VERSION}; rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`).")
+    if not (older and not hasattr(lib, "mpcrl_probe_chain_ext_version")):
+        lib.mpcrl_probe_chain_ext_version.restype = C.c_int
+        if not older and lib.mpcrl_probe_chain_ext_version() != PROBE_CHAIN_EXT_VERSION:
+            raise RuntimeError(f"mpc4rl_amd: {LIB_PATH} reports chain probe extension version {lib.mpcrl_probe_chain_ext_version()}, this binding "
+                               f"expects {PROBE_CHAIN_EXT_VERSION}; rebuild it (`python -c 'import __graft_entry__ as g; g.build()'`).")
     for name, (ret, params) in (list(HEADER.functions.items()) + list(EXT_HEADER.functions.items()) + list(CHAIN_EXT_HEADER.functions.items())
                                 + list(TRAJ_EXT_HEADER.functions.items()) + list(CHAIN_TRAJ_EXT_HEADER.functions.items())
                                 + list(BOUND_EXT_HEADER.functions.items()) + list(COST_EXT_HEADER.functions.items())
                                 + list(TRAJ_JVP_EXT_HEADER.functions.items()) + list(CHAIN_TRAJ_JVP_EXT_HEADER.functions.items())
-                                + list(PROBE_EXT_HEADER.functions.items())):
+                                + list(PROBE_EXT_HEADER.functions.items()) + list(PROBE_CHAIN_EXT_HEADER.functions.items())):
         if older and (name in BOUND_EXT_HEADER.functions or name in COST_EXT_HEADER.functions or name in TRAJ_JVP_EXT_HEADER.functions
-                      or name in CHAIN_TRAJ_JVP_EXT_HEADER.functions or name in PROBE_EXT_HEADER.functions) and not hasattr(lib, name):
+                      or name in CHAIN_TRAJ_JVP_EXT_HEADER.functions or name in PROBE_EXT_HEADER.functions
+                      or name in PROBE_CHAIN_EXT_HEADER.functions) and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         fn.restype = _CTYPE[ret]

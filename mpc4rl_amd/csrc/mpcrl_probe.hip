@@ -1,10 +1,12 @@
-// mpcrl_probe.hip — include/mpcrl_probe_ext.h: test probes of single phases of the solve kernels.  One wavefront, one launch; the shipped
-// form of a phase against a reference copy of an earlier form that lives in this unit only (tests/test_gpu_mx_factor_step.py).
+// mpcrl_probe.hip — include/mpcrl_probe_ext.h, include/mpcrl_probe_chain_ext.h: test probes of single phases of the solve kernels.  One wavefront, one launch; the shipped
+// form of a phase against a reference copy of an earlier form that lives in this unit only (tests/test_gpu_mx_factor_step.py,
+// tests/test_gpu_mx_chain_step.py).
 #include "mpcrl_host.hpp"
 
 #include <cstring>
 
 #include "../../include/mpcrl_probe_ext.h"
+#include "../../include/mpcrl_probe_chain_ext.h"
 #include "small_kernel.hpp"
 
 using namespace mpcrl;
@@ -117,6 +119,76 @@ __global__ void __launch_bounds__(64) mx_factor_probe_kernel(SmallSpec sp, const
     if (lane < 4) ok[lane] = lds[S_t::mxFlag + lane];
 }
 
+// The affine chain as it was before its last turns were peeled and the addresses of its loop written out: a verbatim copy (every
+// fetch clamps its stage with slot_of; MPCRL_CHAIN_DEPTH at its value of that time), with the slot layout it reads — the one of
+// small_kernel.hpp at that time, which the chains have kept (profiles/chain_step.txt).
+struct MxChainBefore : SmallSolver<CartpoleDev> {
+    using M = CartpoleDev;
+    MPCRL_DI MxChainBefore(const SmallSpec &sp_, int k_, int lpi_, int base_) : SmallSolver<CartpoleDev>(sp_, k_, lpi_, base_) {}
+    template <bool FWD>
+    MPCRL_DI void mx_chain() {
+        const int l = threadIdx.x & 63, r = l >> 4, blk = (l >> 2) & 3, c = l & 3;
+        const int ipw = min(64 / lpi, M::MAX_IPW);
+        const bool live = blk < ipw;
+        const double *S0 = ms + (live ? blk : 0) * lpi * MSLOT;
+        const int oA = mxAH + (FWD ? 2 * (4 * c + r) : 2 * (4 * r + c)), oBx = mxCol + 4 * (FWD ? c : r), oKx = mxK + (FWD ? r : c),
+                  oC = mxCol + 4 * r + 3;
+        const bool wr = live && c == 0;
+        double *const wO = wr ? ms + (S0 - ms) + (FWD ? mxRow + 2 * r + 1 : mxCol + 4 * r + 1) : ms + mxDump;
+        const int sO = wr ? MSLOT : 0;
+        double V = 0.0;
+        if constexpr (!FWD) {
+            V = S0[N * MSLOT + oC];
+            wO[N * sO] = V;   // p_N
+        }
+        constexpr int DEPTH = 3;
+        auto slot_of = [&](int s_) { const int sc = s_ < N ? s_ : N - 1; return FWD ? sc : N - 1 - sc; };   // stage of chain step s_ (clamped)
+        double Ar[DEPTH], Br_[DEPTH], Kr_[DEPTH], Cr[DEPTH];
+        auto fetch = [&](int j, int s_) {
+            const double *sl = S0 + slot_of(s_) * MSLOT;
+            Ar[j] = sl[oA], Br_[j] = sl[oBx], Kr_[j] = sl[oKx], Cr[j] = sl[oC];
+        };
+#pragma unroll
+        for (int j = 0; j < DEPTH; ++j) fetch(j, j);
+        int s_ = 0;
+        for (; s_ + DEPTH <= N; s_ += DEPTH) {
+#pragma unroll
+            for (int j = 0; j < DEPTH; ++j) {
+                V = mfma4(fma(-Br_[j], Kr_[j], Ar[j]), V, Cr[j]);
+                wO[(FWD ? slot_of(s_ + j) + 1 : slot_of(s_ + j)) * sO] = V;
+                fetch(j, s_ + j + DEPTH);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < DEPTH - 1; ++j)
+            if (s_ + j < N) {
+                V = mfma4(fma(-Br_[j], Kr_[j], Ar[j]), V, Cr[j]);
+                wO[(FWD ? slot_of(s_ + j) + 1 : slot_of(s_ + j)) * sO] = V;
+            }
+    }
+};
+
+// Every lane copies its slot in, the wavefront runs one chain, every lane copies its slot out.
+template <bool FWD>
+__global__ void __launch_bounds__(64) mx_chain_probe_kernel(SmallSpec sp, const double *in, int which, double *out) {
+    using S_t = MxChainBefore;
+    __shared__ __attribute__((aligned(16))) double lds[S_t::MX_LDS];
+    const int lane = threadIdx.x, lpi = sp.N + 1, slot = lane / lpi, k = lane - slot * lpi;
+    S_t S(sp, k, lpi, slot * lpi);
+    S.ms = lds;
+    double *sl = lds + lane * S_t::MSLOT;
+    for (int i = 0; i < S_t::MSLOT; ++i) sl[i] = in[lane * S_t::MSLOT + i];
+    if (lane < 4) lds[S_t::mxFlag + lane] = -1.0;
+    if (lane < 2) lds[S_t::mxDump + lane] = 0.0;
+    S_t::wave_lds_sync();
+    if (which == 0)   // (wave-uniform)
+        S.template mx_chain<FWD>();
+    else
+        S.SmallSolver<CartpoleDev>::template mx_chain<FWD>();
+    S_t::wave_lds_sync();
+    for (int i = 0; i < S_t::MSLOT; ++i) out[lane * S_t::MSLOT + i] = sl[i];
+}
+
 }  // namespace
 
 extern "C" {
@@ -136,6 +208,23 @@ int mpcrl_debug_mx_factor(const double *slots_in, int N, int flags, int which, d
         hipLaunchKernelGGL(mx_factor_probe_kernel<true>, dim3(1), dim3(64), 0, st, sp, slots_in, pin, which, slots_out, ok_out);
     else
         hipLaunchKernelGGL(mx_factor_probe_kernel<false>, dim3(1), dim3(64), 0, st, sp, slots_in, pin, which, slots_out, ok_out);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int mpcrl_probe_chain_ext_version(void) { return MPCRL_PROBE_CHAIN_EXT_VERSION; }
+
+int mpcrl_debug_mx_chain(const double *slots_in, int N, int forward, int which, double *slots_out, void *stream) {
+    if (!slots_in || !slots_out || N < 1 || N > 63 || which < 0 || which > 1 || forward < 0 || forward > 1) return MPCRL_E_ARG;
+    ON_DEVICE_OF(slots_out);
+    const hipStream_t st = (hipStream_t)stream;
+    SmallSpec sp;
+    std::memset(&sp, 0, sizeof(sp));
+    sp.N = N;
+    if (forward)
+        hipLaunchKernelGGL(mx_chain_probe_kernel<true>, dim3(1), dim3(64), 0, st, sp, slots_in, which, slots_out);
+    else
+        hipLaunchKernelGGL(mx_chain_probe_kernel<false>, dim3(1), dim3(64), 0, st, sp, slots_in, which, slots_out);
     HIP_OK(hipGetLastError());
     return 0;
 }

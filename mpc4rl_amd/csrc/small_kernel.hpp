@@ -623,7 +623,7 @@ struct SmallSolver {
     //   forward   Dx_{k+1} = Acl_k Dx_k + d_k,                 d_k = bb_k - B_k kff_k
     //   backward  p_k      = Acl_k' p_{k+1} + c_k,             c_k = q_k + g_x - K_k' g_u     (q_k does not depend on the right-hand side)
     // and everything off the chain is stage-parallel in the stage lanes: Du_k = -K_k Dx_k - kff_k, the corrector's
-    // kff_k = (g_u + beta_k + B_k' p_{k+1}) / R_k, Dnu_k = P_k Dx_k + p_k.  A chain step is ~8 instructions against 45 (forward) / 60
+    // kff_k = (g_u + beta_k + B_k' p_{k+1}) / R_k, Dnu_k = P_k Dx_k + p_k.  A chain step is 13 instructions (see mx_chain) against 45 (forward) / 60
     // (backward) of the stage-layout sweeps they replace, and the stage lanes no longer hold K, kff, 1/R, P, p (20 doubles).
     static constexpr bool MX = (NX == 4 && NU == 1);
     // Slot of one stage (doubles; 16-byte aligned pairs so that one ds_read_b128 brings two operands — LDS instructions, not
@@ -833,29 +833,51 @@ struct SmallSolver {
 #define MPCRL_CHAIN_DEPTH 3   // measured: 3 beats 2 and 4 (4 costs registers the kernel does not have)
 #endif
         constexpr int DEPTH = MPCRL_CHAIN_DEPTH;
-        auto slot_of = [&](int s_) { const int sc = s_ < N ? s_ : N - 1; return FWD ? sc : N - 1 - sc; };   // stage of chain step s_ (clamped)
+        auto slot_of = [&](int s_) { return FWD ? s_ : N - 1 - s_; };   // stage of chain step s_ (0 <= s_ < N)
         double Ar[DEPTH], Br_[DEPTH], Kr_[DEPTH], Cr[DEPTH];
         auto fetch = [&](int j, int s_) {
             const double *sl = S0 + slot_of(s_) * MSLOT;
             Ar[j] = sl[oA], Br_[j] = sl[oBx], Kr_[j] = sl[oKx], Cr[j] = sl[oC];
         };
+        auto step = [&](int j, int s_) {
+            V = mfma4(fma(-Br_[j], Kr_[j], Ar[j]), V, Cr[j]);
+            wO[(FWD ? slot_of(s_) + 1 : slot_of(s_)) * sO] = V;
+        };
+        // Only the fill of the ring can ask for a step past the last (N < DEPTH) and clamps.  The loop runs while the step it fetches
+        // exists, so no fetch in it clamps or selects: a turn costs 13 instructions a step (3 or 4 LDS reads, the store, fma, MFMA,
+        // 8 address adds a turn) where a clamp per fetch cost 19 (profiles/chain_step.txt).  The last DEPTH .. 2 DEPTH - 1 steps (all N
+        // of a horizon shorter than the ring) are peeled: those that exist, fetching only what exists.
 #pragma unroll
-        for (int j = 0; j < DEPTH; ++j) fetch(j, j);
+        for (int j = 0; j < DEPTH; ++j) fetch(j, j < N ? j : N - 1);
         int s_ = 0;
-        for (; s_ + DEPTH <= N; s_ += DEPTH) {
+        {
+            // the lane's four operand addresses and its store address walk from turn to turn; within a turn the stages are constants
+            // (written out so: left to the compiler, the slot index times MSLOT was added to six bases a turn)
+            constexpr int dT = (FWD ? DEPTH : -DEPTH) * MSLOT, lo = FWD ? 0 : DEPTH - 1;   // (lo: the turn's lowest slot is its base)
+            const double *sT = S0 + slot_of(DEPTH + lo) * MSLOT;
+            const double *fA = sT + oA, *fB = sT + oBx, *fK = sT + oKx, *fC = sT + oC;
+            double *fO = wO + (FWD ? 1 : N - DEPTH) * sO;
+            for (; s_ + 2 * DEPTH <= N; s_ += DEPTH) {
 #pragma unroll
-            for (int j = 0; j < DEPTH; ++j) {
-                V = mfma4(fma(-Br_[j], Kr_[j], Ar[j]), V, Cr[j]);
-                wO[(FWD ? slot_of(s_ + j) + 1 : slot_of(s_ + j)) * sO] = V;
-                fetch(j, s_ + j + DEPTH);
+                for (int j = 0; j < DEPTH; ++j) {
+                    const int o = (FWD ? j : DEPTH - 1 - j);
+                    V = mfma4(fma(-Br_[j], Kr_[j], Ar[j]), V, Cr[j]);
+                    fO[o * sO] = V;
+                    Ar[j] = fA[o * MSLOT], Br_[j] = fB[o * MSLOT], Kr_[j] = fK[o * MSLOT], Cr[j] = fC[o * MSLOT];
+                }
+                fA += dT, fB += dT, fK += dT, fC += dT;
+                fO += (FWD ? DEPTH : -DEPTH) * sO;
             }
         }
 #pragma unroll
-        for (int j = 0; j < DEPTH - 1; ++j)
+        for (int j = 0; j < DEPTH; ++j)
             if (s_ + j < N) {
-                V = mfma4(fma(-Br_[j], Kr_[j], Ar[j]), V, Cr[j]);
-                wO[(FWD ? slot_of(s_ + j) + 1 : slot_of(s_ + j)) * sO] = V;
+                step(j, s_ + j);
+                if (j < DEPTH - 1 && s_ + j + DEPTH < N) fetch(j, s_ + j + DEPTH);
             }
+#pragma unroll
+        for (int j = 0; j < DEPTH - 1; ++j)
+            if (s_ + j + DEPTH < N) step(j, s_ + j + DEPTH);
     }
     // Predictor / adjoint solve: publish, factor, forward chain; the stage lane gets Dx, Du (and with WANT_P the factors needed for
     // Dnu, see mx_dnu).  Returns false where the factorisation met a non-positive pivot.
